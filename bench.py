@@ -10,12 +10,19 @@ leaves the bf16 mu / sigma^2 operand shadows and the prior statistics for the ne
 before the first step (`--prepare-each-step` puts it back into the step: round 1's protocol). `--with-update`
 times the whole training step (step + update) beside it. Inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config wide|small|deep]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config wide|small|deep] [--dump-outputs DIR] [--full]
 N > 1: launched by the driver through torch.distributed.run (one rank per GPU, RCCL) -- or, from a bare shell, by
 bench.py itself: a parent that has not imported torch or touched HIP starts the same torch.distributed.run line as a
-CHILD process, relays its output and exits with its code. The timed region is `--repeats` (7) blocks of exactly K
-steps, each bracketed by barrier + synchronize (wall clock, MAX over ranks) and by HIP events; `ms_per_step` is the
-median block. Prints ONE JSON line on rank 0.
+CHILD process, relays its output and exits with its code. The timed region is `--repeats` blocks of exactly K steps
+(one block by default: K timed steps; seven with --full), each bracketed by barrier + synchronize (wall clock, MAX over
+ranks) and by HIP events; `ms_per_step` is the median block. Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, the warm-up (W steps, more until 0.2 s have passed: the clock
+ramp; --full warms up for W steps exactly), the timed steps, the line. Everything else the line can carry -- the box probes, the per-kernel roofline and the
+probed block, the training step, the CPU baseline, the reporting (fp32) and deep configurations, the multi-rank exchange
+figures and the sharded-update row -- is measured with --full only. --dump-outputs DIR writes, after the timed steps,
+what the last timed step computed (the gradient arena's blocks, the loss and the hit count) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -118,7 +125,7 @@ def measured_traffic(kernel_name, cfg_name):
 
 
 def box_calibration(L, ctx_handle):
-    """Two fixed probes of THIS box, run in this process (vbnn_box_calibrate, csrc/calib.hip; ~40 ms): a register-only MFMA loop
+    """Two fixed probes of THIS box, run in this process (vbnn_box_calibrate, csrc/calib.hip; ~70 ms): a register-only MFMA loop
     on every SIMD -> the clock the chip holds under a pure matrix load and the MFMA rate it reaches there; a 512 MiB -> 512 MiB
     copy -> the HBM rate. The boxes of a pool differ by 5-7 % on one binary: with these a round-to-round delta of the line
     can be read as code or as box."""
@@ -511,6 +518,36 @@ def self_launch(n, argv):
     return subprocess.call(cmd, env=env)
 
 
+WARMUP_MIN_S = 0.2                    # a plain run's warm-up lasts at least this long, whatever --warmup asks for
+DUMP_BUDGET_FLOATS = 8 << 20          # 32 MB of float32 in all: a larger block is written as a fixed, seeded sample
+DUMP_SMALL = 1 << 16                  # blocks up to this many elements are written whole
+
+
+def dump_outputs(eng, loss, correct, out_dir, torch):
+    """What a caller of the timed path receives after its last step, as <out_dir>/<name>.npy: every block of the gradient arena
+    (per VB layer gradWeight / gradSum / gradBias -- with fuse_kl the total d/dmeans, d/dlvars --, the final Linear's gradWeight
+    / gradBias) in float32, the loss and the hit count in float64. A block above DUMP_SMALL elements is a sample: the flat
+    positions np.random.default_rng(0).choice(numel, k, replace=False), sorted, with k its share of DUMP_BUDGET_FLOATS."""
+    import numpy as np
+    blocks = []
+    for li, v in enumerate(eng.vb):
+        blocks += [(f"layer{li}_gradWeight", v.gradWeight), (f"layer{li}_gradSum", v.gradSum), (f"layer{li}_gradBias", v.gradBias)]
+    blocks += [("final_gradWeight", eng.gradWeight3), ("final_gradBias", eng.gradBias3)]
+    small = sum(b.numel() for _, b in blocks if b.numel() <= DUMP_SMALL)
+    n_large = sum(1 for _, b in blocks if b.numel() > DUMP_SMALL)
+    share = max(DUMP_SMALL, (DUMP_BUDGET_FLOATS - small) // max(n_large, 1))
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, b in blocks:
+        flat = b.reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), share, replace=False))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        np.save(os.path.join(out_dir, f"{name}.npy"), flat.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "correct.npy"), np.array([correct], dtype=np.float64))
+
+
 def device_identity(torch, idx):
     p = torch.cuda.get_device_properties(idx)
     uuid = getattr(p, "uuid", None)
@@ -522,8 +559,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=7, help="timed blocks of --steps steps; ms_per_step is the median block (seven: "
-                    "behind a short warm-up the first two blocks still run on the chip's clock ramp, and every block is reported)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed blocks of --steps steps; ms_per_step is the median block (default "
+                    "one: --steps is the number of timed steps; seven with --full: behind a short warm-up the first two blocks still run "
+                    "on the chip's clock ramp, and every block is reported)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: box probes, per-kernel roofline, "
+                    "training step, CPU baseline, reporting and deep configurations, multi-rank exchange figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(gradient arena blocks, loss, hit count) as DIR/<name>.npy")
     ap.add_argument("--config", default="wide", choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reporting-config", action="store_true", help="skip the 784-400-400-10 / batch 256 / fp32 row measured beside the headline")
@@ -535,7 +577,7 @@ def main():
     ap.add_argument("--host-input", action="store_true", help="the minibatch starts in (pinned) HOST memory every step: the PCIe-inclusive "
                     "rate, reported beside the metric in config.pcie_inclusive -- never `value`")
     ap.add_argument("--prepare-each-step", action="store_true", help="round 1's protocol: the parameter sweep inside every step")
-    ap.add_argument("--with-update", action="store_true", help="(default since r04: on) also time step + optimiser update, reported beside the metric as train_step")
+    ap.add_argument("--with-update", action="store_true", help="also time step + optimiser update, reported beside the metric as train_step (--full does so by default)")
     ap.add_argument("--no-train-step", action="store_true", help="skip the train_step entry (step + FusedMLP.update)")
     ap.add_argument("--no-box", action="store_true", help="skip the box block (vbnn_box_calibrate: the MFMA clock / rate and the HBM rate this device holds)")
     ap.add_argument("--no-deep-config", action="store_true", help="skip the deep_config entry (BASELINE configs[4] measured beside the headline)")
@@ -552,6 +594,8 @@ def main():
     ap.add_argument("--exchange-dtype", default="f32", choices=["f32", "bf16"], help="data-parallel exchange payload: fp32 (default, the "
                     "metric) or the optional bf16 copy (half the bytes, a DIFFERENT gradient: reported as an option, config.exchange_dtype)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -662,6 +706,38 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    def warm_up():
+        """--warmup steps; in a plain run then more in chunks of that many until WARMUP_MIN_S have passed (the ranks decide
+        together): a handful of steps leaves the chip on its clock ramp, and the single timed block behind it would time the
+        ramp. The draw counter is then set back to where the --warmup steps left it, so that the timed steps draw the same
+        noise in every run with the same arguments however long the warm-up took. --full keeps the warm-up at --warmup
+        steps: its median of seven blocks is past the ramp, and the kernel mix of its runs stays what profiles/ recorded.
+        Returns the number of warm-up steps run."""
+        barrier()
+        t0, n, chunk = time.perf_counter(), 0, max(1, args.warmup)
+        for _ in range(args.warmup):
+            step()
+            n += 1
+        if args.full:
+            return n
+        d0 = eng.draw
+        while True:
+            barrier()
+            more = int(time.perf_counter() - t0 < WARMUP_MIN_S)
+            if use_dist:
+                flag = torch.tensor([more], dtype=torch.int32, device="cuda")
+                dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+                more = int(flag.item())
+            if not more:
+                eng.draw = d0
+                if eng.device_draw:
+                    eng._draw_dev.fill_(d0)
+                    torch.cuda.synchronize()
+                return n
+            for _ in range(chunk):
+                step()
+                n += 1
+
     def timed_blocks(fn, repeats):
         """`repeats` blocks of exactly --steps calls of fn: wall clock between barrier + synchronize on both sides (MAX
         over ranks) and HIP events on the launch stream around the same block."""
@@ -703,12 +779,11 @@ def main():
                 print(json.dumps({"metric": "VBLinear fwd+bwd samples/sec", "value": None, "n_gpus": world, "exchange_failed": "the exchange did not sum",
                                   "exchange_validation": xval}), flush=True)
             sys.exit(3)
-    for _ in range(args.warmup):
-        step()
+    warmup_run = warm_up()
     # the box's own speed, measured here and now (rank 0's device; every rank runs it so the ranks stay in step): after the
     # warm-up -- the clock has ramped -- and before the timed blocks; once more behind them (`after_timed_blocks`)
     box = None
-    if not args.no_box:
+    if args.full and not args.no_box:
         try:
             torch.cuda.synchronize()
             box = box_calibration(L, eng.ctx.h)
@@ -734,6 +809,8 @@ def main():
         sys.exit(3)
     loss, correct = eng.loss_and_accuracy()
     ms = sorted(wall)[len(wall) // 2]
+    if args.dump_outputs and rank == 0:                   # before anything else runs on the engine: the last timed step's outputs
+        dump_outputs(eng, loss, correct, args.dump_outputs, torch)
     if box is not None and "error" not in box:
         try:
             box["after_timed_blocks"] = {k: v for k, v in box_calibration(L, eng.ctx.h).items() if k in ("mfma_clock_ghz", "mfma_tflops", "hbm_TBps")}
@@ -742,7 +819,7 @@ def main():
     # the SAME step (same launch order, same two-launch accGradParameters) with the collective calls left out: what the
     # exchange costs beyond the compute it overlaps with = ms - this
     noex = None
-    if use_dist:
+    if use_dist and args.full:
         eng.skip_exchange = True
         for _ in range(3):
             step()
@@ -755,19 +832,21 @@ def main():
     # HIP events around every launch of the widest layer's three dual GEMMs, on the stream they are launched on, in one
     # more block of --steps steps of the same step (rank 0; kept out of the blocks above: an event record is a marker
     # packet between two kernels, six per step cost ~3 % of the step)
-    wide_li = max(range(len(eng.vb)), key=lambda k: eng.vb[k].I * eng.vb[k].O)
-    eng.probe = (wide_li, {}) if rank == 0 else None
-    barrier()
-    tp0 = time.perf_counter()
-    for _ in range(args.steps):
-        issue()                                           # launch by launch: events cannot be placed inside a graph replay
-    barrier()
-    probed_ms = (time.perf_counter() - tp0) / args.steps * 1e3
-    probe, eng.probe = eng.probe, None
+    probe = probed_ms = None
+    if args.full:
+        wide_li = max(range(len(eng.vb)), key=lambda k: eng.vb[k].I * eng.vb[k].O)
+        eng.probe = (wide_li, {}) if rank == 0 else None
+        barrier()
+        tp0 = time.perf_counter()
+        for _ in range(args.steps):
+            issue()                                       # launch by launch: events cannot be placed inside a graph replay
+        barrier()
+        probed_ms = (time.perf_counter() - tp0) / args.steps * 1e3
+        probe, eng.probe = eng.probe, None
     # what a kernel boundary costs inside a graph on this box, measured here on the device: a captured graph of 64 dependent
     # one-thread kernels (vbnn_sample with an increment of 0), replayed 20 times
     floor_us = None
-    if rank == 0 and eng.device_draw and graph is not None:
+    if args.full and rank == 0 and eng.device_draw and graph is not None:
         import ctypes as C
         lib = L.lib()
         dd = C.c_void_p(eng._draw_dev.data_ptr())
@@ -810,7 +889,7 @@ def main():
                 "note": "minibatch copied from pinned host memory at the head of every step (no overlap with the previous step)"}
 
     train = None
-    if (args.with_update or not args.no_train_step) and args.mode == "lrt" and not use_graph:
+    if (args.with_update or (args.full and not args.no_train_step)) and args.mode == "lrt" and not use_graph:
         for _ in range(3):
             train_step()
         tw, te = timed_blocks(train_step, max(1, args.repeats) if args.with_update else min(3, max(1, args.repeats)))
@@ -827,14 +906,15 @@ def main():
 
     comm = None
     if use_dist:
-        ident = [None] * world
-        dist.all_gather_object(ident, (rank, local_rank, device_identity(torch, local_rank), os.getpid()))
-        comm = {"backend": eng.comm_backend(), "payload": eng.exchange_dtype, "ranks_seen": [list(i) for i in ident],
-                "distinct_devices": len({i[2] for i in ident}), "allreduce": eng.time_buckets(5)}
+        comm = {"backend": eng.comm_backend(), "payload": eng.exchange_dtype}
         if xprobe is not None:
             comm["probe"] = xprobe
         if xval is not None:
             comm["validation"] = xval
+    if use_dist and args.full:
+        ident = [None] * world
+        dist.all_gather_object(ident, (rank, local_rank, device_identity(torch, local_rank), os.getpid()))
+        comm.update({"ranks_seen": [list(i) for i in ident], "distinct_devices": len({i[2] for i in ident}), "allreduce": eng.time_buckets(5)})
         if noex is not None:
             comm["step_without_exchange"] = noex
         if world > 1 and os.environ.get("VBNN_BENCH_OTHER_BACKEND", "1") != "0":
@@ -863,11 +943,6 @@ def main():
         sizes = [cfg["input_size"]] + cfg["hidden"]
         fps = algorithmic_flops_per_sample(sizes, cfg["n_classes"]) * args.S
         peak = PEAK_TFLOPS[cfg["dtype"]]
-        live = {LIVE_NAMES[k]: sum(a.elapsed_time(b) for a, b in ev) / len(ev) for k, ev in probe[1].items() if ev}
-        _, _, kflops, kall = dominant_kernel_roofline(eng, N, torch)      # the same launches in isolation (cross-check)
-        kname = max(live, key=live.get)
-        kms = live[kname]
-        achieved = kflops / (kms * 1e-3) / 1e12
         out = {
             "metric": "VBLinear fwd+bwd samples/sec", "value": round(N * world * args.S / (ms * 1e-3), 1),
             "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -881,23 +956,30 @@ def main():
                        "step": ("resetGradients, prepare, S x (sample, run), all-reduce" if args.prepare_each_step else
                                 "resetGradients, S x (sample, run), all-reduce; the parameter sweep (compute_prior + operand "
                                 "shadows) belongs to the excluded update, as VBLinear.lua:130 has it: prepare() ran once"),
-                       "timing": f"median of {len(wall)} blocks of {args.steps} steps (all in repeats_wall_ms; behind a short warm-up the first blocks run on the clock ramp), wall clock between barrier+synchronize, MAX over ranks",
+                       "timing": f"median of {len(wall)} block(s) of {args.steps} steps (all in repeats_wall_ms) behind {warmup_run} warm-up steps{'' if args.full else f' (at least {WARMUP_MIN_S} s: the clock ramp)'}, wall clock between barrier+synchronize, MAX over ranks",
+                       "warmup_steps_run": warmup_run,
                        "repeats_wall_ms": [round(v, 4) for v in wall], "repeats_event_ms": [round(v, 4) for v in evms],
-                       "probed_block_ms": round(probed_ms, 4),
                        "backward_order": ("every updateGradInput, then the accGradParameters from the first layer up" if eng.dx_first
                                           and not eng.reduce else "layer by layer, accGradParameters (+ its all-reduce) first"),
                        "cu_budget": (getattr(eng.ctx, "cu_budget", None) if args.cu_budget > 0 else None),
                        "launch": (f"ONE hipGraph launch per step: {graph.kernel_nodes} kernel nodes captured once (vbnn_capture_*), the draw "
                                   "counter in device memory (vbnn_sample is a node), bitwise the launch-by-launch step" if graph else
                                   "one stream launch per kernel")},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": measured_traffic(kname, args.config),
-                         "traffic_source": "profiles/r*_traffic.json: separate rocprofv3 --pmc passes of the same launch "
-                                           "(tools/collect_traffic.py), NOT measured in this run", "kernel": kname,
-                         "kernel_ms": round(kms, 4), "flop_per_launch": kflops,
-                         "timed_region_kernels_ms": {k: round(v_, 4) for k, v_ in live.items()},
-                         "isolated_kernels_ms": kall},
         }
+        if args.full:
+            live = {LIVE_NAMES[k]: sum(a.elapsed_time(b) for a, b in ev) / len(ev) for k, ev in probe[1].items() if ev}
+            _, _, kflops, kall = dominant_kernel_roofline(eng, N, torch)      # the same launches in isolation (cross-check)
+            kname = max(live, key=live.get)
+            kms = live[kname]
+            achieved = kflops / (kms * 1e-3) / 1e12
+            out["config"]["probed_block_ms"] = round(probed_ms, 4)
+            out["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                               "frac": round(achieved / peak, 4), "traffic": measured_traffic(kname, args.config),
+                               "traffic_source": "profiles/r*_traffic.json: separate rocprofv3 --pmc passes of the same launch "
+                                                 "(tools/collect_traffic.py), NOT measured in this run", "kernel": kname,
+                               "kernel_ms": round(kms, 4), "flop_per_launch": kflops,
+                               "timed_region_kernels_ms": {k: round(v_, 4) for k, v_ in live.items()},
+                               "isolated_kernels_ms": kall}
         if box is not None:
             out["box"] = box
             ghz = box.get("mfma_clock_ghz")
@@ -921,13 +1003,13 @@ def main():
             out["config"]["pcie_inclusive"] = pcie
         if comm:
             out["comm"] = comm
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
-        if world == 1 and args.config == "wide" and not use_graph and args.cu_budget == 0 and not args.no_reporting_config:
+        if args.full and world == 1 and args.config == "wide" and not use_graph and args.cu_budget == 0 and not args.no_reporting_config:
             out["reporting_config"] = reporting_config_row(torch, L, FusedMLP, fill_normal, not args.no_cpu_baseline)
     # BASELINE.json configs[4] beside the headline, every rank (its step has its own exchange when N > 1)
     deep = None
-    if args.config == "wide" and not args.no_deep_config and not use_graph and args.cu_budget == 0 and args.mode == "lrt" and args.S == 1:
+    if args.full and args.config == "wide" and not args.no_deep_config and not use_graph and args.cu_budget == 0 and args.mode == "lrt" and args.S == 1:
         try:
             del eng
             torch.cuda.empty_cache()
@@ -936,7 +1018,7 @@ def main():
         except Exception as e:                  # noqa: BLE001 -- never at the price of the headline
             deep = {"error": f"{type(e).__name__}: {e}"[:300]}
     sharded = None
-    if use_dist and cfg["dtype"] == "bf16" and args.mode == "lrt" and args.S == 1 and not args.no_train_step and cfg.get("criterion", "nll") == "nll":
+    if args.full and use_dist and cfg["dtype"] == "bf16" and args.mode == "lrt" and args.S == 1 and not args.no_train_step and cfg.get("criterion", "nll") == "nll":
         try:
             sharded = sharded_train_row(cfg, torch, dist, L, FusedMLP, fill_normal, min(args.steps, 20), min(args.warmup, 5), world, rank,
                                         exchange=opt.get("exchange"))

@@ -504,7 +504,7 @@ int vbnn_p2p_standin(vbnn_p2p* p, int sim_world, double inbound_GBps);
 /* ---- (ABI 6) what THIS device holds, measured in the run that reports a throughput (bench.py's `box` block) ------------------
  * The boxes of a pool differ by 5-7 % on one binary (the clock a power-bound chip holds); the reference's only timing hook is a
  * commented-out sys.clock() (main.lua:20). vbnn_box_calibrate runs two fixed probes on the context's stream and BLOCKS until
- * they are done (~40 ms; 1 GiB of scratch, freed again): a register-only MFMA loop on every SIMD (2 waves x 2^15
+ * they are done (~70 ms; 1 GiB of scratch, freed again): a register-only MFMA loop on every SIMD (2 waves x 2^15
  * v_mfma_f32_16x16x32_bf16, live operands) -- mfma_clock_ghz = median over workgroups of d(s_memtime) / d(s_memrealtime) x 100 MHz,
  * mfma_tflops = its flops / its time -- and a 512 MiB -> 512 MiB copy: hbm_TBps (bytes read + written per second). */
 typedef struct vbnn_box_info {

@@ -82,7 +82,7 @@ def test_bench_launches_its_own_ranks_from_a_bare_shell():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "small", "--steps", "3", "--warmup", "1",
-           "--repeats", "2", "--no-cpu-baseline"]
+           "--repeats", "2", "--no-cpu-baseline", "--full"]
     res = _children.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -129,7 +129,7 @@ def test_bench_rehearsal_with_the_p2p_exchange_reports_its_status():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "small", "--steps", "3", "--warmup", "1",
-           "--repeats", "2", "--no-cpu-baseline"]
+           "--repeats", "2", "--no-cpu-baseline", "--full"]
     res = _children.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
@@ -244,7 +244,7 @@ def test_bench_line_of_a_multi_rank_run_prices_the_sharded_update_exchange():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1",
-           "--no-cpu-baseline", "--no-deep-config"]
+           "--no-cpu-baseline", "--no-deep-config", "--full"]
     res = _children.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])

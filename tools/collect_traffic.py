@@ -3,7 +3,8 @@
 
 Run ON the GPU box from the repository root:   python3 tools/collect_traffic.py r01
 One rocprofv3 pass per counter group (MI355X_MICROARCH.md: FETCH_SIZE and WRITE_SIZE cannot share a pass; counters are
-collected with --kernel-trace only), each pass over `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline`.
+collected with --kernel-trace only), each pass over `python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline` (--full: the
+timed, probed and isolated launches every committed traffic file averaged over, behind a warm-up of exactly one step).
 Per GEMM family the launches of the widest layer are the kernel's LONGEST dispatches; their counter values are averaged.
 FETCH_SIZE is doubled (gfx950 tallies a 128-B request as 64 B); hbm_bytes = (2 FETCH_SIZE + WRITE_SIZE) KB.
 """
@@ -31,7 +32,8 @@ EXTRA = os.environ.get("VBNN_PMC_EXTRA", "")           # e.g. "TCC_EA0_RDREQ_sum
 
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
-    out_dir = os.path.join(ROOT, "gpurun_out", f"pmc_{tag}")
+    results = os.path.abspath(os.environ.get("OUT_DIR") or os.path.join(ROOT, "bench_out"))     # as the tools/*.sh scripts
+    out_dir = os.path.join(results, f"pmc_{tag}")
     os.makedirs(out_dir, exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp")
     res = {k: {} for k in FAMILIES}
@@ -40,7 +42,7 @@ def main():
     for gi, ctrs in enumerate(groups):
         d = os.path.join(out_dir, f"g{gi}")
         cmd = ["rocprofv3", "--kernel-trace", "--pmc", *ctrs, "--output-format", "csv", "-d", d, "-o", f"g{gi}", "--",
-               "python3", os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-box",
+               "python3", os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-box",
                "--no-reporting-config", "--no-deep-config", "--no-train-step", *bench_args]
         print("pass", gi, " ".join(ctrs), flush=True)
         subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=False)
@@ -83,11 +85,11 @@ def main():
         if "SQ_WAIT_ANY" in v and v.get("SQ_WAVE_CYCLES"):
             v["wave_wait_frac"] = round(v["SQ_WAIT_ANY"] / v["SQ_WAVE_CYCLES"], 4)
     res["_note"] = ("tools/collect_traffic.py: rocprofv3 --kernel-trace --pmc <one counter group per pass> on `python3 bench.py "
-                    "--steps 2 --warmup 1`; means over the launches of the 4096 x 4096 (N = 4096) dual GEMM of each family "
+                    "--full --steps 2 --warmup 1`; means over the launches of the 4096 x 4096 (N = 4096) dual GEMM of each family "
                     "(that family's longest dispatches); FETCH_SIZE / WRITE_SIZE in KB as reported; hbm_bytes = (2 * FETCH_SIZE + "
                     "WRITE_SIZE) * 1024 -- FETCH_SIZE doubled per MI355X_MICROARCH.md section HBM; mfma_busy = "
                     "SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs * GRBM_GUI_ACTIVE / 8); l2_hit = TCC_HIT / (TCC_HIT + TCC_MISS)")
-    path = os.path.join(ROOT, "gpurun_out", f"{tag}_traffic.json")
+    path = os.path.join(results, f"{tag}_traffic.json")
     json.dump(res, open(path, "w"), indent=1)
     print("wrote", path)
     for fam, v in res.items():
