@@ -615,6 +615,45 @@ typedef struct vbnn_head_args {
 } vbnn_head_args;
 int vbnn_head_forward_backward(vbnn_ctx* ctx, int dtype, const vbnn_head_args* a);
 
+/* Posterior-predictive head (C <= 16): mlp:test's S draws (mlp.lua:86-107, main.lua:55-74) averaged as PROBABILITIES instead
+ * of as per-draw criteria, with the per-example uncertainty the reference's author plots (visualize.lua:66-100,
+ * show_uncertainties). Operand row n = s R + r is draw s of minibatch row r (the rows_per_draw = R layout of
+ * vbnn_fwd_args). Per draw, in draw order: logits_s = h[n] w3^T + bias, bitwise vbnn_head_forward's on the same h;
+ * o_s = log_softmax(logits_s) (first maximum wins, as Tensor:max); and per row a running state in fp32:
+ *   L[c] = logsumexp over the draws so far of o_s[c] (online; never a sum of probabilities, which underflow),
+ *   sum_s H(p_s) with H(p_s) = -sum_c exp(o_s[c]) o_s[c],  sum_s -o_s[t_r],  sum_s [argmax o_s = t_r].
+ * The finish, per row: log p = L - log S, p = exp(log p), entropy = H[p], expected_entropy = sum_s H(p_s) / S,
+ * mutual_info = entropy - expected_entropy (the epistemic part), pred = argmax p (first maximum). */
+enum { VBNN_PREDICT_STACKED = 0, VBNN_PREDICT_ACCUMULATE = 1 };
+typedef struct vbnn_predict_args {
+    const void* h; int64_t ld_h;            /* packed input of the final Linear (dtype): S x R rows (STACKED) or R rows (ACCUMULATE) */
+    const void* w3; int64_t ld_w;           /* packed C x ld_w final weight, as vbnn_prepare / vbnn_update leave it */
+    const float* bias;                      /* C, or NULL */
+    const int32_t* target;                  /* R class indices, or NULL: no totals (targets are clamped to [0, C - 1]) */
+    int64_t R;                              /* minibatch rows */
+    int64_t H, C;                           /* hidden width (columns of h / w3 read), classes (1 .. 16) */
+    int64_t S;                              /* draws of the WHOLE prediction (>= 1): the finish divides by it */
+    /* VBNN_PREDICT_STACKED: h holds all S draws and this one call walks them in order (first / final / state ignored: the
+     * state stays in registers). VBNN_PREDICT_ACCUMULATE: h holds ONE draw; the running state lives in `state` between
+     * calls. Both forms run the same update in the same order: given the same h per draw, their outputs are bitwise equal. */
+    int32_t form;
+    int32_t first;                          /* ACCUMULATE: 1 = this draw starts the state (nothing is read from `state`) */
+    int32_t final;                          /* ACCUMULATE: 1 = finish after this draw (the outputs and totals are written) */
+    float* state;                           /* ACCUMULATE: R x (C + 3) floats, row r = { L[0 .. C-1], sum H, sum -o[t], hits } */
+    /* outputs of the finish, each optional (NULL to skip) */
+    float* probs; float* log_probs;         /* R x C: p(y | x, D) ~ 1/S sum_s softmax(f_s(x)), and its log */
+    float* entropy;                         /* R: H[p] (total predictive uncertainty) */
+    float* expected_entropy;                /* R: 1/S sum_s H(p_s) (the aleatoric part) */
+    float* mutual_info;                     /* R: entropy - expected_entropy (the epistemic part) */
+    int32_t* pred;                          /* R: argmax p */
+    /* with target: 4 doubles, WRITTEN by the finish, each summed over rows in a fixed order inside the launch (bitwise
+     * reproducible, no float atomics): { sum_r -log p[t_r], sum_r [pred = t_r], sum_{r,s} -o_s[t_r], sum_{r,s} hits } --
+     * the predictive NLL, the ensemble's hits, and the reference's test metrics (mlp:test's mean criterion and accuracy
+     * are the last two / (R S)). NULL to skip. */
+    double* totals;
+} vbnn_predict_args;
+int vbnn_head_predict(vbnn_ctx* ctx, int dtype, const vbnn_predict_args* a);
+
 /* The same criterion as separate modules, for the module-level call order of mlp.lua:77-80:
  * nn.LogSoftMax:updateOutput is vbnn_logsoftmax_nll with g_logits = loss = correct = NULL. */
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,

@@ -440,4 +440,100 @@ function FusedMLP:loss_and_accuracy()
     return a[0], c[0]
 end
 
+-- the posterior predictive (engine.py:FusedMLP.predict, tools/c_host.c:fm_predict): mlp:test's S draws averaged as probabilities
+-- (mlp.lua:86-107, main.lua:55-74, visualize.lua:66-100), forward-only on buffers of its own (in_x[li]: layer li's input,
+-- in_x[#vb + 1] the head's; r: a throwaway noise factor for the one-draw bf16 forwards). Consumes draws draw + 1 .. draw + S, as
+-- mlp:test does. Returns a table of device buffers -- probs, log_probs (R x C floats), entropy, expected_entropy, mutual_info
+-- (R floats), pred (R int32) -- and, with targets, nll / accuracy of the average and mean_draw_nll / mean_draw_accuracy (the two
+-- numbers mlp:test returns), accuracies in percent. opt: predict_rows (32768), predict_stacked ('auto' / true / false).
+function FusedMLP:predict(inputs, ld, targets, R, S, opt)
+    opt = opt or {}
+    local nc, cap = self.n_classes, opt.predict_rows or 32768
+    local widest, omax = 0, 0
+    for _, v in ipairs(self.vb) do widest, omax = math.max(widest, v.I * v.O), math.max(omax, v.O) end
+    local stacked
+    if S == 1 then
+        stacked = true
+    elseif opt.predict_stacked ~= nil and opt.predict_stacked ~= 'auto' then
+        stacked = opt.predict_stacked
+    else
+        stacked = math.min(R, cap) * widest < 2 ^ 32              -- one draw's widest forward small: S launches become one
+    end
+    local Rc = math.max(1, math.min(R, stacked and math.floor(cap / S) or cap))
+    local rows = stacked and S * Rc or Rc
+    local sq = self.dtype == C.VBNN_BF16                           -- (fp32: the forward forms x.x from x itself)
+    local in_x, in_x2 = {}, {}
+    for li = 1, #self.vb + 1 do
+        in_x[li] = packed(rows, self.sizes[li], self.esize)
+        if sq and li <= #self.vb then in_x2[li] = packed(rows, self.sizes[li], self.esize) end
+    end
+    local r = sq and packed(rows, omax, self.esize) or nil
+    local chunks = math.floor((R + Rc - 1) / Rc)
+    local o = { R = R, S = S, stacked = stacked, chunks = chunks }
+    o.probs, o.log_probs = vb.alloc(R * nc * 4), vb.alloc(R * nc * 4)
+    o.entropy, o.expected_entropy, o.mutual_info, o.pred = vb.alloc(R * 4), vb.alloc(R * 4), vb.alloc(R * 4), vb.alloc(R * 4)
+    local totals = vb.alloc(chunks * 32)
+    local state = (not stacked) and vb.alloc(Rc * (nc + 3) * 4) or nil
+    local d0, row0 = self.draw + 1, self.rank * R                 -- the first draw's counter (sample() then run())
+    local pa = ffi.new('vbnn_predict_args')
+    pa.w3, pa.ld_w, pa.bias, pa.H, pa.C, pa.S = self.w3_s.p, self.w3_s.ld, f32(self.bias3), self.sizes[#self.sizes], nc, S
+    pa.form = stacked and C.VBNN_PREDICT_STACKED or C.VBNN_PREDICT_ACCUMULATE
+    pa.state = state and f32(state) or nil
+    for k = 0, chunks - 1 do
+        local c0 = k * Rc
+        local n = math.min(Rc, R - c0)
+        local xc = f32(inputs) + c0 * ld
+        pa.h, pa.ld_h, pa.R = in_x[#self.vb + 1].p, in_x[#self.vb + 1].ld, n
+        pa.target = targets and (ffi.cast('const int32_t*', targets) + c0) or nil
+        pa.totals = targets and (ffi.cast('double*', totals) + 4 * k) or nil
+        pa.probs, pa.log_probs = f32(o.probs) + c0 * nc, f32(o.log_probs) + c0 * nc
+        pa.entropy, pa.expected_entropy, pa.mutual_info = f32(o.entropy) + c0, f32(o.expected_entropy) + c0, f32(o.mutual_info) + c0
+        pa.pred = ffi.cast('int32_t*', o.pred) + c0
+        if stacked then                                            -- every draw in one pass: the chunk stacked S times as rows
+            self:_predict_forward(in_x, in_x2, r, xc, ld, S * n, S > 1 and n or 0, d0, row0 + c0, true)
+            check(C.vbnn_head_predict(vb.ctx, self.dtype, pa))
+        else                                                       -- one draw per forward, the running state between the launches
+            for s = 0, S - 1 do
+                self:_predict_forward(in_x, in_x2, r, xc, ld, n, 0, d0 + s, row0 + c0, s == 0)
+                pa.first, pa.final = (s == 0) and 1 or 0, (s == S - 1) and 1 or 0
+                check(C.vbnn_head_predict(vb.ctx, self.dtype, pa))
+            end
+        end
+    end
+    self.draw = self.draw + S
+    if self.draw_dev then check(C.vbnn_sample(vb.ctx, self.draw_dev, S)) end
+    if targets then                                                -- the chunks' totals, added in chunk order
+        local th = ffi.new('double[?]', 4 * chunks)
+        check(C.vbnn_buf_download(vb.ctx, th, totals, 32 * chunks))
+        local tot = { 0, 0, 0, 0 }
+        for k = 0, chunks - 1 do
+            for j = 1, 4 do tot[j] = tot[j] + th[4 * k + j - 1] end
+        end
+        o.totals = tot
+        o.nll, o.accuracy = tot[1] / R, 100 * tot[2] / R
+        o.mean_draw_nll, o.mean_draw_accuracy = tot[3] / (R * S), 100 * tot[4] / (R * S)
+    end
+    return o
+end
+
+-- predict's forwards: the input packed (stacked draws: rows_per_draw), then every VB layer; r only for one-draw forwards
+function FusedMLP:_predict_forward(in_x, in_x2, r, x, ld, N, rpd, draw, row0, pack)
+    if pack then
+        check(C.vbnn_pack_input(vb.ctx, self.dtype, x, ld, N, self.sizes[1], in_x[1].p, in_x2[1] and in_x2[1].p or nil, in_x[1].ld,
+                                nil, nil, 0, rpd))
+    end
+    for li, v in ipairs(self.vb) do
+        local fa = ffi.new('vbnn_fwd_args')
+        fa.w, fa.w2, fa.x, fa.ld_w, fa.ld_x = v.mu_s.p, v.var_s.p, in_x[li].p, v.mu_s.ld, in_x[li].ld
+        fa.x2 = in_x2[li] and in_x2[li].p or nil
+        fa.N, fa.I, fa.O, fa.bias = N, v.I, v.O, f32(v.bias)
+        fa.seed, fa.layer, fa.draw, fa.row0, fa.draw_dev = self.seed, v.layer_id, draw, row0, nil
+        if rpd == 0 and r then fa.r, fa.ld_r = r.p, r.ld end
+        fa.r_packed, fa.relu, fa.rows_per_draw = 1, 1, rpd
+        fa.h, fa.ld_h = in_x[li + 1].p, in_x[li + 1].ld
+        fa.h2 = (li < #self.vb and in_x2[li + 1]) and in_x2[li + 1].p or nil
+        check(C.vbnn_forward(vb.ctx, self.dtype, fa))
+    end
+end
+
 return FusedMLP

@@ -227,6 +227,27 @@ typedef struct vbnn_head_args {
     const float* logit_slots; int64_t n_slots;
 } vbnn_head_args;
 int vbnn_head_forward_backward(vbnn_ctx* ctx, int dtype, const vbnn_head_args* a);
+enum { VBNN_PREDICT_STACKED = 0, VBNN_PREDICT_ACCUMULATE = 1 };
+typedef struct vbnn_predict_args {
+    const void* h; int64_t ld_h;
+    const void* w3; int64_t ld_w;
+    const float* bias;
+    const int32_t* target;
+    int64_t R;
+    int64_t H, C;
+    int64_t S;
+    int32_t form;
+    int32_t first;
+    int32_t final;
+    float* state;
+    float* probs; float* log_probs;
+    float* entropy;
+    float* expected_entropy;
+    float* mutual_info;
+    int32_t* pred;
+    double* totals;
+} vbnn_predict_args;
+int vbnn_head_predict(vbnn_ctx* ctx, int dtype, const vbnn_predict_args* a);
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,
                      float inv_n, double* loss_sum_dev, int32_t* correct_dev);
 int vbnn_nll_backward(vbnn_ctx* ctx, const int32_t* target, int64_t N, int64_t C, float inv_n, float* g);

@@ -14,6 +14,10 @@
  *
  *   c_host --dtype f32|bf16 --input 784 --hidden 400,400 --classes 10 --batch 256 [--S 1] [--steps 2] [--update]
  *          [--comm [--sharded]] [--graph] [--kl-shadows] [--seed 3] --out arena.bin
+ *          [--predict S [--predict-rows 32768] [--predict-stacked -1|0|1]]
+ *   --predict S: after the steps, the posterior predictive of the minibatch over S draws (fm_predict), appended to the file:
+ *   int64 R, int64 C, int32 S, stacked, chunks, draw counter after it; probs and log_probs (R x C floats); entropy,
+ *   expected_entropy, mutual_info (R floats each); pred (R int32); the four totals (doubles). Without it the file is as above.
  *   --graph: the context gets a stream of its own (vbnn_ctx_create_cu_budget), the draw counter lives on the device
  *   (vbnn_fwd_args.draw_dev, vbnn_sample), step 2 is CAPTURED (vbnn_capture_begin / _end) and steps 2.. are replays of it.
  *   arena.bin: int64 n_grads, double loss, int32 correct, int32 flags, then n_grads floats (the arena after the last
@@ -510,6 +514,100 @@ static void fm_loss_and_accuracy(fused_mlp* m, double* loss, int32_t* correct) {
     *loss = a[0];
 }
 
+/* ---- the posterior predictive (engine.py:FusedMLP.predict, lua/FusedMLP.lua:predict): mlp:test's S draws averaged as
+   probabilities (mlp.lua:86-107, main.lua:55-74, visualize.lua:66-100). Forward-only, on buffers of its own: in_x[li] is layer
+   li's input (in_x[n_layers] the head's), r a throwaway noise factor for the one-draw bf16 forwards (the two-pass kernel stores it). */
+typedef struct {
+    int64_t R, C; int S, stacked, chunks;
+    float *probs, *log_probs, *entropy, *expected_entropy, *mutual_info;   /* device, R x C / R */
+    int32_t* pred;
+    double totals[4];                                                      /* summed over the chunks in chunk order */
+} predict_out;
+
+static void fm_predict_forward(fused_mlp* m, const packed_t* in_x, const packed_t* in_x2, const packed_t* r, const float* x, int64_t ld,
+                               int64_t N, int64_t rpd, uint32_t draw, int64_t row0, int pack) {
+    if (pack)
+        CHECK(vbnn_pack_input(g_ctx, m->dtype, x, ld, N, m->sizes[0], in_x[0].p, in_x2[0].p, in_x[0].ld, NULL, NULL, 0, rpd));
+    for (int li = 0; li < m->n_layers; ++li) {
+        layer_t* v = &m->vb[li];
+        vbnn_fwd_args a;
+        memset(&a, 0, sizeof a);
+        a.w = v->mu_s.p; a.w2 = v->var_s.p; a.x = in_x[li].p; a.x2 = in_x2[li].p; a.ld_w = v->mu_s.ld; a.ld_x = in_x[li].ld;
+        a.N = N; a.I = v->I; a.O = v->O; a.bias = v->bias;
+        a.seed = m->seed; a.layer = v->layer_id; a.draw = draw; a.row0 = row0; a.draw_dev = NULL;
+        a.r = (rpd == 0) ? r->p : NULL; a.ld_r = (rpd == 0 && r->p) ? r->ld : 0; a.r_packed = 1; a.relu = 1;
+        a.h = in_x[li + 1].p; a.h2 = (li + 1 < m->n_layers) ? in_x2[li + 1].p : NULL; a.ld_h = in_x[li + 1].ld;
+        a.rows_per_draw = rpd;
+        CHECK(vbnn_forward(g_ctx, m->dtype, &a));
+    }
+}
+
+static void fm_predict(fused_mlp* m, const float* x, int64_t ld, const int32_t* targets, int64_t R, int S, int64_t cap,
+                       int stacked_opt /* -1 auto, 0, 1 */, predict_out* o) {
+    const int64_t C = m->n_classes;
+    int64_t widest = 0, omax = 0;
+    for (int li = 0; li < m->n_layers; ++li) {
+        if (m->vb[li].I * m->vb[li].O > widest) widest = m->vb[li].I * m->vb[li].O;
+        if (m->vb[li].O > omax) omax = m->vb[li].O;
+    }
+    const int64_t rows_rule = R < cap ? R : cap;
+    const int stacked = S == 1 ? 1 : (stacked_opt >= 0 ? stacked_opt : (rows_rule * widest < ((int64_t)1 << 32)));
+    int64_t Rc = stacked ? cap / S : cap;
+    if (Rc > R) Rc = R;
+    if (Rc < 1) Rc = 1;
+    const int64_t rows = stacked ? S * Rc : Rc;                    /* operand rows of one forward */
+    const int sq = m->dtype == VBNN_BF16;                          /* (fp32: the forward forms x.x from x itself) */
+    packed_t in_x[MAX_LAYERS + 1], in_x2[MAX_LAYERS + 1], r;
+    memset(in_x2, 0, sizeof in_x2);
+    memset(&r, 0, sizeof r);
+    for (int li = 0; li <= m->n_layers; ++li) {
+        in_x[li] = packed(rows, m->sizes[li], m->esize);
+        if (sq && li < m->n_layers) in_x2[li] = packed(rows, m->sizes[li], m->esize);
+    }
+    if (sq) r = packed(rows, omax, m->esize);
+    const int chunks = (int)((R + Rc - 1) / Rc);
+    o->R = R; o->C = C; o->S = S; o->stacked = stacked; o->chunks = chunks;
+    o->probs = (float*)dev_alloc((size_t)R * C * 4); o->log_probs = (float*)dev_alloc((size_t)R * C * 4);
+    o->entropy = (float*)dev_alloc((size_t)R * 4); o->expected_entropy = (float*)dev_alloc((size_t)R * 4);
+    o->mutual_info = (float*)dev_alloc((size_t)R * 4); o->pred = (int32_t*)dev_alloc((size_t)R * 4);
+    double* totals = (double*)dev_alloc((size_t)chunks * 4 * 8);
+    float* state = stacked ? NULL : (float*)dev_alloc((size_t)Rc * (C + 3) * 4);
+    const uint32_t d0 = m->draw + 1;                               /* the first draw's counter (sample() then run()) */
+    vbnn_predict_args a;
+    memset(&a, 0, sizeof a);
+    a.w3 = m->w3_s.p; a.ld_w = m->w3_s.ld; a.bias = m->bias3; a.H = m->sizes[m->n_layers]; a.C = C; a.S = S;
+    a.form = stacked ? VBNN_PREDICT_STACKED : VBNN_PREDICT_ACCUMULATE; a.state = state;
+    for (int k = 0; k < chunks; ++k) {
+        const int64_t c0 = k * Rc, n = (R - c0 < Rc) ? R - c0 : Rc;
+        const float* xc = x + c0 * ld;
+        a.h = in_x[m->n_layers].p; a.ld_h = in_x[m->n_layers].ld; a.R = n;
+        a.target = targets ? targets + c0 : NULL; a.totals = targets ? totals + 4 * k : NULL;
+        a.probs = o->probs + c0 * C; a.log_probs = o->log_probs + c0 * C;
+        a.entropy = o->entropy + c0; a.expected_entropy = o->expected_entropy + c0; a.mutual_info = o->mutual_info + c0;
+        a.pred = o->pred + c0;
+        if (stacked) {                  /* every draw in one pass: the chunk stacked S times as rows */
+            fm_predict_forward(m, in_x, in_x2, &r, xc, ld, S * n, S > 1 ? n : 0, d0, m->rank * R + c0, 1);
+            CHECK(vbnn_head_predict(g_ctx, m->dtype, &a));
+            continue;
+        }
+        for (int s = 0; s < S; ++s) {   /* one draw per forward, the running state between the head's launches */
+            fm_predict_forward(m, in_x, in_x2, &r, xc, ld, n, 0, d0 + (uint32_t)s, m->rank * R + c0, s == 0);
+            a.first = s == 0; a.final = s == S - 1;
+            CHECK(vbnn_head_predict(g_ctx, m->dtype, &a));
+        }
+    }
+    m->draw += (uint32_t)S;                                        /* the draws mlp:test would have consumed */
+    if (m->draw_dev) CHECK(vbnn_sample(g_ctx, m->draw_dev, (uint32_t)S));
+    memset(o->totals, 0, sizeof o->totals);
+    if (targets) {
+        double* th = (double*)malloc((size_t)chunks * 4 * 8);
+        CHECK(vbnn_buf_download(g_ctx, th, totals, (size_t)chunks * 4 * 8));
+        for (int k = 0; k < chunks; ++k)
+            for (int j = 0; j < 4; ++j) o->totals[j] += th[4 * k + j];
+        free(th);
+    }
+}
+
 static const char* arg_value(int argc, char** argv, const char* name, const char* dflt) {
     for (int i = 1; i + 1 < argc; ++i)
         if (!strcmp(argv[i], name)) return argv[i + 1];
@@ -610,6 +708,26 @@ int main(int argc, char** argv) {
             fwrite(mu, 4, n, f);
             free(mu);
         }
+    const int predict_S = atoi(arg_value(argc, argv, "--predict", "0"));
+    if (predict_S > 0) {       /* --predict S: the posterior predictive of the minibatch after the steps, appended to the file */
+        predict_out po;
+        fm_predict(&net, x, sizes[0], t, N, predict_S, atoll(arg_value(argc, argv, "--predict-rows", "32768")),
+                   atoi(arg_value(argc, argv, "--predict-stacked", "-1")), &po);
+        const int64_t RC = po.R * po.C;
+        float* hf = (float*)malloc((size_t)RC * 4);
+        const int32_t head[4] = {po.S, po.stacked, po.chunks, (int32_t)net.draw};
+        fwrite(&po.R, 8, 1, f); fwrite(&po.C, 8, 1, f); fwrite(head, 4, 4, f);
+        float* const rc[2] = {po.probs, po.log_probs};
+        for (int k = 0; k < 2; ++k) { CHECK(vbnn_buf_download(g_ctx, hf, rc[k], (size_t)RC * 4)); fwrite(hf, 4, (size_t)RC, f); }
+        float* const rr[3] = {po.entropy, po.expected_entropy, po.mutual_info};
+        for (int k = 0; k < 3; ++k) { CHECK(vbnn_buf_download(g_ctx, hf, rr[k], (size_t)po.R * 4)); fwrite(hf, 4, (size_t)po.R, f); }
+        CHECK(vbnn_buf_download(g_ctx, hf, po.pred, (size_t)po.R * 4));
+        fwrite(hf, 4, (size_t)po.R, f);
+        fwrite(po.totals, 8, 4, f);
+        free(hf);
+        printf("c_host: predict S %d over %lld rows (%s, %d chunk(s)): mean NLL %.9g, accuracy %.4f%%\n", po.S, (long long)po.R,
+               po.stacked ? "stacked" : "sequential", po.chunks, po.totals[0] / (double)po.R, 100.0 * po.totals[1] / (double)po.R);
+    }
     fclose(f);
     free(arena);
     printf("c_host: %s %lld", dtype == VBNN_F32 ? "f32" : "bf16", (long long)sizes[0]);

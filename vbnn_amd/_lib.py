@@ -88,6 +88,15 @@ class HeadArgs(C.Structure):          # vbnn_head_args
                 ("gT_prev", _vp), ("gvT_prev", _vp), ("ld_gpT", _i64), ("logit_slots", _vp), ("n_slots", _i64)]
 
 
+class PredictArgs(C.Structure):       # vbnn_predict_args
+    _fields_ = [("h", _vp), ("ld_h", _i64), ("w3", _vp), ("ld_w", _i64), ("bias", _vp), ("target", _vp),
+                ("R", _i64), ("H", _i64), ("C", _i64), ("S", _i64), ("form", _i), ("first", _i), ("final", _i),
+                ("state", _vp), ("probs", _vp), ("log_probs", _vp), ("entropy", _vp), ("expected_entropy", _vp),
+                ("mutual_info", _vp), ("pred", _vp), ("totals", _vp)]
+
+
+PREDICT_STACKED, PREDICT_ACCUMULATE = 0, 1
+
 _SIGS = {
     "vbnn_abi_version": ([], _i),
     "vbnn_last_error": ([], C.c_char_p),
@@ -120,6 +129,7 @@ _SIGS = {
     "vbnn_acc_grad_parameters": ([_vp, _i, C.POINTER(DwArgs)], _i),
     "vbnn_backward_pair": ([_vp, _i, C.POINTER(DxArgs), C.POINTER(DwArgs)], _i),
     "vbnn_head_forward_backward": ([_vp, _i, C.POINTER(HeadArgs)], _i),
+    "vbnn_head_predict": ([_vp, _i, C.POINTER(PredictArgs)], _i),
     "vbnn_acc_grad_bias": ([_vp, _i, _vp, _i64, _i64, _i64, _f, _i, _vp], _i),
     "vbnn_prep_layer": ([_vp, _i, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp], _i),
     "vbnn_compute_mugrads": ([_vp, _vp, _vp, _f, _f, _vp, _vp, _i64], _i),

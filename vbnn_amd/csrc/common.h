@@ -60,7 +60,7 @@ struct vbnn_ctx {
     int cu_budget = 0;     // > 0: the stream is CU-masked to this many compute units (vbnn_ctx_create_cu_budget)
 };
 // ticket slots
-constexpr int VBNN_CNT_HEAD_FWD = 0, VBNN_CNT_TILES = 16, VBNN_CNT_TILES_MAX = 1008, VBNN_CNT_TOTAL = 1024;   // [16, 1024): one ticket per column tile of the head's in-launch finish
+constexpr int VBNN_CNT_HEAD_FWD = 0, VBNN_CNT_PREDICT = 1, VBNN_CNT_TILES = 16, VBNN_CNT_TILES_MAX = 1008, VBNN_CNT_TOTAL = 1024;   // [16, 1024): one ticket per column tile of the head's in-launch finish
 
 void vbnn_set_error(const char* fmt, ...);
 inline int g_head_stream = -1;   // vbnn_debug_set key 10 (VBNN_DEBUG_HEAD_BACKWARD): the head's backward -- -1 by shape, 0 tile form, 1 streaming form whenever the operands allow

@@ -83,8 +83,9 @@ struct EpiFwd {
     __host__ __device__ __forceinline__ int64_t t_ld() const { return ld_hT; }
     __device__ __forceinline__ int m_dim() const { return O; }
     __device__ __forceinline__ int n_dim() const { return N; }
-    // the two-pass kernel's fold addresses the noise by launch-wide (draw, row0): stacked draws stay with the other kernels
-    __host__ __device__ __forceinline__ bool v3_ok() const { return rpd == 0; }
+    // the two-pass kernel's fold addresses the noise by launch-wide (draw, row0): stacked draws stay with the other kernels; and
+    // its staged fold stores r unconditionally (FOLD_STAGE, gemm_v3.h): an LRT forward without r stays with the other kernels too
+    __host__ __device__ __forceinline__ bool v3_ok() const { return rpd == 0 && (!noise || r_t != nullptr); }
     // the four normals of a quad: the contract's bit-exact form on the fp32 path, its hardware-transcendental form on the bf16
     // path (common.h, vbnn_normal4_hw; -DVBNN_BF16_EXACT_NORMALS: the exact form there too, A/B)
     static __device__ __forceinline__ vbnn_f32x4 normal4(uint64_t seed_, uint32_t layer_, uint32_t draw_, uint32_t row, uint32_t quad) {

@@ -89,6 +89,39 @@ __device__ __forceinline__ float head_sum_partials(const float* src, int64_t str
     return tot;
 }
 
+// Row maximum of one 16-row block's values (lane (q = lane >> 4, c16 = lane & 15) holds classes 4q .. 4q + 3 of its row in v,
+// classes >= C are -inf): every lane of the row ends with the maximum and its class, the first maximum winning (Tensor:max).
+__device__ __forceinline__ void head_row_max(const float (&v)[4], int q, float& mx, int& arg) {
+    mx = -INFINITY; arg = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (v[j] > mx) { mx = v[j]; arg = 4 * q + j; }
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {           // combine the four lanes (q = 0..3) of a row
+        const float om = __shfl_xor(mx, off, 64);
+        const int oa = __shfl_xor(arg, off, 64);
+        if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }     // first maximum wins (Tensor:max)
+    }
+}
+
+// Bias, arg-max and log-sum-exp of the rows of one 16-row block from their logits (without the bias), lanes as above:
+// the log-softmax of a row is lg - lse.
+__device__ __forceinline__ void head_log_softmax(f32x4 s, int q, int C, const float* __restrict__ bias, float (&lg)[4], int& arg, float& lse) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = 4 * q + j;
+        lg[j] = (c < C) ? s[j] + (bias ? bias[c] : 0.f) : -INFINITY;
+    }
+    float mx;
+    head_row_max(lg, q, mx, arg);
+    float se = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (4 * q + j < C) se += expf(lg[j] - mx);
+    se += __shfl_xor(se, 16, 64);
+    se += __shfl_xor(se, 32, 64);
+    lse = mx + logf(se);
+}
+
 // ------------------------------------------------------------------------------------------ forward
 // The rows of one 16-row block from their logits (without the bias): lane (q = lane >> 4, c16 = lane & 15) of ONE wave holds classes
 // 4q .. 4q + 3 of row n0 + c16 in `s`. Bias, log-softmax, arg-max (first maximum wins: Tensor:max), d(loss)/d(logits), and the
@@ -100,25 +133,9 @@ __device__ __forceinline__ void head_rows_from_logits(f32x4 s, int lane, int64_t
     const int64_t n = n0 + c16;
     const bool row_ok = n < N;
     float lg[4];
-    float mx = -INFINITY; int arg = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = 4 * q + j;
-        lg[j] = (c < C) ? s[j] + (bias ? bias[c] : 0.f) : -INFINITY;
-        if (lg[j] > mx) { mx = lg[j]; arg = c; }
-    }
-#pragma unroll
-    for (int off = 16; off <= 32; off <<= 1) {           // combine the four lanes (q = 0..3) of a row
-        const float om = __shfl_xor(mx, off, 64);
-        const int oa = __shfl_xor(arg, off, 64);
-        if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }     // first maximum wins (Tensor:max)
-    }
-    float se = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (4 * q + j < C) se += expf(lg[j] - mx);
-    se += __shfl_xor(se, 16, 64);
-    se += __shfl_xor(se, 32, 64);
-    const float lse = mx + logf(se);
+    int arg;
+    float lse;
+    head_log_softmax(s, q, C, bias, lg, arg, lse);
     const int t = row_ok ? min(max(target[rpd > 0 ? n % rpd : n], 0), C - 1) : 0;     // stacked draws share the minibatch's targets
     double loss_acc = 0.0;
 #pragma unroll
@@ -161,28 +178,12 @@ __device__ __forceinline__ void head_sum_loss_partials(unsigned* counter, const 
     }
 }
 
-// MFMA orientation: M = class (A operand = w3 rows, rows >= C clamped and ignored), N = minibatch row.
-// Accumulator layout: lane (q = l >> 4, c = l & 15) holds classes 4q .. 4q+3 of row n0 + c.
+// One wave's share of the logits of a 16-row block: the K steps [k_lo, k_hi) of rows hp (lane (q, c16): row n0 + c16, K offset
+// q x CE) against w3 rows wp, as 16 x 16 MFMA partials (M = class, N = row).
 template <typename T>
-__global__ __launch_bounds__(64 * HEAD_FW) void k_head_forward(const T* __restrict__ h, int64_t ld_h, const T* __restrict__ w3, int64_t ld_w,
-                                                      const float* __restrict__ bias, const int32_t* __restrict__ target, int64_t N,
-                                                      int64_t Hp /* H padded to the K step */, int C, float inv_n, float* out,
-                                                      float* g_logits, float* logits, double* loss_sum, int32_t* correct,
-                                                      int accumulate, double* part_loss, int32_t* part_corr, unsigned* counter, int64_t rpd) {
+__device__ __forceinline__ f32x4 head_logits_wave(const T* __restrict__ hp, const T* __restrict__ wp, int64_t k_lo, int64_t k_hi) {
     constexpr int KE = 64 / (int)sizeof(T);      // K elements per MFMA step (16 bytes per lane x 4 lane groups)
-    constexpr int CE = 16 / (int)sizeof(T);
     typedef typename Frag<T>::type frag_t;
-    __shared__ f32x4 part[HEAD_FW][64];
-    __shared__ double red_l[HEAD_FW];
-    __shared__ int red_c[HEAD_FW];
-    __shared__ int last;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t n0 = (int64_t)blockIdx.x * 16;
-    const int q = lane >> 4, c16 = lane & 15;
-    const T* hp = h + min(n0 + c16, N - 1) * ld_h + q * CE;
-    const T* wp = w3 + (int64_t)min(c16, C - 1) * ld_w + q * CE;
-    const int64_t ksteps = Hp / KE;
-    const int64_t k_lo = ksteps * wave / HEAD_FW, k_hi = ksteps * (wave + 1) / HEAD_FW;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     int64_t ks = k_lo;
     for (; ks + 16 <= k_hi; ks += 16) {               // sixteen K steps of loads in flight: at H = 4096 a wave's whole K range in
@@ -220,6 +221,31 @@ __global__ __launch_bounds__(64 * HEAD_FW) void k_head_forward(const T* __restri
         const frag_t b = *reinterpret_cast<const frag_t*>(hp + ks * KE);
         acc = mfma_step<T>(a, b, acc);
     }
+    return acc;
+}
+
+// MFMA orientation: M = class (A operand = w3 rows, rows >= C clamped and ignored), N = minibatch row.
+// Accumulator layout: lane (q = l >> 4, c = l & 15) holds classes 4q .. 4q+3 of row n0 + c.
+template <typename T>
+__global__ __launch_bounds__(64 * HEAD_FW) void k_head_forward(const T* __restrict__ h, int64_t ld_h, const T* __restrict__ w3, int64_t ld_w,
+                                                      const float* __restrict__ bias, const int32_t* __restrict__ target, int64_t N,
+                                                      int64_t Hp /* H padded to the K step */, int C, float inv_n, float* out,
+                                                      float* g_logits, float* logits, double* loss_sum, int32_t* correct,
+                                                      int accumulate, double* part_loss, int32_t* part_corr, unsigned* counter, int64_t rpd) {
+    constexpr int KE = 64 / (int)sizeof(T);      // K elements per MFMA step (16 bytes per lane x 4 lane groups)
+    constexpr int CE = 16 / (int)sizeof(T);
+    __shared__ f32x4 part[HEAD_FW][64];
+    __shared__ double red_l[HEAD_FW];
+    __shared__ int red_c[HEAD_FW];
+    __shared__ int last;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t n0 = (int64_t)blockIdx.x * 16;
+    const int q = lane >> 4, c16 = lane & 15;
+    const T* hp = h + min(n0 + c16, N - 1) * ld_h + q * CE;
+    const T* wp = w3 + (int64_t)min(c16, C - 1) * ld_w + q * CE;
+    const int64_t ksteps = Hp / KE;
+    const int64_t k_lo = ksteps * wave / HEAD_FW, k_hi = ksteps * (wave + 1) / HEAD_FW;
+    const f32x4 acc = head_logits_wave<T>(hp, wp, k_lo, k_hi);
     part[wave][lane] = acc;
     __syncthreads();
     if (wave == 0) {
@@ -266,6 +292,166 @@ __global__ __launch_bounds__(64) void k_head_from_slots(const float* __restrict_
     for (; k < n_slots; ++k) s += *reinterpret_cast<const f32x4*>(p + (int64_t)k * stride);
     head_rows_from_logits(s, lane, n0, N, C, bias, target, rpd, inv_n, out, g_logits, logits, part_loss, part_corr);
     head_sum_loss_partials<64>(counter, part_loss, part_corr, loss_sum, correct, accumulate, red_l, red_c, &last);
+}
+
+// ------------------------------------------------------------------------------------------ posterior predictive
+// -sum_c exp(o[c]) o[c] of the rows of a 16-row block (lanes as head_row_max; classes >= C skipped), in every lane of the row.
+// One function for the per-draw entropies and the entropy of the average: with S = 1 the two are the same bits.
+__device__ __forceinline__ float head_row_entropy(const float (&o)[4], int q, int C) {
+    float e = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (4 * q + j < C) e = fmaf(expf(o[j]), o[j], e);
+    e += __shfl_xor(e, 16, 64);
+    e += __shfl_xor(e, 32, 64);
+    return -e;
+}
+
+// log(exp(a) + exp(b)) without leaving the log domain (the draws' probabilities underflow where their logs do not)
+__device__ __forceinline__ float head_logaddexp(float a, float b) {
+    const float m = fmaxf(a, b);
+    return m + log1pf(expf(fminf(a, b) - m));
+}
+
+// vbnn_head_predict: one workgroup per 16 minibatch rows walks `draws` draws of them in order (draw s = operand rows s R + r).
+// Per draw the logits are k_head_forward's -- the same K split over HEAD_FW waves (head_logits_wave), the partials added in
+// wave order, the same bias / max / log-sum-exp (head_log_softmax) -- and wave 0 folds them into the running state of its
+// rows (registers; `state` between the launches of the accumulating form). The waves' partials go through two LDS buffers,
+// so the other waves stream the next draw's rows while wave 0 does the row arithmetic: one barrier per draw.
+// The finish writes the outputs; with targets the four totals leave as per-workgroup partials (write-through) that the last
+// workgroup to arrive adds in workgroup order (vbnn_last_arriver).
+template <typename T>
+__global__ __launch_bounds__(64 * HEAD_FW) void k_head_predict(const T* __restrict__ h, int64_t ld_h, const T* __restrict__ w3, int64_t ld_w,
+                                                               const float* __restrict__ bias, const int32_t* __restrict__ target, int64_t R,
+                                                               int64_t Hp, int C, int draws, int S, int first, int final_, float* state,
+                                                               float* probs, float* log_probs, float* entropy, float* expected_entropy,
+                                                               float* mutual_info, int32_t* pred, double* totals, double* part,
+                                                               unsigned* counter) {
+    constexpr int KE = 64 / (int)sizeof(T);
+    constexpr int CE = 16 / (int)sizeof(T);
+    __shared__ f32x4 lp_part[2][HEAD_FW][64];
+    __shared__ double red[4][HEAD_FW];
+    __shared__ int last;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t n0 = (int64_t)blockIdx.x * 16;
+    const int q = lane >> 4, c16 = lane & 15;
+    const int64_t r = n0 + c16;
+    const bool row_ok = r < R;
+    const int64_t rr = min(r, R - 1);
+    const T* wp = w3 + (int64_t)min(c16, C - 1) * ld_w + q * CE;
+    const int64_t ksteps = Hp / KE;
+    const int64_t k_lo = ksteps * wave / HEAD_FW, k_hi = ksteps * (wave + 1) / HEAD_FW;
+    const int64_t W = C + 3;                               // state row: L[0 .. C-1], sum H, sum -o[t], hits
+    const int t = (target && row_ok) ? min(max(target[r], 0), C - 1) : -1;
+    float L[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    float sH = 0.f, sNll = 0.f, sHit = 0.f;
+    if (wave == 0 && !first && row_ok) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (4 * q + j < C) L[j] = state[r * W + 4 * q + j];
+        sH = state[r * W + C]; sNll = state[r * W + C + 1]; sHit = state[r * W + C + 2];
+    }
+    for (int s = 0; s < draws; ++s) {
+        const T* hp = h + ((int64_t)s * R + rr) * ld_h + q * CE;
+        lp_part[s & 1][wave][lane] = head_logits_wave<T>(hp, wp, k_lo, k_hi);
+        __syncthreads();
+        if (wave == 0) {
+            f32x4 acc = lp_part[s & 1][0][lane];
+#pragma unroll
+            for (int w = 1; w < HEAD_FW; ++w) acc += lp_part[s & 1][w][lane];
+            float lg[4], o[4];
+            int arg;
+            float lse;
+            head_log_softmax(acc, q, C, bias, lg, arg, lse);
+            float nll = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] = (4 * q + j < C) ? lg[j] - lse : -INFINITY;
+                if (4 * q + j == t) nll = -o[j];
+            }
+            nll += __shfl_xor(nll, 16, 64);                // one lane of the row holds -o[t], the others 0: exact
+            nll += __shfl_xor(nll, 32, 64);
+            const float ent = head_row_entropy(o, q, C);
+            const float hit = (arg == t) ? 1.f : 0.f;
+            if (first && s == 0) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) L[j] = o[j];
+                sH = ent; sNll = nll; sHit = hit;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (4 * q + j < C) L[j] = head_logaddexp(L[j], o[j]);
+                sH += ent; sNll += nll; sHit += hit;
+            }
+        }
+    }
+    if (!final_) {
+        if (wave == 0 && row_ok) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (4 * q + j < C) state[r * W + 4 * q + j] = L[j];
+            if (q == 0) { state[r * W + C] = sH; state[r * W + C + 1] = sNll; state[r * W + C + 2] = sHit; }
+        }
+        return;
+    }
+    if (wave == 0) {
+        const float logS = logf((float)S);
+        float lp[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lp[j] = (4 * q + j < C) ? L[j] - logS : -INFINITY;
+        float mx;
+        int arg;
+        head_row_max(lp, q, mx, arg);
+        const float ent = head_row_entropy(lp, q, C);
+        const float eH = sH / (float)S;
+        double nll_pred = 0.0;
+        if (row_ok) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = 4 * q + j;
+                if (c < C) {
+                    if (log_probs) log_probs[r * C + c] = lp[j];
+                    if (probs) probs[r * C + c] = expf(lp[j]);
+                    if (c == t) nll_pred = -(double)lp[j];
+                }
+            }
+            if (q == 0) {
+                if (entropy) entropy[r] = ent;
+                if (expected_entropy) expected_entropy[r] = eH;
+                if (mutual_info) mutual_info[r] = ent - eH;
+                if (pred) pred[r] = arg;
+            }
+        }
+        if (totals) {
+            const bool mine = row_ok && q == 0;
+            double v[4] = {nll_pred, (mine && arg == t) ? 1.0 : 0.0, mine ? (double)sNll : 0.0, mine ? (double)sHit : 0.0};
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] += __shfl_xor(v[k], off, 64);
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) vbnn_store_wt(&part[(int64_t)k * gridDim.x + blockIdx.x], v[k]);
+            }
+        }
+    }
+    if (!totals || !vbnn_last_arriver(counter, gridDim.x, &last)) return;
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int b = (int)threadIdx.x; b < (int)gridDim.x; b += 64 * HEAD_FW) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] += vbnn_load_wt(&part[(int64_t)k * gridDim.x + b]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] += __shfl_xor(v[k], off, 64);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) red[k][wave] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double tot = 0.0;
+#pragma unroll
+        for (int w = 0; w < HEAD_FW; ++w) tot += red[threadIdx.x][w];
+        totals[threadIdx.x] = tot;
+    }
 }
 
 // ------------------------------------------------------------------------------------------ backward
@@ -1045,6 +1231,42 @@ extern "C" int vbnn_head_forward_slots(vbnn_ctx* ctx, const float* slots, int64_
                        g_logits, logits, loss_sum_dev, correct_dev, accumulate, part_loss, part_corr, ctx->counters + VBNN_CNT_HEAD_FWD,
                        rows_per_draw);
     return vbnn_check_launch("k_head_from_slots");
+    VBNN_API_END
+}
+
+// mlp.lua:86-107 / main.lua:55-74 / visualize.lua:66-100: the posterior predictive of S draws (include/vbnn_hip.h)
+extern "C" int vbnn_head_predict(vbnn_ctx* ctx, int dtype, const vbnn_predict_args* a) {
+    VBNN_API_BEGIN
+    VBNN_REQUIRE(ctx && a && a->h && a->w3, "null argument");
+    VBNN_REQUIRE(a->R > 0 && a->H > 0 && a->C > 0 && a->C <= HEAD_CMAX, "shape (C <= 16)");
+    VBNN_REQUIRE(a->S >= 1 && a->S < (1ll << 24), "draws S >= 1");
+    VBNN_REQUIRE(a->form == VBNN_PREDICT_STACKED || a->form == VBNN_PREDICT_ACCUMULATE, "form");
+    VBNN_REQUIRE(a->ld_h % VBNN_KPAD == 0 && a->ld_w % VBNN_KPAD == 0 && a->ld_h >= a->H && a->ld_w >= a->H, "h and w3 must be packed operands");
+    VBNN_REQUIRE((((uintptr_t)a->h | (uintptr_t)a->w3) & 15u) == 0, "operands must be 16-byte aligned");
+    VBNN_REQUIRE(!a->totals || a->target, "totals need targets");
+    const bool stacked = a->form == VBNN_PREDICT_STACKED;
+    const int draws = stacked ? (int)a->S : 1;
+    const int first = stacked ? 1 : (a->first ? 1 : 0), fin = stacked ? 1 : (a->final ? 1 : 0);
+    VBNN_REQUIRE(a->state || (first && fin), "the accumulating form keeps its running state in `state`");
+    VBNN_REQUIRE(a->R * draws < (1ll << 40), "rows");
+    const unsigned nb = (unsigned)((a->R + 15) / 16);
+    VBNN_REQUIRE((size_t)nb * 4 <= ctx->scratch_doubles, "minibatch too large for the reduction scratch");
+    double* part = ctx->scratch;                                            // [4][nb] doubles
+    unsigned* ticket = ctx->counters + VBNN_CNT_PREDICT;
+    if (dtype == VBNN_F32) {
+        const int64_t Hp = (a->H + 15) / 16 * 16;
+        hipLaunchKernelGGL(k_head_predict<float>, dim3(nb), dim3(64 * HEAD_FW), 0, ctx->stream, (const float*)a->h, a->ld_h,
+                           (const float*)a->w3, a->ld_w, a->bias, a->target, a->R, Hp, (int)a->C, draws, (int)a->S, first, fin,
+                           a->state, a->probs, a->log_probs, a->entropy, a->expected_entropy, a->mutual_info, a->pred, a->totals,
+                           part, ticket);
+    } else if (dtype == VBNN_BF16) {
+        const int64_t Hp = (a->H + 31) / 32 * 32;
+        hipLaunchKernelGGL(k_head_predict<bf16_t>, dim3(nb), dim3(64 * HEAD_FW), 0, ctx->stream, (const bf16_t*)a->h, a->ld_h,
+                           (const bf16_t*)a->w3, a->ld_w, a->bias, a->target, a->R, Hp, (int)a->C, draws, (int)a->S, first, fin,
+                           a->state, a->probs, a->log_probs, a->entropy, a->expected_entropy, a->mutual_info, a->pred, a->totals,
+                           part, ticket);
+    } else { vbnn_set_error("unsupported dtype %d", dtype); return VBNN_ERR_UNSUPPORTED; }
+    return vbnn_check_launch("k_head_predict");
     VBNN_API_END
 }
 

@@ -72,6 +72,25 @@ class _StepGraph:
             self.h = None
 
 
+class _PredictBuffers(list):
+    """predict's operands per layer input (+ .r, the sequential bf16 forwards' throwaway noise factor)."""
+    r = None
+
+
+class PredictResult:
+    """FusedMLP.predict's outputs for R minibatch rows. Device tensors: probs / log_probs (R x C fp32: the S-draw average
+    1/S sum_s softmax(f_s(x)) and its log), entropy (H[p]), expected_entropy (1/S sum_s H(p_s)), mutual_info (their difference:
+    the epistemic part), pred (int32, argmax p). With targets also Python floats: nll (mean -log p[t]) and accuracy (percent)
+    of the averaged prediction, and mean_draw_nll / mean_draw_accuracy -- the mean over draws of each draw's NLL and accuracy,
+    the two numbers test() returns. None without targets."""
+
+    def __init__(self, probs, log_probs, entropy, expected_entropy, mutual_info, pred):
+        self.probs, self.log_probs, self.entropy = probs, log_probs, entropy
+        self.expected_entropy, self.mutual_info, self.pred = expected_entropy, mutual_info, pred
+        self.nll = self.accuracy = self.mean_draw_nll = self.mean_draw_accuracy = None
+        self.S, self.stacked, self.chunks = None, None, None
+
+
 class FusedMLP:
     def __init__(self, opt, device=None, world_size=1, rank=0, process_group=None, force_reduce=False, stream=None):
         """stream: a torch.cuda.Stream for this engine's launches (a library context of its own, hence its own reduction
@@ -282,6 +301,7 @@ class FusedMLP:
         self._rpd = 0            # > 0 inside run_draws: rows per Monte-Carlo draw of the stacked minibatch
         self._x_in = None        # fp32: the raw minibatch of the current run, read in place by layer 1's GEMMs
         self._draws = None
+        self._shadows_ready = False       # prepare() / update() have packed the operand shadows (predict prepares otherwise)
         self.init_parameters()
 
     # mlp.lua:47-55 (He rule for every weight, bias zero) + the bench's non-degenerate means
@@ -404,6 +424,7 @@ class FusedMLP:
     @_ordered
     def prepare(self):
         lib = L.lib()
+        self._shadows_ready = True                             # (predict: the operand shadows hold the parameters)
         if self._params_stale:
             # after a sharded update: every rank already holds what this sweep would produce -- the gathered operand shadows, the
             # combined prior statistics, the packed final weight (_update_sharded; "update leaves what prepare would" is a test)
@@ -495,6 +516,169 @@ class FusedMLP:
             err += loss * self.world            # the criterion divides by the global batch; this is the local mean
             acc += 100.0 * correct / N
         return err / draws, acc / draws
+
+    # ---- the posterior predictive (vbnn_head_predict): what mlp:test averages as per-draw criteria (mlp.lua:86-107, main.lua:55-74),
+    # averaged as PROBABILITIES, with the per-example uncertainty of visualize.lua:66-100 (show_uncertainties). A forward-only
+    # path on buffers of its own: no r, no transposed outputs, no head slots, no squares out of the last layer, and nothing of
+    # the training step (operands it produces, gradient arena, loss accumulators, batch buffers, argument cache) is written.
+    # It reads the operand shadows as prepare() / update() leave them -- on an engine that has had neither it calls prepare()
+    # first, as test() does; after changing the parameters by hand call prepare(), as before run() -- or draws its own weights
+    # from means / lvars (WN).
+    @_ordered
+    def predict(self, inputs, S=None, targets=None, map=False, row0=None):
+        """p(y | x, D) ~ 1/S sum_s softmax(f_s(x)) over draws self.draw + 1 .. self.draw + S -- the draws test() with
+        opt.testSamples = S consumes -- and `self.draw` advances by S (host and device counter). map=True (or opt.quicktest):
+        one pass on the means, S = 1, no draw consumed. row0: the global row of inputs[0] that addresses the noise (default:
+        this rank's first row, as run()). Returns a PredictResult of this rank's rows (no collective, as test())."""
+        lib, ctx, code = L.lib(), self.ctx.h, self.code
+        Cn = self.n_classes
+        if Cn > 16:
+            raise ValueError(f"predict: the predictive head takes at most 16 classes (n_classes = {Cn})")
+        if self.criterion != "nll":
+            raise ValueError("predict: a class-probability predictive needs the NLL criterion (criterion = 'mse' has none)")
+        map = bool(map or self.opt.get("quicktest"))
+        S = 1 if map else int(self.opt["testSamples"] if S is None else S)
+        if S < 1:
+            raise ValueError(f"predict: S = {S} draws (at least one)")
+        x = inputs.reshape(inputs.shape[0], -1)
+        R = x.shape[0]
+        assert x.shape[1] == self.sizes[0] and x.dtype == torch.float32 and x.is_cuda and R > 0
+        if targets is not None:
+            assert targets.dtype == torch.int32 and targets.is_cuda and targets.numel() == R
+            targets = targets.contiguous()
+        row0 = self.rank * R if row0 is None else int(row0)
+        if not self._shadows_ready:            # a fresh engine: the shadows test() would have prepared
+            self.prepare()
+        lrt = self.mode == "lrt" and not map
+        stacked = self._predict_stacked(R, S, lrt)
+        cap = max(1, int(self.opt.get("predict_rows", 32768)))
+        Rc = max(1, min(R, cap // S if stacked else cap))           # minibatch rows per chunk: S Rc (stacked) or Rc operand rows
+        bufs = self._predict_buffers(S * Rc if stacked else Rc, lrt)
+        wts = self._predict_weights() if self.mode == "wn" else None
+        f32 = dict(dtype=torch.float32, device=self.device)
+        res = PredictResult(torch.empty(R, Cn, **f32), torch.empty(R, Cn, **f32), torch.empty(R, **f32), torch.empty(R, **f32),
+                            torch.empty(R, **f32), torch.empty(R, dtype=torch.int32, device=self.device))
+        n_chunks = (R + Rc - 1) // Rc
+        totals = torch.zeros(n_chunks, 4, dtype=torch.float64, device=self.device) if targets is not None else None
+        state = torch.empty(Rc, Cn + 3, **f32) if not stacked else None
+        d0 = self.draw + 1                                           # the first draw's counter (sample() then run())
+        nl = len(self.vb)
+        a = L.PredictArgs(w3=self.w3_s.ptr, ld_w=self.w3_s.ld, bias=_p(self.bias3), H=self.sizes[-1], C=Cn, S=S,
+                          form=L.PREDICT_STACKED if stacked else L.PREDICT_ACCUMULATE, state=_p(state))
+        for k in range(n_chunks):
+            c0 = k * Rc
+            rows = min(Rc, R - c0)
+            xc = x[c0:c0 + rows]
+            a.h, a.ld_h = bufs[nl].x.ptr, bufs[nl].x.ld
+            a.R = rows
+            a.target = C.c_void_p(targets.data_ptr() + 4 * c0) if targets is not None else None
+            a.totals = C.c_void_p(totals[k].data_ptr()) if totals is not None else None
+            for name, t in (("probs", res.probs), ("log_probs", res.log_probs)):
+                setattr(a, name, C.c_void_p(t.data_ptr() + 4 * Cn * c0))
+            for name, t in (("entropy", res.entropy), ("expected_entropy", res.expected_entropy), ("mutual_info", res.mutual_info),
+                            ("pred", res.pred)):
+                setattr(a, name, C.c_void_p(t.data_ptr() + 4 * c0))
+            if stacked:                        # every draw in one pass: the chunk stacked S times as rows, draw s = rows [s rows, (s+1) rows)
+                if wts is not None:            # (weight noise: S = 1)
+                    self._predict_wn_sample(wts, None if map else d0)
+                self._predict_forward(bufs, wts, xc, S * rows, rows if S > 1 else 0, d0, row0 + c0, lrt)
+                L.check(lib.vbnn_head_predict(ctx, code, C.byref(a)))
+                continue
+            for s in range(S):                 # one draw per forward, the running state between the head's launches
+                if wts is not None:
+                    self._predict_wn_sample(wts, d0 + s)
+                self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
+                a.first, a.final = int(s == 0), int(s == S - 1)
+                L.check(lib.vbnn_head_predict(ctx, code, C.byref(a)))
+        if not map:                            # the draws test() would have consumed
+            self.draw += S
+            if self.device_draw:
+                L.check(lib.vbnn_sample(ctx, _p(self._draw_dev), S))
+        if totals is not None:
+            tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
+            res.totals = tot
+            res.nll, res.accuracy = tot[0] / R, 100.0 * tot[1] / R
+            res.mean_draw_nll, res.mean_draw_accuracy = tot[2] / (R * S), 100.0 * tot[3] / (R * S)
+        res.S, res.stacked, res.chunks = S, stacked, n_chunks
+        return res
+
+    def _predict_stacked(self, R, S, lrt):
+        """opt.predict_stacked: True / False / "auto" (default). Weight noise draws a weight matrix per draw: sequential always.
+        "auto": stacked while one draw's widest forward is small (R I O < 2^32 multiply-adds: the reference's operating points,
+        launch-bound, where S launches become one), sequential above -- stacked rows never run on the two-pass 256 x 256 kernel
+        (vbnn_fwd_args.rows_per_draw), which is what the large bf16 forwards take one draw at a time (tools/predict_bench.py)."""
+        if not lrt or S == 1:
+            return S == 1 or lrt
+        ps = self.opt.get("predict_stacked", "auto")
+        if ps != "auto":
+            return bool(ps)
+        rows = min(R, max(1, int(self.opt.get("predict_rows", 32768))))
+        return rows * max(v.I * v.O for v in self.vb) < (1 << 32)
+
+    def _predict_buffers(self, rows, lrt):
+        """predict's operands: the packed input, then one ping-pong PAIR of activation (+ square) buffers per hidden width --
+        layer li writes slot (O, li % 2), so a layer never overwrites its own input and a buffer always holds one layout (its
+        pads stay zero). bufs[li] is layer li's input, bufs[len(vb)] the head's. Kept across calls while the row count holds."""
+        sq = lrt and self.dtype == "bf16"                       # (fp32: the forward forms x.x from x itself)
+        key = (rows, sq)
+        if getattr(self, "_pred_key", None) != key:
+            self._pred_bufs, self._pred_key = None, None
+            dev, tdt, nl = self.device, self.tdt, len(self.vb)
+            slots = {}
+
+            def slot(cols, parity, square):
+                b = slots.get((cols, parity))
+                if b is None:
+                    b = slots[(cols, parity)] = _VB()
+                    b.x, b.x2 = _Packed(rows, cols, tdt, dev), None
+                if square and b.x2 is None:
+                    b.x2 = _Packed(rows, cols, tdt, dev)
+                return b
+            bufs = _PredictBuffers([slot(self.sizes[0], "in", sq)])
+            for li, v in enumerate(self.vb):
+                bufs.append(slot(v.O, li % 2, sq and li < nl - 1))
+            bufs.r = _Packed(rows, max(v.O for v in self.vb), tdt, dev) if sq else None
+            self._pred_bufs, self._pred_key = bufs, key
+        return self._pred_bufs
+
+    def _predict_weights(self):
+        """WN: predict's own sampled weights (fp32) and their packed shadows, per layer (sample() keeps its draw in the training
+        operands; predict leaves them alone)."""
+        if getattr(self, "_pred_wts", None) is None:
+            self._pred_wts = [(torch.zeros(v.O, v.I, dtype=torch.float32, device=self.device), _Packed(v.O, v.I, self.tdt, self.device))
+                              for v in self.vb]
+        return self._pred_wts
+
+    def _predict_wn_sample(self, wts, draw):
+        """VBLinear:sample (VBLinear.lua:49-64) for `draw` into predict's weights; draw None: the means (clamp_to_map)."""
+        lib = L.lib()
+        for v, (w, ws) in zip(self.vb, wts):
+            if draw is not None:
+                L.check(lib.vbnn_wn_sample(self.ctx.h, _p(v.means), None, _p(v.lvars), _p(w), None, v.O, v.I, self.seed, v.layer_id, draw))
+            L.check(lib.vbnn_pack(self.ctx.h, self.code, L.PACK_COPY, _p(w if draw is not None else v.means), None, v.I, v.O, v.I,
+                                  ws.ptr, ws.ld, None, 0))
+
+    def _predict_forward(self, bufs, wts, x, N, rpd, draw, row0, lrt, pack=True):
+        """vbnn_pack_input + every VB layer's forward for predict: N operand rows (rpd > 0: stacked draws of rpd rows each)."""
+        lib, ctx, code = L.lib(), self.ctx.h, self.code
+        if pack:
+            b0 = bufs[0]
+            L.check(lib.vbnn_pack_input(ctx, code, _p(x), x.stride(0), N, self.sizes[0], b0.x.ptr, b0.x2.ptr if b0.x2 else None,
+                                        b0.x.ld, None, None, 0, rpd))
+        nl = len(self.vb)
+        for li, v in enumerate(self.vb):
+            xin, out = bufs[li], bufs[li + 1]
+            w = wts[li][1] if wts is not None else v.mu_s
+            # r: nobody reads it. Only the sequential bf16 LRT forwards are handed a throwaway one -- the two-pass 256 x 256
+            # kernel, which the large one-draw forwards take, stores r as part of its fold and is not selected without it.
+            r = bufs.r if (lrt and rpd == 0 and bufs.r is not None) else None
+            a = L.FwdArgs(w=w.ptr, w2=v.var_s.ptr if lrt else None, x=xin.x.ptr, x2=xin.x2.ptr if (lrt and xin.x2) else None,
+                          ld_w=w.ld, ld_x=xin.x.ld, N=N, I=v.I, O=v.O, bias=_p(v.bias), seed=self.seed, layer=v.layer_id,
+                          draw=draw, draw_dev=None, row0=row0, y=None, ld_y=0, r=r.ptr if r else None, ld_r=r.ld if r else 0,
+                          r_packed=1, relu=1,
+                          h=out.x.ptr, h2=out.x2.ptr if (lrt and li < nl - 1 and out.x2) else None, ld_h=out.x.ld,
+                          hT=None, h2T=None, ld_hT=0, rows_per_draw=rpd)
+            L.check(lib.vbnn_forward(ctx, code, C.byref(a)))
 
     # ---- mlp.lua:69-74
     @_ordered
@@ -1003,6 +1187,7 @@ class FusedMLP:
                 L.check(lib.vbnn_transpose_packed(h, self.code, v.mu_s.ptr, v.mu_s.ld, v.O, v.I, v.muT_s.ptr, v.muT_s.ld))
                 L.check(lib.vbnn_transpose_packed(h, self.code, v.var_s.ptr, v.var_s.ld, v.O, v.I, v.varT_s.ptr, v.varT_s.ld))
         self._params_stale = W > 1
+        self._shadows_ready = True
 
     def exchange(self):
         if self._exchange is None:
@@ -1142,6 +1327,7 @@ class FusedMLP:
         w3 = L.PackDesc(src=_p(self.weight3), rows=self.n_classes, cols=self.sizes[-1], ld_src=self.sizes[-1],
                         dst=self.w3_s.ptr, ld_dst=self.w3_s.ld, dstT=self.w3T_s.ptr, ld_dstT=self.w3T_s.ld)
         L.check(lib.vbnn_update(h, self.code, len(self.vb), descs, C.byref(w3)))
+        self._shadows_ready = True
 
     # ---- reporting (each of these synchronises)
     def loss_and_accuracy(self):

@@ -101,12 +101,19 @@ class Main:
         bs, n = int(opt["testBatchSize"]), int(opt["testSize"])
         starts = list(range(0, n - bs + 1, bs))
         accuracy = error = 0.0
+        pred = {"devacc_pred": 0.0, "devnll_pred": 0.0, "dev_mi": 0.0}
         for t0 in starts:
             inputs, targets = dataset.create_minibatch(t0, bs, n, opt.get("geometry"))
             x, t = self._to_device(inputs, targets)
             err, acc = net.test(x, t)
             accuracy += acc
             error += err
+            if opt.get("predictive"):      # the S-draw model average on the same minibatch (its own draws, after test()'s)
+                r = net.predict(x, targets=t)
+                pred["devacc_pred"] += r.accuracy
+                pred["devnll_pred"] += r.nll
+                pred["dev_mi"] += float(r.mutual_info.double().mean())
+        self.predictive = {k: v / len(starts) for k, v in pred.items()} if opt.get("predictive") else None
         return accuracy / len(starts), error / len(starts)
 
     def save(self):
@@ -125,12 +132,14 @@ class Main:
             trainAccuracy, trainError = self.train(trainSet)
             testAccuracy, testError = self.test(testSet)
             rec = {"devacc": testAccuracy, "trainacc": trainAccuracy, "deverr": testError, "trainerr": trainError}
+            if getattr(self, "predictive", None):                                          # opt.predictive
+                rec.update(self.predictive)
             if getattr(self.net, "sharded", False):
                 self.net.gather_parameters()              # collective (every rank runs this loop): calc_lc and save read fp32 rows
             if self.opt.get("type", "vb") == "vb":
                 rec["lc"] = self.net.calc_lc(self.opt)
             if self.log:
-                for k in ("devacc", "trainacc", "deverr", "trainerr", "lc"):              # main.lua:169-177
+                for k in ("devacc", "trainacc", "deverr", "trainerr", "lc", "devacc_pred", "devnll_pred", "dev_mi"):   # main.lua:169-177 (+ opt.predictive)
                     if k in rec:
                         self.log.add(k, rec[k])
                 self.log.flush()
