@@ -654,6 +654,40 @@ typedef struct vbnn_predict_args {
 } vbnn_predict_args;
 int vbnn_head_predict(vbnn_ctx* ctx, int dtype, const vbnn_predict_args* a);
 
+/* ---- signal-to-noise pruning (additive, ABI 6): mainviz.lua:20-27 on the device, and the pruned operand shadows that let
+ * vbnn_forward / vbnn_head_predict evaluate the pruned network ---------------------------------------------------------------
+ * The key of a weight is snr = |means / sqrt(exp(lvars))| in fp32, operation for operation as mainviz.lua:20 forms
+ * torch.abs(torch.cdiv(means, torch.sqrt(vars))); all three calls below compute it with ONE device function, so a weight has
+ * the same key bits in each. A NaN key (a NaN parameter) orders above every number and is never pruned. */
+typedef struct vbnn_prune_desc {
+    const float* means; const float* lvars; int64_t O, I;     /* the layer's fp32 parameters, O x I */
+    /* vbnn_prune_pack only (vbnn_prune_select and vbnn_prune_workspace_bytes read the four fields above): */
+    void* mu_p; void* var_p; int64_t ld_w;     /* pruned operand shadows, O x ld_w of dtype (allocate zeroed: pads are not written) */
+    double* stats;                             /* 4 doubles, below */
+    uint8_t* mask;                             /* optional O x I bytes, 1 = pruned (the `pruned` tensor of mainviz.lua:21); NULL to skip */
+} vbnn_prune_desc;
+/* mainviz.lua:20: snr_out[i] = the key of weight i (W floats): what nn.VBLinear exposes as :snr(). */
+int vbnn_snr(vbnn_ctx* ctx, const float* means, const float* lvars, int64_t W, float* snr_out);
+/* mainviz.lua:20-21 turned round: tau_dev[0] = the EXACT k-th smallest key (0-based) over the union of the listed layers'
+ * weights (n_layers <= 8; one layer = per-layer pruning, all of them = global), so that `key < tau` prunes at most k weights
+ * (fewer when keys tie at tau). A radix select on the key's 32 bits (11 + 11 + 10): per digit one histogram sweep per layer
+ * (integer counts: bitwise reproducible whatever the order of the atomics) and a one-workgroup kernel that picks the bin and
+ * hands prefix and remaining rank to the next pass in device words. No host synchronisation, no allocation: the caller
+ * passes `workspace` of at least vbnn_prune_workspace_bytes(...) bytes (4-byte aligned; contents irrelevant). Every pass
+ * re-forms the keys from means / lvars (8 B per weight read, nothing per weight written). 0 <= k < W_total, else
+ * VBNN_ERR_INVALID (to prune everything pass tau = +inf to vbnn_prune_pack). Fewer than 2^32 weights in all. */
+int vbnn_prune_workspace_bytes(int n_layers, const vbnn_prune_desc* layers, size_t* bytes);
+int vbnn_prune_select(vbnn_ctx* ctx, int n_layers, const vbnn_prune_desc* layers, int64_t k, float* tau_dev,
+                      void* workspace, size_t workspace_bytes);
+/* mainviz.lua:21-27: pruned = key < tau (strict, torch.lt) with tau = tau_dev[0] read on the device (chained behind
+ * vbnn_prune_select without a host round trip), or tau_host when tau_dev is NULL. One sweep per layer and ONE finish kernel
+ * for all layers (the shape of vbnn_prepare). Per layer: mu_p / var_p -- a kept weight's two values are bitwise what
+ * vbnn_prepare writes to mu_s / var_s, a pruned weight's are +0 in both (no mean, no variance); stats[0..3] = { number
+ * pruned, sum of exp(lvars) over the pruned weights, sum of exp(lvars) over all weights, W } -- pruned:sum(),
+ * prunedvars:mean() W and vars:mean() W of mainviz.lua:22-27 -- from per-workgroup partials added in a fixed order (two
+ * runs give the same bits); and optionally the byte mask. No transposed shadows: the predictive path is forward-only. */
+int vbnn_prune_pack(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prune_desc* layers, const float* tau_dev, float tau_host);
+
 /* The same criterion as separate modules, for the module-level call order of mlp.lua:77-80:
  * nn.LogSoftMax:updateOutput is vbnn_logsoftmax_nll with g_logits = loss = correct = NULL. */
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,

@@ -389,6 +389,7 @@ end
 -- shadows and prior statistics of the next minibatch; `log` (a FloatTensor-free double[14 * layers] on the device)
 function FusedMLP:update(opt, log14)
     self:finish()
+    self.version = (self.version or 0) + 1                          -- a pruned view (:prune) is a snapshot of one version
     if self.sharded then return self:_update_sharded(opt) end
     local lr = opt.state.learningRate
     local H = self.sizes[#self.sizes]
@@ -440,6 +441,76 @@ function FusedMLP:loss_and_accuracy()
     return a[0], c[0]
 end
 
+-- signal-to-noise pruning (mainviz.lua:20-27; engine.py:FusedMLP.prune, tools/c_host.c:fm_prune): every weight with
+-- |mu| / sigma < tau. Exactly one of `fraction` (0 .. 1: tau = the exact k-th smallest key, k = floor(fraction W); 1 = everything,
+-- tau = +inf) and `threshold` (tau itself; the reference's 0.005); scope 'global' (one tau over all VB layers, the default) or
+-- 'layer' (the fraction per layer). Returns a table: tau[li], layers[li] = { n_pruned, W, fraction_pruned, mean_var,
+-- mean_pruned_var }, the same five as totals (the numbers mainviz.lua:22-27 prints), and the pruned operand shadows mu_p[li] /
+-- var_p[li] that predict() reads once the table is handed to use_pruned.
+function FusedMLP:prune(fraction, threshold, scope)
+    assert((fraction == nil) ~= (threshold == nil), 'prune: exactly one of fraction and threshold')
+    scope = scope or 'global'
+    assert(scope == 'global' or scope == 'layer', "prune: scope 'global' or 'layer'")
+    assert(fraction == nil or (fraction >= 0 and fraction <= 1), 'prune: fraction in 0 .. 1')
+    local n = #self.vb
+    local o = { scope = scope, tau = {}, layers = {}, mu_p = {}, var_p = {} }
+    local stats, tau = vb.alloc(32 * n), vb.alloc(4 * n)
+    local function descs(first, count)
+        local d = ffi.new('vbnn_prune_desc[?]', count)
+        for j = 0, count - 1 do
+            local v, e = self.vb[first + j], d[j]
+            e.means, e.lvars, e.O, e.I = f32(v.means), f32(v.lvars), v.O, v.I
+            e.mu_p, e.var_p, e.ld_w = o.mu_p[first + j].p, o.var_p[first + j].p, o.mu_p[first + j].ld
+            e.stats = ffi.cast('double*', stats) + 4 * (first + j - 1)
+            e.mask = nil
+        end
+        return d
+    end
+    for li, v in ipairs(self.vb) do o.mu_p[li], o.var_p[li] = packed(v.O, v.I, self.esize), packed(v.O, v.I, self.esize) end
+    local nbytes = ffi.new('size_t[1]')
+    check(C.vbnn_prune_workspace_bytes(n, descs(1, n), nbytes))
+    local ws = vb.alloc(tonumber(nbytes[0]))
+    local groups = (scope == 'global') and { { 1, n } } or {}
+    if scope == 'layer' then for li = 1, n do groups[li] = { li, 1 } end end
+    local selected = {}
+    for _, g in ipairs(groups) do
+        local d, Wg = descs(g[1], g[2]), 0
+        for li = g[1], g[1] + g[2] - 1 do Wg = Wg + self.vb[li].O * self.vb[li].I end
+        local k = fraction and math.floor(fraction * Wg) or Wg
+        local tau_g = nil
+        if k < Wg then                                             -- the threshold stays on the device, behind the select
+            tau_g = f32(tau) + (g[1] - 1)
+            check(C.vbnn_prune_select(vb.ctx, g[2], d, k, tau_g, ws, nbytes[0]))
+        end
+        check(C.vbnn_prune_pack(vb.ctx, self.dtype, g[2], d, tau_g, threshold or math.huge))
+        for li = g[1], g[1] + g[2] - 1 do selected[li] = tau_g and g[1] or false end
+    end
+    local sh, th = ffi.new('double[?]', 4 * n), ffi.new('float[?]', n)
+    check(C.vbnn_buf_download(vb.ctx, sh, stats, 32 * n))
+    check(C.vbnn_buf_download(vb.ctx, th, tau, 4 * n))
+    local function summary(np, sp, sa, W)
+        return { n_pruned = np, W = W, fraction_pruned = np / W, mean_var = sa / W, mean_pruned_var = sp / np }
+    end
+    local tot = { 0, 0, 0, 0 }
+    for li = 1, n do
+        o.tau[li] = selected[li] and th[selected[li] - 1] or (threshold or math.huge)
+        o.layers[li] = summary(sh[4 * li - 4], sh[4 * li - 3], sh[4 * li - 2], sh[4 * li - 1])
+        for j = 1, 4 do tot[j] = tot[j] + sh[4 * li - 5 + j] end
+    end
+    local t = summary(tot[1], tot[2], tot[3], tot[4])
+    o.n_pruned, o.W, o.fraction_pruned, o.mean_var, o.mean_pruned_var = t.n_pruned, t.W, t.fraction_pruned, t.mean_var, t.mean_pruned_var
+    o.owner, o.version = self, self.version or 0
+    return o
+end
+
+-- predict() reads the pruned operands of `result` (a table from :prune) from now on; nil: the unpruned shadows again. Nothing
+-- else looks at the view. A view is a snapshot: prune again after update() (self.version counts the updates).
+function FusedMLP:use_pruned(result)
+    assert(result == nil or result.owner == self, 'use_pruned: a result of this :prune, or nil')
+    assert(result == nil or result.version == (self.version or 0), 'use_pruned: the parameters changed since this result was taken')
+    self.pruned_view = result
+end
+
 -- the posterior predictive (engine.py:FusedMLP.predict, tools/c_host.c:fm_predict): mlp:test's S draws averaged as probabilities
 -- (mlp.lua:86-107, main.lua:55-74, visualize.lua:66-100), forward-only on buffers of its own (in_x[li]: layer li's input,
 -- in_x[#vb + 1] the head's; r: a throwaway noise factor for the one-draw bf16 forwards). Consumes draws draw + 1 .. draw + S, as
@@ -448,6 +519,7 @@ end
 -- numbers mlp:test returns), accuracies in percent. opt: predict_rows (32768), predict_stacked ('auto' / true / false).
 function FusedMLP:predict(inputs, ld, targets, R, S, opt)
     opt = opt or {}
+    assert(not self.pruned_view or self.pruned_view.version == (self.version or 0), 'predict: the pruned view is of older parameters')
     local nc, cap = self.n_classes, opt.predict_rows or 32768
     local widest, omax = 0, 0
     for _, v in ipairs(self.vb) do widest, omax = math.max(widest, v.I * v.O), math.max(omax, v.O) end
@@ -524,7 +596,9 @@ function FusedMLP:_predict_forward(in_x, in_x2, r, x, ld, N, rpd, draw, row0, pa
     end
     for li, v in ipairs(self.vb) do
         local fa = ffi.new('vbnn_fwd_args')
-        fa.w, fa.w2, fa.x, fa.ld_w, fa.ld_x = v.mu_s.p, v.var_s.p, in_x[li].p, v.mu_s.ld, in_x[li].ld
+        local pv = self.pruned_view                                -- a pruned view (:use_pruned): ITS shadows in place of mu_s / var_s
+        local mu, var = pv and pv.mu_p[li] or v.mu_s, pv and pv.var_p[li] or v.var_s
+        fa.w, fa.w2, fa.x, fa.ld_w, fa.ld_x = mu.p, var.p, in_x[li].p, mu.ld, in_x[li].ld
         fa.x2 = in_x2[li] and in_x2[li].p or nil
         fa.N, fa.I, fa.O, fa.bias = N, v.I, v.O, f32(v.bias)
         fa.seed, fa.layer, fa.draw, fa.row0, fa.draw_dev = self.seed, v.layer_id, draw, row0, nil

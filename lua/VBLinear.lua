@@ -234,6 +234,15 @@ function VBLinear:calc_lc(opt)                                      -- VBLinear.
     return torch.Tensor(1):fill(s[0])
 end
 
+-- mainviz.lua:20: the signal-to-noise ratio |means / sqrt(exp(lvars))| per weight (the pruning key) as an O x I FloatTensor
+function VBLinear:snr()
+    local f = function(p) return ffi.cast('float*', p) end
+    local out, d_out = torch.FloatTensor(self.means:size(1), self.means:size(2)), vb.alloc(self.W * 4)
+    check(C.vbnn_snr(vb.ctx, f(self.d.means), f(self.d.lvars), self.W, f(d_out)))
+    check(C.vbnn_buf_download(vb.ctx, out:data(), d_out, self.W * 4))
+    return out
+end
+
 -- VBLinear:update (VBLinear.lua:124-166): SGD on the bias, compute_prior, likelihood + KL gradients, Adam on means
 -- (opt.meanState) and on lvars (opt.varState) with per-layer moment state -- on the device (vbnn_sgd_step /
 -- vbnn_adam_step: one streaming pass per tensor, the two gradient parts added inside it); the host tensors are

@@ -248,6 +248,17 @@ typedef struct vbnn_predict_args {
     double* totals;
 } vbnn_predict_args;
 int vbnn_head_predict(vbnn_ctx* ctx, int dtype, const vbnn_predict_args* a);
+typedef struct vbnn_prune_desc {
+    const float* means; const float* lvars; int64_t O, I;
+    void* mu_p; void* var_p; int64_t ld_w;
+    double* stats;
+    uint8_t* mask;
+} vbnn_prune_desc;
+int vbnn_snr(vbnn_ctx* ctx, const float* means, const float* lvars, int64_t W, float* snr_out);
+int vbnn_prune_workspace_bytes(int n_layers, const vbnn_prune_desc* layers, size_t* bytes);
+int vbnn_prune_select(vbnn_ctx* ctx, int n_layers, const vbnn_prune_desc* layers, int64_t k, float* tau_dev,
+                      void* workspace, size_t workspace_bytes);
+int vbnn_prune_pack(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prune_desc* layers, const float* tau_dev, float tau_host);
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,
                      float inv_n, double* loss_sum_dev, int32_t* correct_dev);
 int vbnn_nll_backward(vbnn_ctx* ctx, const int32_t* target, int64_t N, int64_t C, float inv_n, float* g);

@@ -14,10 +14,13 @@
  *
  *   c_host --dtype f32|bf16 --input 784 --hidden 400,400 --classes 10 --batch 256 [--S 1] [--steps 2] [--update]
  *          [--comm [--sharded]] [--graph] [--kl-shadows] [--seed 3] --out arena.bin
- *          [--predict S [--predict-rows 32768] [--predict-stacked -1|0|1]]
+ *          [--predict S [--predict-rows 32768] [--predict-stacked -1|0|1] [--prune Q | --prune-threshold T]]
  *   --predict S: after the steps, the posterior predictive of the minibatch over S draws (fm_predict), appended to the file:
  *   int64 R, int64 C, int32 S, stacked, chunks, draw counter after it; probs and log_probs (R x C floats); entropy,
  *   expected_entropy, mutual_info (R floats each); pred (R int32); the four totals (doubles). Without it the file is as above.
+ *   --prune Q | --prune-threshold T (with --predict S): then the signal-to-noise pruning (fm_prune: the fraction Q of all VB weights, or
+ *   every weight below T) and the predictive once more under the pruned view, appended: int32 layers, float tau, per layer four
+ *   doubles (pruned, sum of pruned variances, sum of variances, W), then a second predict block as above (S more draws).
  *   --graph: the context gets a stream of its own (vbnn_ctx_create_cu_budget), the draw counter lives on the device
  *   (vbnn_fwd_args.draw_dev, vbnn_sample), step 2 is CAPTURED (vbnn_capture_begin / _end) and steps 2.. are replays of it.
  *   arena.bin: int64 n_grads, double loss, int32 correct, int32 flags, then n_grads floats (the arena after the last
@@ -106,6 +109,7 @@ typedef struct {
     int first;
     int64_t N;
     vbnn_comm* comm;
+    const packed_t *view_mu, *view_var;   /* the pruned view (fm_prune): per layer, read by fm_predict_forward in place of mu_s / var_s; NULL: none */
 } fused_mlp;
 
 /* ---- FusedMLP.new (lua/FusedMLP.lua; engine.py:FusedMLP.__init__ + init_parameters) */
@@ -514,6 +518,48 @@ static void fm_loss_and_accuracy(fused_mlp* m, double* loss, int32_t* correct) {
     *loss = a[0];
 }
 
+/* ---- signal-to-noise pruning (mainviz.lua:20-27; engine.py:FusedMLP.prune, lua/FusedMLP.lua:prune), scope 'global': every weight
+   with |mu| / sigma < tau, tau the threshold itself (fraction < 0) or the exact k-th smallest key, k = floor(fraction W)
+   (fraction = 1: everything, tau = +inf). Leaves the pruned operand shadows and the numbers mainviz.lua:22-27 prints. */
+typedef struct {
+    packed_t mu_p[MAX_LAYERS], var_p[MAX_LAYERS];
+    float tau;
+    double stats[MAX_LAYERS][4];                                           /* per layer: pruned, sum of pruned vars, sum of vars, W */
+} prune_out;
+
+static void fm_prune(fused_mlp* m, double fraction, float threshold, prune_out* o) {
+    const int n = m->n_layers;
+    vbnn_prune_desc d[MAX_LAYERS];
+    double* stats = (double*)dev_alloc((size_t)n * 4 * 8);
+    float* tau = (float*)dev_alloc(4);
+    int64_t W = 0;
+    memset(d, 0, sizeof d);
+    for (int li = 0; li < n; ++li) {
+        layer_t* v = &m->vb[li];
+        o->mu_p[li] = packed(v->O, v->I, m->esize); o->var_p[li] = packed(v->O, v->I, m->esize);
+        d[li].means = v->means; d[li].lvars = v->lvars; d[li].O = v->O; d[li].I = v->I;
+        d[li].mu_p = o->mu_p[li].p; d[li].var_p = o->var_p[li].p; d[li].ld_w = o->mu_p[li].ld;
+        d[li].stats = stats + 4 * li; d[li].mask = NULL;
+        W += v->O * v->I;
+    }
+    size_t nbytes = 0;
+    CHECK(vbnn_prune_workspace_bytes(n, d, &nbytes));
+    void* ws = dev_alloc(nbytes);
+    const int64_t k = fraction >= 0 ? (int64_t)floor(fraction * (double)W) : W;
+    const float* tau_dev = NULL;
+    o->tau = fraction >= 0 ? INFINITY : threshold;
+    if (k < W) {                                                           /* the threshold stays on the device, behind the select */
+        tau_dev = tau;
+        CHECK(vbnn_prune_select(g_ctx, n, d, k, tau, ws, nbytes));
+    }
+    CHECK(vbnn_prune_pack(g_ctx, m->dtype, n, d, tau_dev, o->tau));
+    CHECK(vbnn_buf_download(g_ctx, o->stats, stats, (size_t)n * 4 * 8));
+    if (tau_dev) CHECK(vbnn_buf_download(g_ctx, &o->tau, tau, 4));
+}
+static void fm_use_pruned(fused_mlp* m, const prune_out* o) {
+    m->view_mu = o ? o->mu_p : NULL; m->view_var = o ? o->var_p : NULL;
+}
+
 /* ---- the posterior predictive (engine.py:FusedMLP.predict, lua/FusedMLP.lua:predict): mlp:test's S draws averaged as
    probabilities (mlp.lua:86-107, main.lua:55-74, visualize.lua:66-100). Forward-only, on buffers of its own: in_x[li] is layer
    li's input (in_x[n_layers] the head's), r a throwaway noise factor for the one-draw bf16 forwards (the two-pass kernel stores it). */
@@ -532,7 +578,9 @@ static void fm_predict_forward(fused_mlp* m, const packed_t* in_x, const packed_
         layer_t* v = &m->vb[li];
         vbnn_fwd_args a;
         memset(&a, 0, sizeof a);
-        a.w = v->mu_s.p; a.w2 = v->var_s.p; a.x = in_x[li].p; a.x2 = in_x2[li].p; a.ld_w = v->mu_s.ld; a.ld_x = in_x[li].ld;
+        const packed_t* mu = m->view_mu ? &m->view_mu[li] : &v->mu_s;      /* a pruned view: ITS shadows in place of mu_s / var_s */
+        const packed_t* var = m->view_var ? &m->view_var[li] : &v->var_s;
+        a.w = mu->p; a.w2 = var->p; a.x = in_x[li].p; a.x2 = in_x2[li].p; a.ld_w = mu->ld; a.ld_x = in_x[li].ld;
         a.N = N; a.I = v->I; a.O = v->O; a.bias = v->bias;
         a.seed = m->seed; a.layer = v->layer_id; a.draw = draw; a.row0 = row0; a.draw_dev = NULL;
         a.r = (rpd == 0) ? r->p : NULL; a.ld_r = (rpd == 0 && r->p) ? r->ld : 0; a.r_packed = 1; a.relu = 1;
@@ -709,7 +757,22 @@ int main(int argc, char** argv) {
             free(mu);
         }
     const int predict_S = atoi(arg_value(argc, argv, "--predict", "0"));
-    if (predict_S > 0) {       /* --predict S: the posterior predictive of the minibatch after the steps, appended to the file */
+    const char* prune_q = arg_value(argc, argv, "--prune", NULL);
+    const char* prune_t = arg_value(argc, argv, "--prune-threshold", NULL);
+    const int prune_passes = (predict_S > 0 && (prune_q || prune_t)) ? 2 : 1;
+    prune_out pr;
+    for (int pass = 0; pass < prune_passes && predict_S > 0; ++pass) {
+        /* --predict S: the posterior predictive of the minibatch after the steps, appended to the file; with --prune Q /
+           --prune-threshold T once more under the pruned view, behind the numbers of the pruning */
+        if (pass == 1) {
+            fm_prune(&net, prune_q ? atof(prune_q) : -1.0, prune_t ? (float)atof(prune_t) : 0.f, &pr);
+            fm_use_pruned(&net, &pr);
+            const int32_t nl = n_layers;
+            fwrite(&nl, 4, 1, f); fwrite(&pr.tau, 4, 1, f); fwrite(pr.stats, 8, (size_t)4 * n_layers, f);
+            double np = 0, W = 0;
+            for (int li = 0; li < n_layers; ++li) { np += pr.stats[li][0]; W += pr.stats[li][3]; }
+            printf("c_host: pruned %.0f of %.0f weights below snr %.9g\n", np, W, (double)pr.tau);
+        }
         predict_out po;
         fm_predict(&net, x, sizes[0], t, N, predict_S, atoll(arg_value(argc, argv, "--predict-rows", "32768")),
                    atoi(arg_value(argc, argv, "--predict-stacked", "-1")), &po);
@@ -728,6 +791,7 @@ int main(int argc, char** argv) {
         printf("c_host: predict S %d over %lld rows (%s, %d chunk(s)): mean NLL %.9g, accuracy %.4f%%\n", po.S, (long long)po.R,
                po.stacked ? "stacked" : "sequential", po.chunks, po.totals[0] / (double)po.R, 100.0 * po.totals[1] / (double)po.R);
     }
+    fm_use_pruned(&net, NULL);
     fclose(f);
     free(arena);
     printf("c_host: %s %lld", dtype == VBNN_F32 ? "f32" : "bf16", (long long)sizes[0]);

@@ -97,6 +97,12 @@ class PredictArgs(C.Structure):       # vbnn_predict_args
 
 PREDICT_STACKED, PREDICT_ACCUMULATE = 0, 1
 
+
+class PruneDesc(C.Structure):         # vbnn_prune_desc
+    _fields_ = [("means", _vp), ("lvars", _vp), ("O", _i64), ("I", _i64), ("mu_p", _vp), ("var_p", _vp), ("ld_w", _i64),
+                ("stats", _vp), ("mask", _vp)]
+
+
 _SIGS = {
     "vbnn_abi_version": ([], _i),
     "vbnn_last_error": ([], C.c_char_p),
@@ -180,6 +186,10 @@ _SIGS = {
                            _vp, _i64, _vp, _vp, _i64], _i),
     "vbnn_mse_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _vp, _i64, _i, _vp], _i),
     "vbnn_mse_backward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _vp, _i64], _i),
+    "vbnn_snr": ([_vp, _vp, _vp, _i64, _vp], _i),
+    "vbnn_prune_workspace_bytes": ([_i, _vp, C.POINTER(C.c_size_t)], _i),
+    "vbnn_prune_select": ([_vp, _i, _vp, _i64, _vp, _vp, C.c_size_t], _i),
+    "vbnn_prune_pack": ([_vp, _i, _i, _vp, _vp, _f], _i),
     "vbnn_nll_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _f, _vp, _vp], _i),
     "vbnn_nll_backward": ([_vp, _vp, _i64, _i64, _f, _vp], _i),
     "vbnn_logsoftmax_backward": ([_vp, _vp, _vp, _vp, _i64, _i64], _i),

@@ -91,6 +91,35 @@ class PredictResult:
         self.S, self.stacked, self.chunks = None, None, None
 
 
+class PruneResult:
+    """FusedMLP.prune's outcome: the signal-to-noise pruning of mainviz.lua:20-27 at one threshold per VB layer, and the pruned
+    operand shadows (mu_p / var_p per layer, owned here) that predict() reads while this result is the engine's pruned view
+    (FusedMLP.use_pruned / pruned). Per layer (lists, VB layer order): tau (the threshold: key < tau is pruned; one value
+    repeated when scope = "global"), layers[li] = dict(n_pruned, W, fraction_pruned, mean_var, mean_pruned_var); the same five
+    names as attributes are the totals over all layers -- n_pruned and mean_pruned_var are what mainviz.lua:22-27 prints
+    (`pruned count`, `pruned var mean`; mean_pruned_var is nan when nothing was pruned, as the mean of an empty tensor).
+    mask(li): the layer's `pruned` tensor (mainviz.lua:21) as an O x I bool tensor, produced on request by one more pack
+    sweep of that layer. A result is a snapshot of the parameters it was taken from (version)."""
+
+    def __init__(self, engine, scope, tau, stats, mu_p, var_p, version):
+        self.engine, self.scope, self.version = engine, scope, version
+        self.tau = [float(t) for t in tau]
+        self.mu_p, self.var_p = mu_p, var_p
+        self.stats = [tuple(float(x) for x in st) for st in stats]         # per layer: pruned, sum pruned vars, sum vars, W
+        self.layers = [self._summary(*st) for st in self.stats]
+        tot = self._summary(*[sum(col) for col in zip(*self.stats)]) if self.stats else self._summary(0.0, 0.0, 0.0, 0.0)
+        self.n_pruned, self.W, self.fraction_pruned = tot["n_pruned"], tot["W"], tot["fraction_pruned"]
+        self.mean_var, self.mean_pruned_var = tot["mean_var"], tot["mean_pruned_var"]
+
+    @staticmethod
+    def _summary(n, s_pruned, s_all, W):
+        return dict(n_pruned=int(n), W=int(W), fraction_pruned=n / W if W else 0.0, mean_var=s_all / W if W else float("nan"),
+                    mean_pruned_var=s_pruned / n if n else float("nan"))
+
+    def mask(self, li):
+        return self.engine._prune_mask(self, li)
+
+
 class FusedMLP:
     def __init__(self, opt, device=None, world_size=1, rank=0, process_group=None, force_reduce=False, stream=None):
         """stream: a torch.cuda.Stream for this engine's launches (a library context of its own, hence its own reduction
@@ -302,12 +331,16 @@ class FusedMLP:
         self._x_in = None        # fp32: the raw minibatch of the current run, read in place by layer 1's GEMMs
         self._draws = None
         self._shadows_ready = False       # prepare() / update() have packed the operand shadows (predict prepares otherwise)
+        self._pruned = None               # the pruned view predict() reads its operands from (use_pruned), or None
+        self._pver = 0                    # parameter version: a pruned view is a snapshot of ONE version (prune / predict)
+        self._prune_ws = None
         self.init_parameters()
 
     # mlp.lua:47-55 (He rule for every weight, bias zero) + the bench's non-degenerate means
     # (means ~ N(0, sqrt(2/I)); the shipped mu_init = 0 gives an all-zero net).
     @_ordered
     def init_parameters(self):
+        self._pver += 1
         for v in self.vb:
             fill_normal(v.means, self.seed, L.STREAM_HEINIT, v.layer_id, 0, scale=math.sqrt(2.0 / v.I), ctx=self.ctx)
             v.bias.zero_()
@@ -435,6 +468,7 @@ class FusedMLP:
                     L.check(lib.vbnn_transpose_packed(self.ctx.h, self.code, v.mu_s.ptr, v.mu_s.ld, v.O, v.I, v.muT_s.ptr, v.muT_s.ld))
                     L.check(lib.vbnn_transpose_packed(self.ctx.h, self.code, v.var_s.ptr, v.var_s.ld, v.O, v.I, v.varT_s.ptr, v.varT_s.ld))
             return
+        self._pver += 1                                       # re-packed from the fp32 parameters: a caller may have changed them
         if self.mode == "lrt":                                # one call: a sweep per layer + ONE finish kernel
             descs = (L.PrepDesc * len(self.vb))()
             for k, v in enumerate(self.vb):
@@ -549,6 +583,13 @@ class FusedMLP:
         row0 = self.rank * R if row0 is None else int(row0)
         if not self._shadows_ready:            # a fresh engine: the shadows test() would have prepared
             self.prepare()
+        if self._pruned is not None:           # a pruned view replaces the operand shadows: it must be of THESE parameters
+            if self.mode == "wn" and not map:
+                raise ValueError("predict: weight-noise draws under a pruned view are not supported -- they sample from the fp32 "
+                                 "means / lvars, which the view does not replace (use map=True, or mode = 'lrt')")
+            if self._pruned.version != self._pver:
+                raise RuntimeError("predict: the pruned view was taken from older parameters (update / prepare / init_parameters "
+                                   "ran since): prune() again, or use_pruned(None)")
         lrt = self.mode == "lrt" and not map
         stacked = self._predict_stacked(R, S, lrt)
         cap = max(1, int(self.opt.get("predict_rows", 32768)))
@@ -666,13 +707,15 @@ class FusedMLP:
             L.check(lib.vbnn_pack_input(ctx, code, _p(x), x.stride(0), N, self.sizes[0], b0.x.ptr, b0.x2.ptr if b0.x2 else None,
                                         b0.x.ld, None, None, 0, rpd))
         nl = len(self.vb)
+        pv = self._pruned                      # a pruned view: ITS shadows in place of mu_s / var_s (or of WN's packed means)
         for li, v in enumerate(self.vb):
             xin, out = bufs[li], bufs[li + 1]
-            w = wts[li][1] if wts is not None else v.mu_s
+            w = pv.mu_p[li] if pv is not None else (wts[li][1] if wts is not None else v.mu_s)
+            w2 = pv.var_p[li] if pv is not None else v.var_s
             # r: nobody reads it. Only the sequential bf16 LRT forwards are handed a throwaway one -- the two-pass 256 x 256
             # kernel, which the large one-draw forwards take, stores r as part of its fold and is not selected without it.
             r = bufs.r if (lrt and rpd == 0 and bufs.r is not None) else None
-            a = L.FwdArgs(w=w.ptr, w2=v.var_s.ptr if lrt else None, x=xin.x.ptr, x2=xin.x2.ptr if (lrt and xin.x2) else None,
+            a = L.FwdArgs(w=w.ptr, w2=w2.ptr if lrt else None, x=xin.x.ptr, x2=xin.x2.ptr if (lrt and xin.x2) else None,
                           ld_w=w.ld, ld_x=xin.x.ld, N=N, I=v.I, O=v.O, bias=_p(v.bias), seed=self.seed, layer=v.layer_id,
                           draw=draw, draw_dev=None, row0=row0, y=None, ld_y=0, r=r.ptr if r else None, ld_r=r.ld if r else 0,
                           r_packed=1, relu=1,
@@ -1142,6 +1185,7 @@ class FusedMLP:
         operand shadows and the slices' prior statistics are all-gathered and every rank forms the layers' statistics from the
         same gathered parts (vbnn_stats_combine). Biases and the final Linear: all-reduced gradients, replicated SGD."""
         lib, h, W, R = L.lib(), self.ctx.h, self.world, self.rank
+        self._pver += 1
         ex = self.exchange()
         lr = float(opt["state"]["learningRate"])
         st = self.__dict__.setdefault("_opt_state", {})
@@ -1282,6 +1326,7 @@ class FusedMLP:
             assert not log, "the 14 logged series need whole-layer norms: not with the sharded update"
             return self._update_sharded(opt)
         lib, h = L.lib(), self.ctx.h
+        self._pver += 1
         lr = float(opt["state"]["learningRate"])
         st = self.__dict__.setdefault("_opt_state", {})
         if log and getattr(self, "update_log", None) is None:
@@ -1348,3 +1393,107 @@ class FusedMLP:
                                          _p(self._lc), v.O * v.I))
             lc += float(self._lc[0].item())
         return lc
+
+    # ---- signal-to-noise pruning (mainviz.lua:20-27) and the pruned view of predict(). Nothing of the training step is
+    # touched: the pruned operands are shadows of their own (PruneResult), read by predict() alone while the view is set.
+    def _prune_descs(self, mu_p, var_p, stats, lis, masks=None):
+        descs = (L.PruneDesc * len(lis))()
+        for j, li in enumerate(lis):
+            v = self.vb[li]
+            descs[j] = L.PruneDesc(means=_p(v.means), lvars=_p(v.lvars), O=v.O, I=v.I, mu_p=mu_p[li].ptr, var_p=var_p[li].ptr,
+                                   ld_w=mu_p[li].ld, stats=C.c_void_p(stats[li].data_ptr()),
+                                   mask=_p(masks[li]) if masks is not None else None)
+        return descs
+
+    @_ordered
+    def snr(self, li):
+        """|means / sqrt(exp(lvars))| of VB layer li (mainviz.lua:20) as an O x I fp32 tensor: the pruning key, bit for bit."""
+        self._need_gathered_parameters("snr")
+        v = self.vb[li]
+        out = torch.empty_like(v.means)
+        L.check(L.lib().vbnn_snr(self.ctx.h, _p(v.means), _p(v.lvars), v.O * v.I, _p(out)))
+        return out
+
+    @_ordered
+    def prune(self, fraction=None, threshold=None, scope="global"):
+        """Prune by signal-to-noise ratio: every weight with |mu| / sigma < tau (mainviz.lua:20-21). Exactly one of
+        threshold (tau itself; the reference uses 0.005) and fraction in [0, 1] (tau = the exact k-th smallest key,
+        k = floor(fraction W), so at most k weights go -- fewer when keys tie at tau; fraction = 1: tau = +inf, everything).
+        scope = "global": one tau over all VB layers; "layer": the fraction applies to each layer (one tau per layer).
+        Returns a PruneResult (synchronises to read tau and the counts); nothing changes for predict() until use_pruned."""
+        if (fraction is None) == (threshold is None):
+            raise ValueError("prune: exactly one of fraction and threshold")
+        if scope not in ("global", "layer"):
+            raise ValueError(f"prune: scope = {scope!r} ('global' or 'layer')")
+        if fraction is not None and not 0.0 <= float(fraction) <= 1.0:
+            raise ValueError(f"prune: fraction = {fraction} (0 .. 1)")
+        self._need_gathered_parameters("prune")
+        if not self._shadows_ready:            # (predict under the view reads the packed final weight)
+            self.prepare()
+        lib, ctx, dev, nl = L.lib(), self.ctx.h, self.device, len(self.vb)
+        mu_p = [_Packed(v.O, v.I, self.tdt, dev) for v in self.vb]
+        var_p = [_Packed(v.O, v.I, self.tdt, dev) for v in self.vb]
+        stats = torch.zeros(nl, 4, dtype=torch.float64, device=dev)
+        tau = torch.full((nl,), float(threshold) if threshold is not None else float("inf"), dtype=torch.float32, device=dev)
+        groups = [list(range(nl))] if scope == "global" else [[li] for li in range(nl)]
+        nbytes = C.c_size_t()
+        L.check(lib.vbnn_prune_workspace_bytes(nl, self._prune_descs(mu_p, var_p, stats, list(range(nl))), C.byref(nbytes)))
+        if self._prune_ws is None or self._prune_ws.numel() < nbytes.value:
+            self._prune_ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        for g in groups:
+            descs = self._prune_descs(mu_p, var_p, stats, g)
+            Wg = sum(self.vb[li].O * self.vb[li].I for li in g)
+            k = int(math.floor(float(fraction) * Wg)) if fraction is not None else Wg
+            tau_g = C.c_void_p(tau.data_ptr() + 4 * g[0]) if k < Wg else None       # on the device, behind the select
+            if tau_g is not None:
+                L.check(lib.vbnn_prune_select(ctx, len(g), descs, k, tau_g, _p(self._prune_ws), self._prune_ws.numel()))
+                if len(g) > 1:
+                    tau[g[0] + 1:g[-1] + 1] = tau[g[0]]
+            L.check(lib.vbnn_prune_pack(ctx, self.code, len(g), descs, tau_g,
+                                        float(threshold) if threshold is not None else float("inf")))
+        return PruneResult(self, scope, tau.cpu().tolist(), stats.cpu().tolist(), mu_p, var_p, self._pver)
+
+    @_ordered
+    def _prune_mask(self, res, li):
+        if res.engine is not self or res.version != self._pver:
+            raise RuntimeError("PruneResult.mask: the parameters changed since this result was taken")
+        self._need_gathered_parameters("mask")
+        v = self.vb[li]
+        masks = {li: torch.zeros(v.O, v.I, dtype=torch.uint8, device=self.device)}
+        stats = {li: torch.zeros(4, dtype=torch.float64, device=self.device)}
+        descs = self._prune_descs(res.mu_p, res.var_p, stats, [li], masks)          # the same sweep: the shadows get the same bits
+        L.check(L.lib().vbnn_prune_pack(self.ctx.h, self.code, 1, descs, None, res.tau[li]))
+        return masks[li].bool()
+
+    def use_pruned(self, result):
+        """predict() reads the pruned operands of `result` (a PruneResult of this engine) from now on; None: the unpruned
+        shadows again. Nothing else looks at the view: run / test / update / prepare and their operands are untouched."""
+        if result is not None and (not isinstance(result, PruneResult) or result.engine is not self):
+            raise ValueError("use_pruned: a PruneResult of this engine, or None")
+        self._pruned = result
+
+    @contextlib.contextmanager
+    def pruned(self, result):
+        """with eng.pruned(result): ... -- use_pruned(result) for the block, the previous view afterwards."""
+        prev = self._pruned
+        self.use_pruned(result)
+        try:
+            yield result
+        finally:
+            self._pruned = prev
+
+    def prune_curve(self, inputs, targets, fractions, S=None, map=False, scope="global"):
+        """What pruning costs: for every fraction q a prune(fraction=q, scope=scope) and a predict(inputs, S, targets, map)
+        under that view. One dict per fraction: fraction, tau (per layer), n_pruned, nll, accuracy, mean_draw_nll,
+        mean_draw_accuracy, mutual_info (mean over rows). The keys are re-formed by every select and pack sweep (nothing per
+        weight is kept between the points). Each point consumes S draws as a predict() call of its own would (none with
+        map=True), so the points see different noise; the engine's view is afterwards what it was before."""
+        rows = []
+        for q in fractions:
+            res = self.prune(fraction=q, scope=scope)
+            with self.pruned(res):
+                p = self.predict(inputs, S=S, targets=targets, map=map)
+            rows.append(dict(fraction=float(q), tau=res.tau, n_pruned=res.n_pruned, nll=p.nll, accuracy=p.accuracy,
+                             mean_draw_nll=p.mean_draw_nll, mean_draw_accuracy=p.mean_draw_accuracy,
+                             mutual_info=float(p.mutual_info.mean().item())))
+        return rows

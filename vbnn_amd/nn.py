@@ -579,6 +579,12 @@ class VBLinear(Linear):
                                      float(opt["B"]), _p(lc_elem), _p(self._lc), self.W))
         return (self._lc, lc_elem) if elementwise else self._lc
 
+    # -- mainviz.lua:20: the signal-to-noise ratio |means / sqrt(exp(lvars))| per weight (the pruning key), O x I fp32
+    def snr(self):
+        out = torch.empty_like(self.means)
+        L.check(L.lib().vbnn_snr(self.ctx.h, _p(self.means), _p(self.lvars), self.W, _p(out)))
+        return out
+
     # -- VBLinear.lua:124-166: SGD on bias, compute_prior, likelihood + KL gradients, optim.adam on means (meanState)
     # and lvars (varState). Returns (mu_normratio, var_normratio), the two ratios the reference logs (:139,144);
     # its other twelve Log:add statistics (:149-164) are host-side logging and are not reproduced.

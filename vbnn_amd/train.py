@@ -116,6 +116,28 @@ class Main:
         self.predictive = {k: v / len(starts) for k, v in pred.items()} if opt.get("predictive") else None
         return accuracy / len(starts), error / len(starts)
 
+    def _prune_series(self, testSet):
+        """opt.prune_report = T: the two numbers mainviz.lua:22-27 prints at threshold T (`pruned count`, `pruned var mean`), from
+        the device (FusedMLP.prune). opt.prune_eval = [fractions]: `devacc_pruned@<q>`, the accuracy of the MAP prediction over
+        the test set with the fraction q of the weights pruned globally (FusedMLP.prune_curve per test minibatch)."""
+        opt, net, rec = self.opt, self.net, {}
+        if opt.get("prune_report") is not None:
+            r = net.prune(threshold=float(opt["prune_report"]))
+            rec["pruned count"], rec["pruned var mean"] = r.n_pruned, r.mean_pruned_var
+        qs = list(opt.get("prune_eval") or [])
+        if qs:
+            bs, n = int(opt["testBatchSize"]), int(opt["testSize"])
+            starts = list(range(0, n - bs + 1, bs))
+            acc = [0.0] * len(qs)
+            for t0 in starts:
+                inputs, targets = testSet.create_minibatch(t0, bs, n, opt.get("geometry"))
+                x, t = self._to_device(inputs, targets)
+                for j, row in enumerate(net.prune_curve(x, t, qs, map=True)):
+                    acc[j] += row["accuracy"]
+            for q, a in zip(qs, acc):
+                rec[f"devacc_pruned@{q:g}"] = a / len(starts)
+        return rec
+
     def save(self):
         """The run directory's data files (mainviz.lua:11-15): every VB layer's means / vars flattened and
         concatenated in layer order -- the order of the reference's flat `parameters` vector (mlp.lua:37)."""
@@ -138,9 +160,13 @@ class Main:
                 self.net.gather_parameters()              # collective (every rank runs this loop): calc_lc and save read fp32 rows
             if self.opt.get("type", "vb") == "vb":
                 rec["lc"] = self.net.calc_lc(self.opt)
+            rec.update(self._prune_series(testSet))       # opt.prune_report / opt.prune_eval (both off by default)
             if self.log:
                 for k in ("devacc", "trainacc", "deverr", "trainerr", "lc", "devacc_pred", "devnll_pred", "dev_mi"):   # main.lua:169-177 (+ opt.predictive)
                     if k in rec:
+                        self.log.add(k, rec[k])
+                for k in rec:
+                    if k in ("pruned count", "pruned var mean") or k.startswith("devacc_pruned@"):
                         self.log.add(k, rec[k])
                 self.log.flush()
                 self.save()                                                                # main.lua:181
