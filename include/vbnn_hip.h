@@ -688,6 +688,59 @@ int vbnn_prune_select(vbnn_ctx* ctx, int n_layers, const vbnn_prune_desc* layers
  * runs give the same bits); and optionally the byte mask. No transposed shadows: the predictive path is forward-only. */
 int vbnn_prune_pack(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prune_desc* layers, const float* tau_dev, float tau_host);
 
+/* ---- compressed pruned weights and the forward that multiplies by them (additive, ABI 6) ------------------------------------
+ * The pruned shadows above are dense: a network with 90 % of its weights pruned still streams every +0. The compressed form of
+ * the same pruning keeps the KEPT weights only, per layer as CSR over output rows:
+ *   row_ptr  O + 1 uint32: row o's entries are [row_ptr[o], row_ptr[o + 1]); row_ptr[0] = 0, row_ptr[O] = nnz
+ *   cols     the entries' input units, ascending within a row; idx_bytes = 2 (uint16; I <= 65536 only) or 4 (uint32; any I)
+ *   mu_v, var_v  the entries' two values in the packed dtype
+ * An entry is a weight vbnn_prune_pack keeps -- !(key < tau) with the same key function and the same tau, so a NaN key is kept --
+ * and its values are the bits vbnn_prune_pack stores for it, T(mean) and T(expf(lvar)): scattering the entries over +0 gives
+ * mu_p / var_p bit for bit. A kept weight whose value is zero is still an entry: nnz = W - (number pruned), always. */
+typedef struct vbnn_sparse_desc {
+    uint32_t* row_ptr;                     /* O + 1 words */
+    void* cols;                            /* nnz_cap indices of idx_bytes each */
+    void* mu_v; void* var_v;               /* nnz_cap values of dtype each; var_v may be NULL (means only) */
+    int64_t O, I;
+    int64_t nnz_cap;                       /* entries the three arrays hold: nothing is written at or past it */
+    uint32_t* nnz_dev;                     /* optional device word: the nnz this compress produced (= row_ptr[O]) */
+    int32_t idx_bytes;                     /* 2 or 4; 2 with I > 65536 is VBNN_ERR_INVALID */
+    int32_t reserved;
+} vbnn_sparse_desc;
+/* Builds the compressed form of layers[l] (its means, lvars, O, I are read; nothing else of the prune desc) into sparse[l], at
+ * tau = tau_dev[0] read on the device (chained behind vbnn_prune_select like vbnn_prune_pack) or tau_host when tau_dev is NULL.
+ * Per layer a count sweep (one wave per output row), ONE scan kernel for all layers (exclusive sums into row_ptr, nnz_dev) and
+ * an ordered fill sweep (a wave walks its row in column order; an entry's place is its rank among the row's kept weights, from
+ * a wave ballot): no atomics, no order dependence, two runs give the same bytes. No host synchronisation: the capacity is known
+ * to a host that has read a vbnn_prune_pack's stats[0] for the same tau (nnz = W - pruned); with a smaller nnz_cap the entries
+ * past it are dropped (row_ptr and nnz_dev still tell the true count, so the host can check). n_layers <= 8. */
+int vbnn_prune_compress(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prune_desc* layers, const vbnn_sparse_desc* sparse,
+                        const float* tau_dev, float tau_host);
+
+/* One VB layer's updateOutput on compressed weights: m = x mu^T + b, v = (x.x)(sigma^2)^T, y = m + sqrt(v) . z -- the epilogue,
+ * the noise addressing ((seed, ZETA, layer, draw, row0 + n, o >> 2), stacked draws by rows_per_draw; bf16 draws in the hardware
+ * form, fp32 in the bit-exact form), ReLU and the packed outputs are vbnn_forward's own (one epilogue definition). var_v == NULL:
+ * the single-product MAP form y = x mu^T + b. The input is K-MAJOR: xT (I x ld_xT, ld_xT >= N), the transpose vbnn_pack_input
+ * (xT_s) and a forward's hT produce; x2T likewise, or NULL: the square is formed in registers as the packer stores it,
+ * T(x . x) of the rounded x. A wave owns one output unit and 64 operand rows (a lane each): it walks the row's entries in
+ * column order, each entry one coalesced read of xT[col][n .. n + 63], and adds in that order in fp32 -- bitwise reproducible.
+ * Any N >= 1, O, I; rows without entries and nnz = 0 are fine. */
+typedef struct vbnn_sparse_fwd_args {
+    const uint32_t* row_ptr; const void* cols; const void* mu_v; const void* var_v;   /* as vbnn_sparse_desc */
+    int64_t idx_bytes;
+    const void* xT; const void* x2T; int64_t ld_xT;
+    int64_t N, I, O;
+    const float* bias;  /* O, may be NULL */
+    uint64_t seed; uint32_t layer; uint32_t draw; int64_t row0;    /* LRT noise, as vbnn_fwd_args; ignored if var_v == NULL */
+    /* outputs, each optional; meanings as in vbnn_fwd_args */
+    float* y; int64_t ld_y;
+    int64_t relu;
+    void* h; void* h2; int64_t ld_h;       /* row-major N x ld_h (ld_h % 4 == 0): what the classifier head reads */
+    void* hT; void* h2T; int64_t ld_hT;    /* K-major O x ld_hT: what the next sparse layer reads */
+    int64_t rows_per_draw;
+} vbnn_sparse_fwd_args;
+int vbnn_forward_sparse(vbnn_ctx* ctx, int dtype, const vbnn_sparse_fwd_args* a);
+
 /* The same criterion as separate modules, for the module-level call order of mlp.lua:77-80:
  * nn.LogSoftMax:updateOutput is vbnn_logsoftmax_nll with g_logits = loss = correct = NULL. */
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,

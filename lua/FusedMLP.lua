@@ -23,7 +23,7 @@ FusedMLP.__index = FusedMLP
 local function f32(p) return ffi.cast('float*', p) end
 local function packed(rows, cols, esize)
     local ld = vb.pad_ld(cols)
-    return { p = vb.alloc(rows * ld * esize), ld = ld }
+    return { p = vb.alloc(rows * ld * esize), ld = ld, rows = rows }
 end
 
 -- opt: input_size, hidden = {..}, n_classes (<= 16: the fused classifier head), var_init, B, S, seed, dtype ('bf16')
@@ -511,6 +511,68 @@ function FusedMLP:use_pruned(result)
     self.pruned_view = result
 end
 
+-- The compressed form of a :prune result (engine.py:FusedMLP._compress, tools/c_host.c:fm_compress): the kept weights only, CSR per
+-- layer over output rows (include/vbnn_hip.h: vbnn_sparse_desc), built on the device at the result's own tau; the entry count is
+-- W - n_pruned, known from the result. Returns a result :use_pruned takes like any other; under it predict() multiplies by the
+-- entries directly (:_predict_forward_sparse). It owns no dense shadows.
+function FusedMLP:compress(result)
+    assert(result and result.owner == self, 'compress: a result of this :prune')
+    assert(result.version == (self.version or 0), 'compress: the parameters changed since this result was taken')
+    if result.sparse then return result end
+    local n = #self.vb
+    local o = { scope = result.scope, tau = result.tau, layers = result.layers, sparse = true, owner = self, version = result.version,
+                n_pruned = result.n_pruned, W = result.W, fraction_pruned = result.fraction_pruned, mean_var = result.mean_var,
+                mean_pruned_var = result.mean_pruned_var, row_ptr = {}, cols = {}, mu_v = {}, var_v = {}, nnz = {}, idx_bytes = {},
+                nbytes = 0, dense_nbytes = 0 }
+    local nnz_dev = vb.alloc(4 * n)
+    for li, v in ipairs(self.vb) do
+        local nnz = result.layers[li].W - result.layers[li].n_pruned
+        local ib, cap = (v.I <= 65536) and 2 or 4, math.max(nnz, 1)
+        o.nnz[li], o.idx_bytes[li] = nnz, ib
+        o.row_ptr[li], o.cols[li] = vb.alloc(4 * (v.O + 1)), vb.alloc(ib * cap)
+        o.mu_v[li], o.var_v[li] = vb.alloc(self.esize * cap), vb.alloc(self.esize * cap)
+        o.nbytes = o.nbytes + 4 * (v.O + 1) + (ib + 2 * self.esize) * cap
+        o.dense_nbytes = o.dense_nbytes + 2 * v.O * vb.pad_ld(v.I) * self.esize
+        local d, sd = ffi.new('vbnn_prune_desc[1]'), ffi.new('vbnn_sparse_desc[1]')
+        d[0].means, d[0].lvars, d[0].O, d[0].I = f32(v.means), f32(v.lvars), v.O, v.I
+        sd[0].row_ptr, sd[0].cols, sd[0].mu_v, sd[0].var_v = ffi.cast('uint32_t*', o.row_ptr[li]), o.cols[li], o.mu_v[li], o.var_v[li]
+        sd[0].O, sd[0].I, sd[0].nnz_cap, sd[0].idx_bytes = v.O, v.I, nnz, ib
+        sd[0].nnz_dev = ffi.cast('uint32_t*', nnz_dev) + (li - 1)
+        check(C.vbnn_prune_compress(vb.ctx, self.dtype, 1, d, sd, nil, result.tau[li]))
+    end
+    local got = ffi.new('uint32_t[?]', n)
+    check(C.vbnn_buf_download(vb.ctx, got, nnz_dev, 4 * n))
+    for li = 1, n do assert(got[li - 1] == o.nnz[li], 'compress: the device kept another number of weights than the pruning counted') end
+    return o
+end
+
+-- predict's forwards under a compressed view: the input packed with its transpose, then every VB layer on its entries -- K-major
+-- activations from layer to layer (xT[li]: layer li's input), the last layer writes the row-major h the head reads
+function FusedMLP:_predict_forward_sparse(in_x, x, ld, N, rpd, draw, row0, pack)
+    local pv = self.pruned_view
+    if not pv.xT or pv.xT_rows ~= in_x[1].rows then
+        pv.xT, pv.xT_rows = {}, in_x[1].rows
+        for li = 1, #self.vb do pv.xT[li] = packed(self.sizes[li], in_x[1].rows, self.esize) end
+    end
+    if pack then
+        check(C.vbnn_pack_input(vb.ctx, self.dtype, x, ld, N, self.sizes[1], in_x[1].p, nil, in_x[1].ld, pv.xT[1].p, nil, pv.xT[1].ld, rpd))
+    end
+    for li, v in ipairs(self.vb) do
+        local sa = ffi.new('vbnn_sparse_fwd_args')
+        sa.row_ptr, sa.cols, sa.mu_v, sa.var_v = ffi.cast('const uint32_t*', pv.row_ptr[li]), pv.cols[li], pv.mu_v[li], pv.var_v[li]
+        sa.idx_bytes, sa.xT, sa.x2T, sa.ld_xT = pv.idx_bytes[li], pv.xT[li].p, nil, pv.xT[li].ld
+        sa.N, sa.I, sa.O, sa.bias = N, v.I, v.O, f32(v.bias)
+        sa.seed, sa.layer, sa.draw, sa.row0 = self.seed, v.layer_id, draw, row0
+        sa.relu, sa.rows_per_draw = 1, rpd
+        if li == #self.vb then
+            sa.h, sa.ld_h = in_x[li + 1].p, in_x[li + 1].ld
+        else
+            sa.hT, sa.ld_hT = pv.xT[li + 1].p, pv.xT[li + 1].ld
+        end
+        check(C.vbnn_forward_sparse(vb.ctx, self.dtype, sa))
+    end
+end
+
 -- the posterior predictive (engine.py:FusedMLP.predict, tools/c_host.c:fm_predict): mlp:test's S draws averaged as probabilities
 -- (mlp.lua:86-107, main.lua:55-74, visualize.lua:66-100), forward-only on buffers of its own (in_x[li]: layer li's input,
 -- in_x[#vb + 1] the head's; r: a throwaway noise factor for the one-draw bf16 forwards). Consumes draws draw + 1 .. draw + S, as
@@ -590,6 +652,9 @@ end
 
 -- predict's forwards: the input packed (stacked draws: rows_per_draw), then every VB layer; r only for one-draw forwards
 function FusedMLP:_predict_forward(in_x, in_x2, r, x, ld, N, rpd, draw, row0, pack)
+    if self.pruned_view and self.pruned_view.sparse then           -- the compressed view: its own forward (above :predict)
+        return self:_predict_forward_sparse(in_x, x, ld, N, rpd, draw, row0, pack)
+    end
     if pack then
         check(C.vbnn_pack_input(vb.ctx, self.dtype, x, ld, N, self.sizes[1], in_x[1].p, in_x2[1] and in_x2[1].p or nil, in_x[1].ld,
                                 nil, nil, 0, rpd))

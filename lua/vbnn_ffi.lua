@@ -259,6 +259,32 @@ int vbnn_prune_workspace_bytes(int n_layers, const vbnn_prune_desc* layers, size
 int vbnn_prune_select(vbnn_ctx* ctx, int n_layers, const vbnn_prune_desc* layers, int64_t k, float* tau_dev,
                       void* workspace, size_t workspace_bytes);
 int vbnn_prune_pack(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prune_desc* layers, const float* tau_dev, float tau_host);
+typedef struct vbnn_sparse_desc {
+    uint32_t* row_ptr;
+    void* cols;
+    void* mu_v; void* var_v;
+    int64_t O, I;
+    int64_t nnz_cap;
+    uint32_t* nnz_dev;
+    int32_t idx_bytes;
+    int32_t reserved;
+} vbnn_sparse_desc;
+int vbnn_prune_compress(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prune_desc* layers, const vbnn_sparse_desc* sparse,
+                        const float* tau_dev, float tau_host);
+typedef struct vbnn_sparse_fwd_args {
+    const uint32_t* row_ptr; const void* cols; const void* mu_v; const void* var_v;
+    int64_t idx_bytes;
+    const void* xT; const void* x2T; int64_t ld_xT;
+    int64_t N, I, O;
+    const float* bias;
+    uint64_t seed; uint32_t layer; uint32_t draw; int64_t row0;
+    float* y; int64_t ld_y;
+    int64_t relu;
+    void* h; void* h2; int64_t ld_h;
+    void* hT; void* h2T; int64_t ld_hT;
+    int64_t rows_per_draw;
+} vbnn_sparse_fwd_args;
+int vbnn_forward_sparse(vbnn_ctx* ctx, int dtype, const vbnn_sparse_fwd_args* a);
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,
                      float inv_n, double* loss_sum_dev, int32_t* correct_dev);
 int vbnn_nll_backward(vbnn_ctx* ctx, const int32_t* target, int64_t N, int64_t C, float inv_n, float* g);

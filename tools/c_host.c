@@ -14,13 +14,15 @@
  *
  *   c_host --dtype f32|bf16 --input 784 --hidden 400,400 --classes 10 --batch 256 [--S 1] [--steps 2] [--update]
  *          [--comm [--sharded]] [--graph] [--kl-shadows] [--seed 3] --out arena.bin
- *          [--predict S [--predict-rows 32768] [--predict-stacked -1|0|1] [--prune Q | --prune-threshold T]]
+ *          [--predict S [--predict-rows 32768] [--predict-stacked -1|0|1] [--prune Q | --prune-threshold T [--sparse]]]
  *   --predict S: after the steps, the posterior predictive of the minibatch over S draws (fm_predict), appended to the file:
  *   int64 R, int64 C, int32 S, stacked, chunks, draw counter after it; probs and log_probs (R x C floats); entropy,
  *   expected_entropy, mutual_info (R floats each); pred (R int32); the four totals (doubles). Without it the file is as above.
  *   --prune Q | --prune-threshold T (with --predict S): then the signal-to-noise pruning (fm_prune: the fraction Q of all VB weights, or
  *   every weight below T) and the predictive once more under the pruned view, appended: int32 layers, float tau, per layer four
  *   doubles (pruned, sum of pruned variances, sum of variances, W), then a second predict block as above (S more draws).
+ *   --sparse (with --prune / --prune-threshold): that second predict runs under the COMPRESSED view of the same pruning (fm_compress,
+ *   fm_predict_forward_sparse: vbnn_prune_compress, vbnn_forward_sparse); the file layout is unchanged.
  *   --graph: the context gets a stream of its own (vbnn_ctx_create_cu_budget), the draw counter lives on the device
  *   (vbnn_fwd_args.draw_dev, vbnn_sample), step 2 is CAPTURED (vbnn_capture_begin / _end) and steps 2.. are replays of it.
  *   arena.bin: int64 n_grads, double loss, int32 correct, int32 flags, then n_grads floats (the arena after the last
@@ -110,6 +112,8 @@ typedef struct {
     int64_t N;
     vbnn_comm* comm;
     const packed_t *view_mu, *view_var;   /* the pruned view (fm_prune): per layer, read by fm_predict_forward in place of mu_s / var_s; NULL: none */
+    struct sparse_out* sparse;            /* the compressed pruned view (fm_compress): fm_predict_forward then runs fm_predict_forward_sparse; NULL: none */
+    int64_t pred_rows;                    /* operand rows of fm_predict's buffers (the K-major buffers of the sparse forward match them) */
 } fused_mlp;
 
 /* ---- FusedMLP.new (lua/FusedMLP.lua; engine.py:FusedMLP.__init__ + init_parameters) */
@@ -560,6 +564,72 @@ static void fm_use_pruned(fused_mlp* m, const prune_out* o) {
     m->view_mu = o ? o->mu_p : NULL; m->view_var = o ? o->var_p : NULL;
 }
 
+/* ---- the compressed pruned view (engine.py:FusedMLP._compress / _predict_forward_sparse, lua/FusedMLP.lua:compress): the kept
+   weights of a pruning as CSR per layer (vbnn_prune_compress at the pruning's own tau; the entry count is W - pruned, known from
+   its statistics) and predict's forward on them: K-major activations from layer to layer, the last layer writes the row-major h
+   the head reads. */
+typedef struct sparse_out {
+    uint32_t* row_ptr[MAX_LAYERS]; void* cols[MAX_LAYERS]; void* mu_v[MAX_LAYERS]; void* var_v[MAX_LAYERS];
+    int64_t nnz[MAX_LAYERS]; int idx_bytes[MAX_LAYERS];
+    packed_t xT[MAX_LAYERS];              /* xT[li]: layer li's K-major input, sizes[li] x pad64(rows) */
+    int64_t rows;
+} sparse_out;
+
+static void fm_compress(fused_mlp* m, const prune_out* p, sparse_out* s) {
+    const int n = m->n_layers;
+    uint32_t* nnz_dev = (uint32_t*)dev_alloc((size_t)n * 4);
+    uint32_t got[MAX_LAYERS];
+    memset(s, 0, sizeof *s);
+    for (int li = 0; li < n; ++li) {
+        layer_t* v = &m->vb[li];
+        vbnn_prune_desc d;
+        vbnn_sparse_desc sd;
+        memset(&d, 0, sizeof d); memset(&sd, 0, sizeof sd);
+        s->nnz[li] = (int64_t)(p->stats[li][3] - p->stats[li][0]);           /* W - pruned, as vbnn_prune_pack counted them */
+        s->idx_bytes[li] = v->I <= 65536 ? 2 : 4;
+        const size_t cap = (size_t)(s->nnz[li] > 0 ? s->nnz[li] : 1);
+        s->row_ptr[li] = (uint32_t*)dev_alloc((size_t)(v->O + 1) * 4);
+        s->cols[li] = dev_alloc(cap * (size_t)s->idx_bytes[li]);
+        s->mu_v[li] = dev_alloc(cap * (size_t)m->esize); s->var_v[li] = dev_alloc(cap * (size_t)m->esize);
+        d.means = v->means; d.lvars = v->lvars; d.O = v->O; d.I = v->I;
+        sd.row_ptr = s->row_ptr[li]; sd.cols = s->cols[li]; sd.mu_v = s->mu_v[li]; sd.var_v = s->var_v[li];
+        sd.O = v->O; sd.I = v->I; sd.nnz_cap = s->nnz[li]; sd.nnz_dev = nnz_dev + li; sd.idx_bytes = s->idx_bytes[li];
+        CHECK(vbnn_prune_compress(g_ctx, m->dtype, 1, &d, &sd, NULL, p->tau));
+    }
+    CHECK(vbnn_buf_download(g_ctx, got, nnz_dev, (size_t)n * 4));
+    for (int li = 0; li < n; ++li)
+        if ((int64_t)got[li] != s->nnz[li]) {
+            fprintf(stderr, "c_host: compress kept %u weights of layer %d, the pruning's statistics say %lld\n", got[li], li, (long long)s->nnz[li]);
+            exit(1);
+        }
+}
+static void fm_use_sparse(fused_mlp* m, sparse_out* s) { m->sparse = s; }
+
+static void fm_predict_forward_sparse(fused_mlp* m, const packed_t* in_x, const float* x, int64_t ld, int64_t N, int64_t rpd, uint32_t draw,
+                                      int64_t row0, int pack) {
+    sparse_out* s = m->sparse;
+    if (s->rows != m->pred_rows) {
+        for (int li = 0; li < m->n_layers; ++li) s->xT[li] = packed(m->sizes[li], m->pred_rows, m->esize);
+        s->rows = m->pred_rows;
+    }
+    if (pack)
+        CHECK(vbnn_pack_input(g_ctx, m->dtype, x, ld, N, m->sizes[0], in_x[0].p, NULL, in_x[0].ld, s->xT[0].p, NULL, s->xT[0].ld, rpd));
+    for (int li = 0; li < m->n_layers; ++li) {
+        layer_t* v = &m->vb[li];
+        const int last = li + 1 == m->n_layers;
+        vbnn_sparse_fwd_args a;
+        memset(&a, 0, sizeof a);
+        a.row_ptr = s->row_ptr[li]; a.cols = s->cols[li]; a.mu_v = s->mu_v[li]; a.var_v = s->var_v[li]; a.idx_bytes = s->idx_bytes[li];
+        a.xT = s->xT[li].p; a.x2T = NULL; a.ld_xT = s->xT[li].ld;
+        a.N = N; a.I = v->I; a.O = v->O; a.bias = v->bias;
+        a.seed = m->seed; a.layer = v->layer_id; a.draw = draw; a.row0 = row0; a.relu = 1;
+        if (last) { a.h = in_x[li + 1].p; a.ld_h = in_x[li + 1].ld; }
+        else { a.hT = s->xT[li + 1].p; a.ld_hT = s->xT[li + 1].ld; }
+        a.rows_per_draw = rpd;
+        CHECK(vbnn_forward_sparse(g_ctx, m->dtype, &a));
+    }
+}
+
 /* ---- the posterior predictive (engine.py:FusedMLP.predict, lua/FusedMLP.lua:predict): mlp:test's S draws averaged as
    probabilities (mlp.lua:86-107, main.lua:55-74, visualize.lua:66-100). Forward-only, on buffers of its own: in_x[li] is layer
    li's input (in_x[n_layers] the head's), r a throwaway noise factor for the one-draw bf16 forwards (the two-pass kernel stores it). */
@@ -572,6 +642,7 @@ typedef struct {
 
 static void fm_predict_forward(fused_mlp* m, const packed_t* in_x, const packed_t* in_x2, const packed_t* r, const float* x, int64_t ld,
                                int64_t N, int64_t rpd, uint32_t draw, int64_t row0, int pack) {
+    if (m->sparse) { fm_predict_forward_sparse(m, in_x, x, ld, N, rpd, draw, row0, pack); return; }     /* the compressed view */
     if (pack)
         CHECK(vbnn_pack_input(g_ctx, m->dtype, x, ld, N, m->sizes[0], in_x[0].p, in_x2[0].p, in_x[0].ld, NULL, NULL, 0, rpd));
     for (int li = 0; li < m->n_layers; ++li) {
@@ -604,6 +675,7 @@ static void fm_predict(fused_mlp* m, const float* x, int64_t ld, const int32_t* 
     if (Rc > R) Rc = R;
     if (Rc < 1) Rc = 1;
     const int64_t rows = stacked ? S * Rc : Rc;                    /* operand rows of one forward */
+    m->pred_rows = rows;
     const int sq = m->dtype == VBNN_BF16;                          /* (fp32: the forward forms x.x from x itself) */
     packed_t in_x[MAX_LAYERS + 1], in_x2[MAX_LAYERS + 1], r;
     memset(in_x2, 0, sizeof in_x2);
@@ -761,12 +833,20 @@ int main(int argc, char** argv) {
     const char* prune_t = arg_value(argc, argv, "--prune-threshold", NULL);
     const int prune_passes = (predict_S > 0 && (prune_q || prune_t)) ? 2 : 1;
     prune_out pr;
+    static sparse_out sp;
     for (int pass = 0; pass < prune_passes && predict_S > 0; ++pass) {
         /* --predict S: the posterior predictive of the minibatch after the steps, appended to the file; with --prune Q /
            --prune-threshold T once more under the pruned view, behind the numbers of the pruning */
         if (pass == 1) {
             fm_prune(&net, prune_q ? atof(prune_q) : -1.0, prune_t ? (float)atof(prune_t) : 0.f, &pr);
             fm_use_pruned(&net, &pr);
+            if (arg_flag(argc, argv, "--sparse")) {               /* the same pruning, compressed: predict multiplies by the entries */
+                fm_compress(&net, &pr, &sp);
+                fm_use_sparse(&net, &sp);
+                int64_t nnz = 0;
+                for (int li = 0; li < n_layers; ++li) nnz += sp.nnz[li];
+                printf("c_host: compressed view, %lld entries\n", (long long)nnz);
+            }
             const int32_t nl = n_layers;
             fwrite(&nl, 4, 1, f); fwrite(&pr.tau, 4, 1, f); fwrite(pr.stats, 8, (size_t)4 * n_layers, f);
             double np = 0, W = 0;
@@ -792,6 +872,7 @@ int main(int argc, char** argv) {
                po.stacked ? "stacked" : "sequential", po.chunks, po.totals[0] / (double)po.R, 100.0 * po.totals[1] / (double)po.R);
     }
     fm_use_pruned(&net, NULL);
+    fm_use_sparse(&net, NULL);
     fclose(f);
     free(arena);
     printf("c_host: %s %lld", dtype == VBNN_F32 ? "f32" : "bf16", (long long)sizes[0]);

@@ -103,6 +103,18 @@ class PruneDesc(C.Structure):         # vbnn_prune_desc
                 ("stats", _vp), ("mask", _vp)]
 
 
+class SparseDesc(C.Structure):        # vbnn_sparse_desc
+    _fields_ = [("row_ptr", _vp), ("cols", _vp), ("mu_v", _vp), ("var_v", _vp), ("O", _i64), ("I", _i64), ("nnz_cap", _i64),
+                ("nnz_dev", _vp), ("idx_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SparseFwdArgs(C.Structure):     # vbnn_sparse_fwd_args
+    _fields_ = [("row_ptr", _vp), ("cols", _vp), ("mu_v", _vp), ("var_v", _vp), ("idx_bytes", _i64),
+                ("xT", _vp), ("x2T", _vp), ("ld_xT", _i64), ("N", _i64), ("I", _i64), ("O", _i64), ("bias", _vp),
+                ("seed", _u64), ("layer", _u32), ("draw", _u32), ("row0", _i64), ("y", _vp), ("ld_y", _i64), ("relu", _i64),
+                ("h", _vp), ("h2", _vp), ("ld_h", _i64), ("hT", _vp), ("h2T", _vp), ("ld_hT", _i64), ("rows_per_draw", _i64)]
+
+
 _SIGS = {
     "vbnn_abi_version": ([], _i),
     "vbnn_last_error": ([], C.c_char_p),
@@ -190,6 +202,8 @@ _SIGS = {
     "vbnn_prune_workspace_bytes": ([_i, _vp, C.POINTER(C.c_size_t)], _i),
     "vbnn_prune_select": ([_vp, _i, _vp, _i64, _vp, _vp, C.c_size_t], _i),
     "vbnn_prune_pack": ([_vp, _i, _i, _vp, _vp, _f], _i),
+    "vbnn_prune_compress": ([_vp, _i, _i, _vp, _vp, _vp, _f], _i),
+    "vbnn_forward_sparse": ([_vp, _i, C.POINTER(SparseFwdArgs)], _i),
     "vbnn_nll_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _f, _vp, _vp], _i),
     "vbnn_nll_backward": ([_vp, _vp, _i64, _i64, _f, _vp], _i),
     "vbnn_logsoftmax_backward": ([_vp, _vp, _vp, _vp, _i64, _i64], _i),

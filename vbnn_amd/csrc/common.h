@@ -34,6 +34,15 @@ __device__ __forceinline__ vbnn_f32x4 vbnn_normal4_hw(uint64_t seed, uint32_t st
 }
 #endif
 
+// THE pruning key (mainviz.lua:20: torch.abs(torch.cdiv(means, torch.sqrt(vars))), vars = exp(lvars) as k_prep_layer forms var_s),
+// op for op in fp32. One definition for prune.hip and sparse.hip (both compiled without fp contraction): every kernel that
+// decides kept / pruned must give one weight the same bits.
+#if defined(__HIPCC__)
+__device__ __forceinline__ float vbnn_snr_key(float mean, float lvar) {
+    return fabsf(__fdiv_rn(mean, __fsqrt_rn(expf(lvar))));
+}
+#endif
+
 // A loop the compiler MUST unroll: `#pragma unroll` is silently dropped when the unrolled body exceeds LLVM's
 // pragma-unroll-threshold (16 K instructions), and a rolled loop indexing a register array sends the WHOLE array to
 // scratch (seen: gemm_nt_v2<.., EpiDw>'s generic epilogue, 528 B of scratch and 64 stores on every path).

@@ -9,11 +9,7 @@
 // workspace is three histograms and two words of state.
 #include "common.h"
 
-// THE key (mainviz.lua:20: torch.abs(torch.cdiv(means, torch.sqrt(vars))), vars = exp(lvars) as k_prep_layer forms var_s),
-// op for op in fp32. One definition: the three kernels below must give one weight the same bits.
-__device__ __forceinline__ float vbnn_snr_key(float mean, float lvar) {
-    return fabsf(__fdiv_rn(mean, __fsqrt_rn(expf(lvar))));
-}
+// THE key: vbnn_snr_key (common.h), one definition -- the kernels below and sparse.hip's must give one weight the same bits.
 
 static inline int prune_grid(int64_t W) {
     int64_t b = (W + 4095) / 4096;             // >= 16 weights per thread before a second block is worth its histogram flush

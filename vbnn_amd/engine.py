@@ -119,6 +119,55 @@ class PruneResult:
     def mask(self, li):
         return self.engine._prune_mask(self, li)
 
+    def compress(self):
+        """The same pruning in compressed form (a SparsePruneResult: the kept weights only, CSR per layer): under that view
+        predict() multiplies by the entries directly (vbnn_forward_sparse). Synchronises to check the entry counts."""
+        return self.engine._compress(self)
+
+
+class SparsePruneResult(PruneResult):
+    """PruneResult.compress()'s outcome: a PruneResult (use_pruned / pruned take it unchanged; tau, layers, totals and the
+    version guard are the dense result's) whose weights are per-layer CSR over output rows instead of dense shadows -- lists in
+    VB layer order: row_ptr[li] (O + 1 offsets, int32 storage of the library's uint32), cols[li] (ascending within a row;
+    int16 storage of uint16 when idx_bytes[li] == 2, int32 otherwise), mu_v[li] / var_v[li] (the packed dtype), nnz[li]
+    (= W - n_pruned: a kept weight that is zero is still an entry). nbytes / dense_nbytes: device bytes of this form and of
+    the dense shadows it replaces. It owns no dense shadows (mu_p / var_p are None): dropping the dense result frees them.
+    to_dense(li) rebuilds them (for checking), mask(li) the layer's `pruned` tensor."""
+
+    def __init__(self, base, row_ptr, cols, mu_v, var_v, nnz, idx_bytes, dense_nbytes):
+        super().__init__(base.engine, base.scope, base.tau, base.stats, None, None, base.version)
+        self.row_ptr, self.cols, self.mu_v, self.var_v = row_ptr, cols, mu_v, var_v
+        self.nnz, self.idx_bytes = [int(n) for n in nnz], list(idx_bytes)
+        self.nbytes = sum(t[li].numel() * t[li].element_size() for t in (row_ptr, cols, mu_v, var_v) for li in range(len(nnz)))
+        self.dense_nbytes = int(dense_nbytes)
+
+    def _coords(self, li):
+        rp = self.row_ptr[li].to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(rp.numel() - 1, device=rp.device), rp[1:] - rp[:-1])
+        mask = 0xffff if self.idx_bytes[li] == 2 else 0xffffffff
+        return rows, self.cols[li][:self.nnz[li]].to(torch.int64) & mask
+
+    def to_dense(self, li):
+        """(mu_p, var_p) of layer li as vbnn_prune_pack writes them: O x ld_w of the packed dtype, +0 wherever no entry is."""
+        v = self.engine.vb[li]
+        rows, cols = self._coords(li)
+        out = []
+        for vals in (self.mu_v[li], self.var_v[li]):
+            d = torch.zeros(v.O, L.pad_ld(v.I), dtype=vals.dtype, device=vals.device)
+            d[rows, cols] = vals[:self.nnz[li]]
+            out.append(d)
+        return tuple(out)
+
+    def mask(self, li):
+        v = self.engine.vb[li]
+        m = torch.ones(v.O, v.I, dtype=torch.bool, device=self.row_ptr[li].device)
+        rows, cols = self._coords(li)
+        m[rows, cols] = False
+        return m
+
+    def compress(self):
+        return self
+
 
 class FusedMLP:
     def __init__(self, opt, device=None, world_size=1, rank=0, process_group=None, force_reduce=False, stream=None):
@@ -701,6 +750,8 @@ class FusedMLP:
 
     def _predict_forward(self, bufs, wts, x, N, rpd, draw, row0, lrt, pack=True):
         """vbnn_pack_input + every VB layer's forward for predict: N operand rows (rpd > 0: stacked draws of rpd rows each)."""
+        if isinstance(self._pruned, SparsePruneResult):        # the compressed view: its own forward (below prune_curve)
+            return self._predict_forward_sparse(bufs, x, N, rpd, draw, row0, lrt, pack)
         lib, ctx, code = L.lib(), self.ctx.h, self.code
         if pack:
             b0 = bufs[0]
@@ -1497,3 +1548,82 @@ class FusedMLP:
                              mean_draw_nll=p.mean_draw_nll, mean_draw_accuracy=p.mean_draw_accuracy,
                              mutual_info=float(p.mutual_info.mean().item())))
         return rows
+
+    def prune_curve_sparse(self, inputs, targets, fractions, S=None, map=False, scope="global"):
+        """prune_curve with every point evaluated through the compressed form (prune(...).compress() as the view)."""
+        rows = []
+        for q in fractions:
+            res = self.prune(fraction=q, scope=scope).compress()
+            with self.pruned(res):
+                p = self.predict(inputs, S=S, targets=targets, map=map)
+            rows.append(dict(fraction=float(q), tau=res.tau, n_pruned=res.n_pruned, nnz=sum(res.nnz), nbytes=res.nbytes,
+                             dense_nbytes=res.dense_nbytes, nll=p.nll, accuracy=p.accuracy, mean_draw_nll=p.mean_draw_nll,
+                             mean_draw_accuracy=p.mean_draw_accuracy, mutual_info=float(p.mutual_info.mean().item())))
+        return rows
+
+    # ---- the compressed pruned view (csrc/sparse.hip). compress: a PruneResult's kept weights as CSR, built on the device at
+    # the result's own tau (the entry count is known from its statistics: no extra synchronisation before the allocation).
+    # _predict_forward_sparse: predict's forward under such a view -- K-major activations from layer to layer (xT from the
+    # input packer, hT from every layer but the last, which writes the row-major h the head reads), squares formed in registers.
+    @_ordered
+    def _compress(self, res):
+        if not isinstance(res, PruneResult) or res.engine is not self:
+            raise ValueError("compress: a PruneResult of this engine")
+        if res.version != self._pver:
+            raise RuntimeError("compress: the parameters changed since this result was taken (prune() again)")
+        if isinstance(res, SparsePruneResult):
+            return res
+        self._need_gathered_parameters("compress")
+        lib, ctx, dev, nl = L.lib(), self.ctx.h, self.device, len(self.vb)
+        nnz = [int(st[3]) - int(st[0]) for st in res.stats]                       # W - pruned, as vbnn_prune_pack counted them
+        idx = [2 if v.I <= 65536 else 4 for v in self.vb]
+        row_ptr = [torch.zeros(v.O + 1, dtype=torch.int32, device=dev) for v in self.vb]
+        cols = [torch.zeros(max(n, 1), dtype=torch.int16 if ib == 2 else torch.int32, device=dev) for n, ib in zip(nnz, idx)]
+        mu_v = [torch.zeros(max(n, 1), dtype=self.tdt, device=dev) for n in nnz]
+        var_v = [torch.zeros(max(n, 1), dtype=self.tdt, device=dev) for n in nnz]
+        nnz_dev = torch.zeros(nl, dtype=torch.int32, device=dev)
+        for li, v in enumerate(self.vb):
+            pd = (L.PruneDesc * 1)(L.PruneDesc(means=_p(v.means), lvars=_p(v.lvars), O=v.O, I=v.I))
+            sd = (L.SparseDesc * 1)(L.SparseDesc(row_ptr=_p(row_ptr[li]), cols=_p(cols[li]), mu_v=_p(mu_v[li]), var_v=_p(var_v[li]),
+                                                 O=v.O, I=v.I, nnz_cap=nnz[li], nnz_dev=C.c_void_p(nnz_dev.data_ptr() + 4 * li),
+                                                 idx_bytes=idx[li]))
+            L.check(lib.vbnn_prune_compress(ctx, self.code, 1, pd, sd, None, res.tau[li]))
+        got = [n & 0xffffffff for n in nnz_dev.cpu().tolist()]
+        if got != nnz:
+            raise RuntimeError(f"compress: the device kept {got} weights per layer, the pruning's statistics say {nnz}")
+        esz = torch.empty(0, dtype=self.tdt).element_size()
+        dense = sum(2 * v.O * L.pad_ld(v.I) * esz for v in self.vb)
+        return SparsePruneResult(res, row_ptr, cols, mu_v, var_v, nnz, idx, dense)
+
+    def _sparse_buffers(self, rows):
+        """K-major operands of the sparse forward: T[0] the packed input's transpose, T[li + 1] layer li's hT (ping-pong per
+        hidden width, as _predict_buffers). Kept across calls while the row count holds."""
+        if getattr(self, "_sparse_key", None) != rows:
+            slots = {}
+            T = [_Packed(self.sizes[0], rows, self.tdt, self.device)]
+            for li, v in enumerate(self.vb[:-1]):
+                if (v.O, li % 2) not in slots:
+                    slots[(v.O, li % 2)] = _Packed(v.O, rows, self.tdt, self.device)
+                T.append(slots[(v.O, li % 2)])
+            self._sparse_bufs, self._sparse_key = T, rows
+        return self._sparse_bufs
+
+    def _predict_forward_sparse(self, bufs, x, N, rpd, draw, row0, lrt, pack=True):
+        """_predict_forward under a compressed view: vbnn_pack_input (with the transposed copy) + vbnn_forward_sparse per layer."""
+        lib, ctx, code = L.lib(), self.ctx.h, self.code
+        pv, nl = self._pruned, len(self.vb)
+        T = self._sparse_buffers(bufs[0].x.t.shape[0])
+        if pack:                               # (the packer always writes the row-major copy too; no sparse layer reads it)
+            b0 = bufs[0]
+            L.check(lib.vbnn_pack_input(ctx, code, _p(x), x.stride(0), N, self.sizes[0], b0.x.ptr, None, b0.x.ld, T[0].ptr, None,
+                                        T[0].ld, rpd))
+        for li, v in enumerate(self.vb):
+            last = li == nl - 1
+            out = bufs[li + 1]
+            a = L.SparseFwdArgs(row_ptr=_p(pv.row_ptr[li]), cols=_p(pv.cols[li]), mu_v=_p(pv.mu_v[li]),
+                                var_v=_p(pv.var_v[li]) if lrt else None, idx_bytes=pv.idx_bytes[li], xT=T[li].ptr, x2T=None,
+                                ld_xT=T[li].ld, N=N, I=v.I, O=v.O, bias=_p(v.bias), seed=self.seed, layer=v.layer_id, draw=draw,
+                                row0=row0, y=None, ld_y=0, relu=1, h=out.x.ptr if last else None, h2=None,
+                                ld_h=out.x.ld if last else 0, hT=None if last else T[li + 1].ptr, h2T=None,
+                                ld_hT=0 if last else T[li + 1].ld, rows_per_draw=rpd)
+            L.check(lib.vbnn_forward_sparse(ctx, code, C.byref(a)))
