@@ -741,6 +741,51 @@ typedef struct vbnn_sparse_fwd_args {
 } vbnn_sparse_fwd_args;
 int vbnn_forward_sparse(vbnn_ctx* ctx, int dtype, const vbnn_sparse_fwd_args* a);
 
+/* ---- structured pruning: whole hidden units by signal-to-noise, and the compact network that is left (additive, ABI 6) ------
+ * The group form of mainviz.lua:20-27. Unstructured pruning (above) leaves a network of the same shape; a hidden unit whose
+ * incoming weights are all noise can go as a whole, and what remains is a smaller DENSE network for the ordinary kernels.
+ * The key of output unit o of a VB layer is ||means[o, :]||_2 / ||sqrt(exp(lvars[o, :]))||_2 -- mainviz.lua:20's |mu| / sigma
+ * when I = 1. None of the calls below synchronises or allocates. */
+typedef struct vbnn_unit_desc {
+    const float* means; const float* lvars; int64_t O, I;     /* the layer's fp32 parameters, O x I (read by vbnn_unit_snr only) */
+    float* key;                                /* O floats: written by vbnn_unit_snr, read by vbnn_unit_select / vbnn_unit_index */
+    uint32_t* keep;                            /* vbnn_unit_index: O words, the kept units ascending; the first n_keep[0] are written */
+    uint32_t* n_keep;                          /* vbnn_unit_index: one device word, the length of the list */
+} vbnn_unit_desc;
+/* mainviz.lua:20 per unit: key[o] = sqrt(sum_i means[o,i]^2) / sqrt(sum_i expf(lvars[o,i])) for every listed layer. expf is the
+ * weight key's (vbnn_snr); both sums run in double in one fixed order (a wave per row, or a workgroup per row when the rows are
+ * few and long: wave shuffles, then the waves in order), square roots and quotient in double, ONE rounding to fp32: two runs give
+ * the same bits. A NaN key (a NaN parameter, 0 / 0) is stored as the positive quiet NaN 0x7fc00000, so that keys order as their
+ * bit patterns with NaN above every number; such a unit is never pruned. 8 B read per weight. n_layers <= 8. */
+int vbnn_unit_snr(vbnn_ctx* ctx, int n_layers, const vbnn_unit_desc* layers);
+/* mainviz.lua:20-21 turned round, per unit: tau = the EXACT k-th smallest key (0-based) over the union of the listed layers'
+ * units, read from the key arrays vbnn_unit_snr wrote, so that `key < tau` prunes at most k units (fewer when keys tie at tau)
+ * -- what vbnn_prune_select is for weights. It is written to tau_dev[0 .. n_layers), one copy per listed layer: the array
+ * vbnn_unit_index reads (all layers in one call = one global threshold; a call per layer with tau_dev + l = one per layer). One
+ * one-workgroup kernel (a radix select on the 32 key bits, integer counts). 0 <= k < n_units, else VBNN_ERR_INVALID (to prune
+ * everything pass tau = +inf to vbnn_unit_index). */
+int vbnn_unit_select(vbnn_ctx* ctx, int n_layers, const vbnn_unit_desc* layers, int64_t k, float* tau_dev);
+/* mainviz.lua:21 per unit, as index lists: layer l's threshold is tau_dev[l] read on the device (an array of n_layers floats,
+ * chained behind vbnn_unit_select), or tau_host for every layer when tau_dev is NULL. With n0 = #{o : !(key[o] < tau)} and
+ * n = min(O, multiple ceil(max(n0, 1) / multiple)), the kept set is the n units that come first in the order "larger key first,
+ * NaN above all numbers, on equal keys the lower index first": with multiple = 1 and n0 >= 1 exactly {o : !(key[o] < tau)}; a
+ * layer that would lose every unit keeps its best one; multiple = 256 gives widths the tiled GEMM kernels take. keep[0 .. n) =
+ * the kept units ascending, n_keep[0] = n. One workgroup per layer; places come from ordered counts (wave ballots): no atomics
+ * on the list, two runs give the same words. multiple >= 1. */
+int vbnn_unit_index(vbnn_ctx* ctx, int n_layers, const vbnn_unit_desc* layers, const float* tau_dev, float tau_host, int64_t multiple);
+/* The compaction: dst_means[r, c] = means[rows[r], cols[c]], dst_lvars likewise in the same sweep, dst_bias[r] = bias[rows[r]] --
+ * fp32 bit copies into dense n_rows x n_cols arrays. rows == NULL: every row (n_rows = O); cols == NULL: every column
+ * (n_cols = I). lvars / dst_lvars and bias / dst_bias are optional, in pairs: a VB layer passes all three (rows = its own kept
+ * list, cols = the previous layer's), the final Linear its weight alone with cols = the last VB layer's list. The list LENGTHS
+ * are host values (read back from n_keep). Index words are clamped to the source shape. Any O, I, n_rows, n_cols >= 1. */
+typedef struct vbnn_unit_gather_args {
+    const float* means; const float* lvars; const float* bias; int64_t O, I;      /* source: O x I (and O) */
+    const uint32_t* rows; int64_t n_rows;
+    const uint32_t* cols; int64_t n_cols;
+    float* dst_means; float* dst_lvars; float* dst_bias;                           /* n_rows x n_cols (and n_rows) */
+} vbnn_unit_gather_args;
+int vbnn_unit_gather(vbnn_ctx* ctx, const vbnn_unit_gather_args* a);
+
 /* The same criterion as separate modules, for the module-level call order of mlp.lua:77-80:
  * nn.LogSoftMax:updateOutput is vbnn_logsoftmax_nll with g_logits = loss = correct = NULL. */
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,

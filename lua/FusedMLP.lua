@@ -441,6 +441,105 @@ function FusedMLP:loss_and_accuracy()
     return a[0], c[0]
 end
 
+-- structured pruning (the group form of mainviz.lua:20-21; engine.py:FusedMLP.prune_units, tools/c_host.c:fm_prune_units): every
+-- hidden unit with ||mu_o|| / ||sigma_o|| < tau. Exactly one of `fraction` (0 .. 1: tau = the exact k-th smallest unit key,
+-- k = floor(fraction units); 1 = tau = +inf) and `threshold` (tau itself); scope 'global' (one tau over the units of all VB layers,
+-- the default) or 'layer'; `multiple` (default 1): every layer's kept count is rounded up to a multiple of it (256: widths the tiled
+-- GEMM kernels take); a layer never loses its last unit. Returns a table: tau[li], keep[li] (device, uint32, ascending),
+-- hidden[li] (the kept counts), layers[li] = { n_units, n_pruned, fraction_pruned } and the same three as totals, n_weights,
+-- n_weights_before. :compact(result) builds the smaller network.
+function FusedMLP:prune_units(fraction, threshold, scope, multiple)
+    assert((fraction == nil) ~= (threshold == nil), 'prune_units: exactly one of fraction and threshold')
+    scope, multiple = scope or 'global', multiple or 1
+    assert(scope == 'global' or scope == 'layer', "prune_units: scope 'global' or 'layer'")
+    assert(fraction == nil or (fraction >= 0 and fraction <= 1), 'prune_units: fraction in 0 .. 1')
+    assert(multiple >= 1 and multiple == math.floor(multiple), 'prune_units: multiple is an integer >= 1')
+    assert(not self.sharded, 'prune_units: the fp32 parameters of a sharded engine are this rank\'s rows only')
+    local n = #self.vb
+    local o = { scope = scope, multiple = multiple, tau = {}, keep = {}, hidden = {}, layers = {} }
+    local tau, n_keep, keys = vb.alloc(4 * n), vb.alloc(4 * n), {}
+    for li, v in ipairs(self.vb) do keys[li], o.keep[li] = vb.alloc(4 * v.O), vb.alloc(4 * v.O) end
+    local function descs(first, count)
+        local d = ffi.new('vbnn_unit_desc[?]', count)
+        for j = 0, count - 1 do
+            local v, e = self.vb[first + j], d[j]
+            e.means, e.lvars, e.O, e.I = f32(v.means), f32(v.lvars), v.O, v.I
+            e.key, e.keep = f32(keys[first + j]), ffi.cast('uint32_t*', o.keep[first + j])
+            e.n_keep = ffi.cast('uint32_t*', n_keep) + (first + j - 1)
+        end
+        return d
+    end
+    check(C.vbnn_unit_snr(vb.ctx, n, descs(1, n)))
+    local select = fraction ~= nil and fraction < 1                -- else the threshold is a host value
+    local groups = (scope == 'global') and { { 1, n } } or {}
+    if scope == 'layer' then for li = 1, n do groups[li] = { li, 1 } end end
+    for _, g in ipairs(groups) do
+        if select then                                             -- the threshold stays on the device, behind the select
+            local units = 0
+            for li = g[1], g[1] + g[2] - 1 do units = units + self.vb[li].O end
+            local k = math.min(math.floor(fraction * units), units - 1)
+            check(C.vbnn_unit_select(vb.ctx, g[2], descs(g[1], g[2]), k, f32(tau) + (g[1] - 1)))
+        end
+    end
+    local tau_host = threshold or math.huge
+    check(C.vbnn_unit_index(vb.ctx, n, descs(1, n), select and f32(tau) or nil, tau_host, multiple))
+    local nh, th = ffi.new('uint32_t[?]', n), ffi.new('float[?]', n)
+    check(C.vbnn_buf_download(vb.ctx, nh, n_keep, 4 * n))
+    if select then check(C.vbnn_buf_download(vb.ctx, th, tau, 4 * n)) end
+    local function weights(sizes)
+        local w = sizes[#sizes] * self.n_classes
+        for k = 1, #sizes - 1 do w = w + sizes[k] * sizes[k + 1] end
+        return w
+    end
+    local sizes, units, kept = { self.sizes[1] }, 0, 0
+    for li, v in ipairs(self.vb) do
+        local nk = tonumber(nh[li - 1])
+        o.tau[li] = select and th[li - 1] or tau_host
+        o.hidden[li], sizes[li + 1] = nk, nk
+        o.layers[li] = { n_units = v.O, n_pruned = v.O - nk, fraction_pruned = (v.O - nk) / v.O }
+        units, kept = units + v.O, kept + nk
+    end
+    o.n_units, o.n_pruned, o.fraction_pruned = units, units - kept, (units - kept) / units
+    o.n_weights, o.n_weights_before = weights(sizes), weights(self.sizes)
+    o.owner, o.version, o.units = self, self.version or 0, true
+    return o
+end
+
+-- The network a :prune_units result leaves (engine.py:FusedMLP.compact, tools/c_host.c:fm_compact): a new FusedMLP with
+-- hidden = result.hidden (one process), its parameters gathered on the device -- a layer's rows by its own kept list, its columns
+-- by the previous layer's, the final weight by the last list; the final bias copied (a plain gather), the draw counter advanced to this one's -- and
+-- prepared. Fresh optimiser state; the removed units' constant activations are dropped. `overrides`: options that differ.
+function FusedMLP:compact(result, overrides)
+    assert(result and result.units and result.owner == self, 'compact: a result of this :prune_units')
+    assert(result.version == (self.version or 0), 'compact: the parameters changed since this result was taken')
+    local opt = {}
+    for k, v in pairs(self.opt) do opt[k] = v end
+    opt.world, opt.rank, opt.comm_id, opt.exchange_mode = nil, nil, nil, nil
+    for k, v in pairs(overrides or {}) do opt[k] = v end
+    opt.hidden = result.hidden
+    local new = FusedMLP.new(opt)
+    local ga = ffi.new('vbnn_unit_gather_args')
+    local cols = nil
+    for li, v in ipairs(self.vb) do
+        local w = new.vb[li]
+        ga.means, ga.lvars, ga.bias, ga.O, ga.I = f32(v.means), f32(v.lvars), f32(v.bias), v.O, v.I
+        ga.rows, ga.n_rows, ga.cols, ga.n_cols = ffi.cast('uint32_t*', result.keep[li]), w.O, cols, w.I
+        ga.dst_means, ga.dst_lvars, ga.dst_bias = f32(w.means), f32(w.lvars), f32(w.bias)
+        check(C.vbnn_unit_gather(vb.ctx, ga))
+        cols = ffi.cast('uint32_t*', result.keep[li])
+    end
+    ga.means, ga.lvars, ga.bias, ga.O, ga.I = f32(self.weight3), nil, nil, self.n_classes, self.sizes[#self.sizes]
+    ga.rows, ga.n_rows, ga.cols, ga.n_cols = nil, self.n_classes, cols, new.sizes[#new.sizes]
+    ga.dst_means, ga.dst_lvars, ga.dst_bias = f32(new.weight3), nil, nil
+    check(C.vbnn_unit_gather(vb.ctx, ga))
+    ga.means, ga.O, ga.I, ga.n_rows, ga.cols, ga.n_cols, ga.dst_means = f32(self.bias3), 1, self.n_classes, 1, nil, self.n_classes, f32(new.bias3)
+    check(C.vbnn_unit_gather(vb.ctx, ga))
+    new.draw = self.draw
+    if new.draw_dev then check(C.vbnn_sample(vb.ctx, new.draw_dev, self.draw)) end   -- its device counter starts at zero
+    new:prepare()
+    return new
+end
+
 -- signal-to-noise pruning (mainviz.lua:20-27; engine.py:FusedMLP.prune, tools/c_host.c:fm_prune): every weight with
 -- |mu| / sigma < tau. Exactly one of `fraction` (0 .. 1: tau = the exact k-th smallest key, k = floor(fraction W); 1 = everything,
 -- tau = +inf) and `threshold` (tau itself; the reference's 0.005); scope 'global' (one tau over all VB layers, the default) or

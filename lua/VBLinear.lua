@@ -243,6 +243,19 @@ function VBLinear:snr()
     return out
 end
 
+-- the unit form of mainviz.lua:20: ||means[o, :]|| / ||sigma[o, :]|| per output unit (the key of structured pruning,
+-- FusedMLP:prune_units) as an O-element FloatTensor
+function VBLinear:unit_snr()
+    local O, I = self.means:size(1), self.means:size(2)
+    local out, d_out = torch.FloatTensor(O), vb.alloc(O * 4)
+    local d = ffi.new('vbnn_unit_desc[1]')
+    d[0].means, d[0].lvars = ffi.cast('float*', self.d.means), ffi.cast('float*', self.d.lvars)
+    d[0].O, d[0].I, d[0].key = O, I, ffi.cast('float*', d_out)
+    check(C.vbnn_unit_snr(vb.ctx, 1, d))
+    check(C.vbnn_buf_download(vb.ctx, out:data(), d_out, O * 4))
+    return out
+end
+
 -- VBLinear:update (VBLinear.lua:124-166): SGD on the bias, compute_prior, likelihood + KL gradients, Adam on means
 -- (opt.meanState) and on lvars (opt.varState) with per-layer moment state -- on the device (vbnn_sgd_step /
 -- vbnn_adam_step: one streaming pass per tensor, the two gradient parts added inside it); the host tensors are

@@ -285,6 +285,22 @@ typedef struct vbnn_sparse_fwd_args {
     int64_t rows_per_draw;
 } vbnn_sparse_fwd_args;
 int vbnn_forward_sparse(vbnn_ctx* ctx, int dtype, const vbnn_sparse_fwd_args* a);
+typedef struct vbnn_unit_desc {
+    const float* means; const float* lvars; int64_t O, I;
+    float* key;
+    uint32_t* keep;
+    uint32_t* n_keep;
+} vbnn_unit_desc;
+int vbnn_unit_snr(vbnn_ctx* ctx, int n_layers, const vbnn_unit_desc* layers);
+int vbnn_unit_select(vbnn_ctx* ctx, int n_layers, const vbnn_unit_desc* layers, int64_t k, float* tau_dev);
+int vbnn_unit_index(vbnn_ctx* ctx, int n_layers, const vbnn_unit_desc* layers, const float* tau_dev, float tau_host, int64_t multiple);
+typedef struct vbnn_unit_gather_args {
+    const float* means; const float* lvars; const float* bias; int64_t O, I;
+    const uint32_t* rows; int64_t n_rows;
+    const uint32_t* cols; int64_t n_cols;
+    float* dst_means; float* dst_lvars; float* dst_bias;
+} vbnn_unit_gather_args;
+int vbnn_unit_gather(vbnn_ctx* ctx, const vbnn_unit_gather_args* a);
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,
                      float inv_n, double* loss_sum_dev, int32_t* correct_dev);
 int vbnn_nll_backward(vbnn_ctx* ctx, const int32_t* target, int64_t N, int64_t C, float inv_n, float* g);

@@ -14,7 +14,8 @@
  *
  *   c_host --dtype f32|bf16 --input 784 --hidden 400,400 --classes 10 --batch 256 [--S 1] [--steps 2] [--update]
  *          [--comm [--sharded]] [--graph] [--kl-shadows] [--seed 3] --out arena.bin
- *          [--predict S [--predict-rows 32768] [--predict-stacked -1|0|1] [--prune Q | --prune-threshold T [--sparse]]]
+ *          [--predict S [--predict-rows 32768] [--predict-stacked -1|0|1] [--prune Q | --prune-threshold T [--sparse]]
+ *                       [--prune-units Q [--unit-multiple M]]]
  *   --predict S: after the steps, the posterior predictive of the minibatch over S draws (fm_predict), appended to the file:
  *   int64 R, int64 C, int32 S, stacked, chunks, draw counter after it; probs and log_probs (R x C floats); entropy,
  *   expected_entropy, mutual_info (R floats each); pred (R int32); the four totals (doubles). Without it the file is as above.
@@ -23,6 +24,11 @@
  *   doubles (pruned, sum of pruned variances, sum of variances, W), then a second predict block as above (S more draws).
  *   --sparse (with --prune / --prune-threshold): that second predict runs under the COMPRESSED view of the same pruning (fm_compress,
  *   fm_predict_forward_sparse: vbnn_prune_compress, vbnn_forward_sparse); the file layout is unchanged.
+ *   --prune-units Q [--unit-multiple M] (with --predict S, instead of --prune): then the structured pruning (fm_prune_units: the
+ *   fraction Q of all hidden units, every layer's kept count rounded up to a multiple of M), the compact network (fm_compact) and
+ *   the predictive of THAT network, appended: int32 layers, float tau, per layer int32 kept count, per layer the kept list (int32),
+ *   per layer the compact means, lvars (O' x I' floats each) and bias (O'), the compact final weight (C x H') and bias (C), then a
+ *   second predict block as above (S more draws of the compact network's own counter).
  *   --graph: the context gets a stream of its own (vbnn_ctx_create_cu_budget), the draw counter lives on the device
  *   (vbnn_fwd_args.draw_dev, vbnn_sample), step 2 is CAPTURED (vbnn_capture_begin / _end) and steps 2.. are replays of it.
  *   arena.bin: int64 n_grads, double loss, int32 correct, int32 flags, then n_grads floats (the arena after the last
@@ -522,6 +528,79 @@ static void fm_loss_and_accuracy(fused_mlp* m, double* loss, int32_t* correct) {
     *loss = a[0];
 }
 
+/* ---- structured pruning (engine.py:FusedMLP.prune_units / compact, lua/FusedMLP.lua:prune_units / compact), scope 'global': every
+   hidden unit with ||mu_o|| / ||sigma_o|| < tau goes, tau the exact k-th smallest unit key over all VB layers, k = floor(fraction
+   units) (fraction = 1: tau = +inf; a layer keeps its best unit); every layer's kept count rounded up to `multiple`. Leaves the
+   kept lists on the device and their lengths on the host. */
+typedef struct {
+    float tau;
+    uint32_t* keep[MAX_LAYERS];                                            /* device: a layer's kept units, ascending */
+    int32_t n_keep[MAX_LAYERS];
+} unit_out;
+
+static void fm_prune_units(fused_mlp* m, double fraction, int64_t multiple, unit_out* o) {
+    const int n = m->n_layers;
+    vbnn_unit_desc d[MAX_LAYERS];
+    float* tau = (float*)dev_alloc((size_t)n * 4);
+    uint32_t* n_keep = (uint32_t*)dev_alloc((size_t)n * 4);
+    int64_t units = 0;
+    memset(d, 0, sizeof d);
+    for (int li = 0; li < n; ++li) {
+        layer_t* v = &m->vb[li];
+        o->keep[li] = (uint32_t*)dev_alloc((size_t)v->O * 4);
+        d[li].means = v->means; d[li].lvars = v->lvars; d[li].O = v->O; d[li].I = v->I;
+        d[li].key = (float*)dev_alloc((size_t)v->O * 4); d[li].keep = o->keep[li]; d[li].n_keep = n_keep + li;
+        units += v->O;
+    }
+    CHECK(vbnn_unit_snr(g_ctx, n, d));
+    const int select = fraction < 1.0;                                     /* else the threshold is a host value */
+    o->tau = INFINITY;
+    if (select) {                                                          /* the threshold stays on the device, behind the select */
+        int64_t k = (int64_t)floor(fraction * (double)units);
+        if (k > units - 1) k = units - 1;
+        CHECK(vbnn_unit_select(g_ctx, n, d, k, tau));
+    }
+    CHECK(vbnn_unit_index(g_ctx, n, d, select ? tau : NULL, o->tau, multiple));
+    CHECK(vbnn_buf_download(g_ctx, o->n_keep, n_keep, (size_t)n * 4));
+    if (select) CHECK(vbnn_buf_download(g_ctx, &o->tau, tau, 4));
+}
+
+/* the network a unit pruning leaves, as a second fused_mlp: a layer's rows by its own kept list, its columns by the previous
+   layer's, the final weight by the last list; the final bias copied (a plain gather), the draw counter advanced to the
+   source's; then prepared */
+static void fm_compact(fused_mlp* m, const unit_out* o, fused_mlp* c) {
+    const int n = m->n_layers;
+    int64_t sizes[MAX_LAYERS + 1];
+    sizes[0] = m->sizes[0];
+    for (int li = 0; li < n; ++li) sizes[li + 1] = o->n_keep[li];
+    fm_new(c, m->dtype, sizes, n, m->n_classes, m->seed, m->var_init, m->B, m->S, 0);
+    c->kl_in_update = m->kl_in_update;
+    vbnn_unit_gather_args ga;
+    const uint32_t* cols = NULL;
+    for (int li = 0; li < n; ++li) {
+        layer_t *v = &m->vb[li], *w = &c->vb[li];
+        memset(&ga, 0, sizeof ga);
+        ga.means = v->means; ga.lvars = v->lvars; ga.bias = v->bias; ga.O = v->O; ga.I = v->I;
+        ga.rows = o->keep[li]; ga.n_rows = w->O; ga.cols = cols; ga.n_cols = w->I;
+        ga.dst_means = w->means; ga.dst_lvars = w->lvars; ga.dst_bias = w->bias;
+        CHECK(vbnn_unit_gather(g_ctx, &ga));
+        cols = o->keep[li];
+    }
+    memset(&ga, 0, sizeof ga);
+    ga.means = m->weight3; ga.O = m->n_classes; ga.I = m->sizes[n]; ga.n_rows = m->n_classes; ga.cols = cols; ga.n_cols = sizes[n];
+    ga.dst_means = c->weight3;
+    CHECK(vbnn_unit_gather(g_ctx, &ga));
+    memset(&ga, 0, sizeof ga);
+    ga.means = m->bias3; ga.O = 1; ga.I = m->n_classes; ga.n_rows = 1; ga.n_cols = m->n_classes; ga.dst_means = c->bias3;
+    CHECK(vbnn_unit_gather(g_ctx, &ga));
+    c->draw = m->draw;
+    if (m->draw_dev) {                                                     /* its device counter starts at zero */
+        c->draw_dev = (uint32_t*)dev_alloc(4);
+        CHECK(vbnn_sample(g_ctx, c->draw_dev, m->draw));
+    }
+    fm_prepare(c);
+}
+
 /* ---- signal-to-noise pruning (mainviz.lua:20-27; engine.py:FusedMLP.prune, lua/FusedMLP.lua:prune), scope 'global': every weight
    with |mu| / sigma < tau, tau the threshold itself (fraction < 0) or the exact k-th smallest key, k = floor(fraction W)
    (fraction = 1: everything, tau = +inf). Leaves the pruned operand shadows and the numbers mainviz.lua:22-27 prints. */
@@ -831,13 +910,49 @@ int main(int argc, char** argv) {
     const int predict_S = atoi(arg_value(argc, argv, "--predict", "0"));
     const char* prune_q = arg_value(argc, argv, "--prune", NULL);
     const char* prune_t = arg_value(argc, argv, "--prune-threshold", NULL);
-    const int prune_passes = (predict_S > 0 && (prune_q || prune_t)) ? 2 : 1;
+    const char* prune_u = arg_value(argc, argv, "--prune-units", NULL);
+    if (prune_u && (prune_q || prune_t)) { fprintf(stderr, "c_host: --prune-units or --prune / --prune-threshold, not both\n"); return 1; }
+    if (predict_S <= 0 && prune_u) { fprintf(stderr, "c_host: --prune-units needs --predict S\n"); return 1; }
+    const int prune_passes = (predict_S > 0 && (prune_q || prune_t || prune_u)) ? 2 : 1;
     prune_out pr;
     static sparse_out sp;
+    static fused_mlp compact;
+    fused_mlp* pn = &net;                                        /* the network predict runs on */
     for (int pass = 0; pass < prune_passes && predict_S > 0; ++pass) {
         /* --predict S: the posterior predictive of the minibatch after the steps, appended to the file; with --prune Q /
            --prune-threshold T once more under the pruned view, behind the numbers of the pruning */
-        if (pass == 1) {
+        if (pass == 1 && prune_u) {
+            /* --prune-units Q: the structured pruning, the compact network it leaves, and the predictive of that network */
+            unit_out un;
+            fm_prune_units(&net, atof(prune_u), atoll(arg_value(argc, argv, "--unit-multiple", "1")), &un);
+            fm_compact(&net, &un, &compact);
+            pn = &compact;
+            const int32_t nl = n_layers;
+            fwrite(&nl, 4, 1, f); fwrite(&un.tau, 4, 1, f); fwrite(un.n_keep, 4, (size_t)n_layers, f);
+            for (int li = 0; li < n_layers; ++li) {
+                int32_t* kh = (int32_t*)malloc((size_t)un.n_keep[li] * 4);
+                CHECK(vbnn_buf_download(g_ctx, kh, un.keep[li], (size_t)un.n_keep[li] * 4));
+                fwrite(kh, 4, (size_t)un.n_keep[li], f);
+                free(kh);
+            }
+            for (int li = 0; li <= n_layers; ++li) {             /* the compact parameters: VB layers, then the final Linear */
+                const size_t rows = li < n_layers ? (size_t)compact.vb[li].O : (size_t)n_classes;
+                const size_t w = rows * (size_t)compact.sizes[li];
+                float* const src[3] = {li < n_layers ? compact.vb[li].means : compact.weight3, li < n_layers ? compact.vb[li].lvars : NULL,
+                                       li < n_layers ? compact.vb[li].bias : compact.bias3};
+                const size_t cnt[3] = {w, w, rows};
+                float* ph = (float*)malloc(w * 4);
+                for (int k = 0; k < 3; ++k) {
+                    if (!src[k]) continue;
+                    CHECK(vbnn_buf_download(g_ctx, ph, src[k], cnt[k] * 4));
+                    fwrite(ph, 4, cnt[k], f);
+                }
+                free(ph);
+            }
+            printf("c_host: pruned units below snr %.9g, compact network %lld", (double)un.tau, (long long)sizes[0]);
+            for (int li = 0; li < n_layers; ++li) printf("-%d", un.n_keep[li]);
+            printf("-%d\n", n_classes);
+        } else if (pass == 1) {
             fm_prune(&net, prune_q ? atof(prune_q) : -1.0, prune_t ? (float)atof(prune_t) : 0.f, &pr);
             fm_use_pruned(&net, &pr);
             if (arg_flag(argc, argv, "--sparse")) {               /* the same pruning, compressed: predict multiplies by the entries */
@@ -854,11 +969,11 @@ int main(int argc, char** argv) {
             printf("c_host: pruned %.0f of %.0f weights below snr %.9g\n", np, W, (double)pr.tau);
         }
         predict_out po;
-        fm_predict(&net, x, sizes[0], t, N, predict_S, atoll(arg_value(argc, argv, "--predict-rows", "32768")),
+        fm_predict(pn, x, sizes[0], t, N, predict_S, atoll(arg_value(argc, argv, "--predict-rows", "32768")),
                    atoi(arg_value(argc, argv, "--predict-stacked", "-1")), &po);
         const int64_t RC = po.R * po.C;
         float* hf = (float*)malloc((size_t)RC * 4);
-        const int32_t head[4] = {po.S, po.stacked, po.chunks, (int32_t)net.draw};
+        const int32_t head[4] = {po.S, po.stacked, po.chunks, (int32_t)pn->draw};
         fwrite(&po.R, 8, 1, f); fwrite(&po.C, 8, 1, f); fwrite(head, 4, 4, f);
         float* const rc[2] = {po.probs, po.log_probs};
         for (int k = 0; k < 2; ++k) { CHECK(vbnn_buf_download(g_ctx, hf, rc[k], (size_t)RC * 4)); fwrite(hf, 4, (size_t)RC, f); }

@@ -115,6 +115,15 @@ class SparseFwdArgs(C.Structure):     # vbnn_sparse_fwd_args
                 ("h", _vp), ("h2", _vp), ("ld_h", _i64), ("hT", _vp), ("h2T", _vp), ("ld_hT", _i64), ("rows_per_draw", _i64)]
 
 
+class UnitDesc(C.Structure):          # vbnn_unit_desc
+    _fields_ = [("means", _vp), ("lvars", _vp), ("O", _i64), ("I", _i64), ("key", _vp), ("keep", _vp), ("n_keep", _vp)]
+
+
+class UnitGatherArgs(C.Structure):    # vbnn_unit_gather_args
+    _fields_ = [("means", _vp), ("lvars", _vp), ("bias", _vp), ("O", _i64), ("I", _i64), ("rows", _vp), ("n_rows", _i64),
+                ("cols", _vp), ("n_cols", _i64), ("dst_means", _vp), ("dst_lvars", _vp), ("dst_bias", _vp)]
+
+
 _SIGS = {
     "vbnn_abi_version": ([], _i),
     "vbnn_last_error": ([], C.c_char_p),
@@ -204,6 +213,10 @@ _SIGS = {
     "vbnn_prune_pack": ([_vp, _i, _i, _vp, _vp, _f], _i),
     "vbnn_prune_compress": ([_vp, _i, _i, _vp, _vp, _vp, _f], _i),
     "vbnn_forward_sparse": ([_vp, _i, C.POINTER(SparseFwdArgs)], _i),
+    "vbnn_unit_snr": ([_vp, _i, _vp], _i),
+    "vbnn_unit_select": ([_vp, _i, _vp, _i64, _vp], _i),
+    "vbnn_unit_index": ([_vp, _i, _vp, _vp, _f, _i64], _i),
+    "vbnn_unit_gather": ([_vp, C.POINTER(UnitGatherArgs)], _i),
     "vbnn_nll_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _f, _vp, _vp], _i),
     "vbnn_nll_backward": ([_vp, _vp, _i64, _i64, _f, _vp], _i),
     "vbnn_logsoftmax_backward": ([_vp, _vp, _vp, _vp, _i64, _i64], _i),

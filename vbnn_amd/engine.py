@@ -169,6 +169,35 @@ class SparsePruneResult(PruneResult):
         return self
 
 
+class UnitPruneResult:
+    """FusedMLP.prune_units' outcome: structured signal-to-noise pruning, whole hidden units by ||mu_o|| / ||sigma_o|| (the group
+    form of mainviz.lua:20-21). Lists in VB layer order: tau (the threshold: a unit with key < tau goes; one value repeated when
+    scope = "global"), keep[li] (the kept units, an ascending int32 device tensor), hidden (their counts: the widths of the
+    compact network), layers[li] = dict(n_units, n_pruned, fraction_pruned); the same three names as attributes are the totals.
+    n_weights / n_weights_before: weights of the VB layers plus the final Linear, after and before. A result is a snapshot of
+    the parameters it was taken from (version); FusedMLP.compact(result) builds the smaller dense engine."""
+
+    def __init__(self, engine, scope, multiple, tau, keep, sizes, n_classes, version):
+        self.engine, self.scope, self.multiple, self.version = engine, scope, int(multiple), version
+        self.tau = [float(t) for t in tau]
+        self.keep = list(keep)
+        self.hidden = [int(k.numel()) for k in self.keep]
+        units = [int(o) for o in sizes[1:]]
+        self.layers = [self._summary(o, o - n) for o, n in zip(units, self.hidden)]
+        tot = self._summary(sum(units), sum(units) - sum(self.hidden))
+        self.n_units, self.n_pruned, self.fraction_pruned = tot["n_units"], tot["n_pruned"], tot["fraction_pruned"]
+        self.n_weights_before = self._weights([int(sizes[0])] + units, n_classes)
+        self.n_weights = self._weights([int(sizes[0])] + self.hidden, n_classes)
+
+    @staticmethod
+    def _summary(n_units, n_pruned):
+        return dict(n_units=int(n_units), n_pruned=int(n_pruned), fraction_pruned=n_pruned / n_units if n_units else 0.0)
+
+    @staticmethod
+    def _weights(sizes, n_classes):
+        return sum(sizes[i] * sizes[i + 1] for i in range(len(sizes) - 1)) + sizes[-1] * int(n_classes)
+
+
 class FusedMLP:
     def __init__(self, opt, device=None, world_size=1, rank=0, process_group=None, force_reduce=False, stream=None):
         """stream: a torch.cuda.Stream for this engine's launches (a library context of its own, hence its own reduction
@@ -1444,6 +1473,123 @@ class FusedMLP:
                                          _p(self._lc), v.O * v.I))
             lc += float(self._lc[0].item())
         return lc
+
+    # ---- structured pruning (csrc/units.hip): whole hidden units by the group form of mainviz.lua:20-21, and the compact engine
+    # that is left -- a smaller DENSE network for the ordinary kernels. Nothing of this engine changes: prune_units reads the
+    # fp32 parameters, compact writes a new FusedMLP.
+    def _unit_descs(self, keys, keep, n_keep, lis):
+        descs = (L.UnitDesc * len(lis))()
+        for j, li in enumerate(lis):
+            v = self.vb[li]
+            descs[j] = L.UnitDesc(means=_p(v.means), lvars=_p(v.lvars), O=v.O, I=v.I, key=_p(keys[li]),
+                                  keep=_p(keep[li]) if keep is not None else None,
+                                  n_keep=C.c_void_p(n_keep.data_ptr() + 4 * li) if n_keep is not None else None)
+        return descs
+
+    @_ordered
+    def unit_snr(self, li):
+        """||means[o, :]|| / ||sigma[o, :]|| of VB layer li's output units as an O-element fp32 tensor: the unit pruning key, bit
+        for bit (|mu| / sigma of mainviz.lua:20 when the layer has one input)."""
+        self._need_gathered_parameters("unit_snr")
+        keys = {li: torch.empty(self.vb[li].O, dtype=torch.float32, device=self.device)}
+        L.check(L.lib().vbnn_unit_snr(self.ctx.h, 1, self._unit_descs(keys, None, None, [li])))
+        return keys[li]
+
+    @_ordered
+    def prune_units(self, fraction=None, threshold=None, scope="global", multiple=1):
+        """Prune whole hidden units by signal-to-noise ratio: every output unit of a VB layer with ||mu_o|| / ||sigma_o|| < tau.
+        Exactly one of threshold (tau itself) and fraction in [0, 1] (tau = the exact k-th smallest unit key, k = floor(fraction
+        n_units), so at most k units go -- fewer when keys tie at tau; fraction = 1: tau = +inf). scope = "global": one tau over
+        the units of all VB layers; "layer": the fraction applies to each layer. multiple: every layer's kept count is rounded
+        UP to a multiple of it (capped at the layer's width) by taking back the best of the pruned units -- 256 gives widths the
+        tiled GEMM kernels take; a layer never loses its last unit. Returns a UnitPruneResult (synchronises once, to read tau and
+        the kept counts); nothing changes in this engine -- compact(result) builds the smaller one."""
+        if (fraction is None) == (threshold is None):
+            raise ValueError("prune_units: exactly one of fraction and threshold")
+        if scope not in ("global", "layer"):
+            raise ValueError(f"prune_units: scope = {scope!r} ('global' or 'layer')")
+        if fraction is not None and not 0.0 <= float(fraction) <= 1.0:
+            raise ValueError(f"prune_units: fraction = {fraction} (0 .. 1)")
+        if int(multiple) != multiple or int(multiple) < 1:
+            raise ValueError(f"prune_units: multiple = {multiple} (an integer >= 1)")
+        self._need_gathered_parameters("prune_units")
+        if not self._shadows_ready:            # (prepare() counts as a parameter change: do it before the snapshot is versioned)
+            self.prepare()
+        lib, ctx, dev, nl = L.lib(), self.ctx.h, self.device, len(self.vb)
+        keys = [torch.empty(v.O, dtype=torch.float32, device=dev) for v in self.vb]
+        keep = [torch.zeros(v.O, dtype=torch.int32, device=dev) for v in self.vb]
+        words = torch.zeros(2 * nl, dtype=torch.int32, device=dev)               # [tau per layer | kept count per layer]: ONE read-back
+        tau, n_keep = words[:nl].view(torch.float32), words[nl:]
+        tau_host = float(threshold) if threshold is not None else float("inf")
+        select = fraction is not None and float(fraction) < 1.0                   # else the threshold is a host value
+        every = list(range(nl))
+        L.check(lib.vbnn_unit_snr(ctx, nl, self._unit_descs(keys, keep, n_keep, every)))
+        for g in ([every] if scope == "global" else [[li] for li in every]):
+            if select:                         # the threshold stays on the device, behind the select
+                n_g = sum(self.vb[li].O for li in g)
+                k = min(int(math.floor(float(fraction) * n_g)), n_g - 1)
+                L.check(lib.vbnn_unit_select(ctx, len(g), self._unit_descs(keys, keep, n_keep, g), k, C.c_void_p(tau.data_ptr() + 4 * g[0])))
+        L.check(lib.vbnn_unit_index(ctx, nl, self._unit_descs(keys, keep, n_keep, every), _p(tau) if select else None, tau_host,
+                                    int(multiple)))
+        host = words.cpu()
+        counts = host[nl:].tolist()
+        return UnitPruneResult(self, scope, multiple, host[:nl].view(torch.float32).tolist() if select else [tau_host] * nl,
+                               [keep[li][:counts[li]] for li in every], self.sizes, self.n_classes, self._pver)
+
+    @_ordered
+    def compact(self, result, **opt_overrides):
+        """The network `result` (a UnitPruneResult of this engine) leaves, as a new, ordinary FusedMLP on the same device: hidden =
+        result.hidden, one process; means / lvars / bias of every VB layer and the final weight gathered on the device (a
+        layer's rows by its own kept list, its columns by the previous layer's; the first layer keeps every input), the final
+        bias copied, prepare()d, with this engine's seed and draw counter and a fresh optimiser state. The removed units'
+        constant activations are dropped, not folded into the next bias. The noise of the compact engine is addressed by the
+        compacted unit index: its sampled predictions are the pruned network's in distribution, not draw for draw.
+        opt_overrides: options of the new engine that differ from this one's."""
+        if not isinstance(result, UnitPruneResult) or result.engine is not self:
+            raise ValueError("compact: a UnitPruneResult of this engine")
+        if result.version != self._pver:
+            raise RuntimeError("compact: the parameters changed since this result was taken (prune_units() again)")
+        self._need_gathered_parameters("compact")
+        opt = dict(self.opt)
+        for name in ("exchange_mode", "exchange", "cu_budget"):                   # one process, this engine's stream
+            opt.pop(name, None)
+        opt.update(opt_overrides)
+        opt["hidden"] = list(result.hidden)
+        new = FusedMLP(opt, device=self.device, stream=self.ctx.torch_stream)
+        lib = L.lib()
+        with new._on_stream():
+            cols = None
+            for v, w, rows in zip(self.vb, new.vb, result.keep):
+                a = L.UnitGatherArgs(means=_p(v.means), lvars=_p(v.lvars), bias=_p(v.bias), O=v.O, I=v.I, rows=_p(rows), n_rows=w.O,
+                                     cols=_p(cols), n_cols=w.I, dst_means=_p(w.means), dst_lvars=_p(w.lvars), dst_bias=_p(w.bias))
+                L.check(lib.vbnn_unit_gather(new.ctx.h, C.byref(a)))
+                cols = rows
+            a = L.UnitGatherArgs(means=_p(self.weight3), lvars=None, bias=None, O=self.n_classes, I=self.sizes[-1], rows=None,
+                                 n_rows=self.n_classes, cols=_p(cols), n_cols=new.sizes[-1], dst_means=_p(new.weight3),
+                                 dst_lvars=None, dst_bias=None)
+            L.check(lib.vbnn_unit_gather(new.ctx.h, C.byref(a)))
+            a = L.UnitGatherArgs(means=_p(self.bias3), lvars=None, bias=None, O=1, I=self.n_classes, rows=None, n_rows=1, cols=None,
+                                 n_cols=self.n_classes, dst_means=_p(new.bias3), dst_lvars=None, dst_bias=None)     # (a plain copy)
+            L.check(lib.vbnn_unit_gather(new.ctx.h, C.byref(a)))
+            new.draw = self.draw
+            if new._draw_dev is not None:      # the new engine's device counter starts at zero: advance it to the mirror
+                L.check(lib.vbnn_sample(new.ctx.h, _p(new._draw_dev), self.draw))
+        new.prepare()
+        return new
+
+    def prune_units_curve(self, inputs, targets, fractions, S=None, map=False, scope="global", multiple=1):
+        """What unit pruning costs: for every fraction q a prune_units(fraction=q, scope=scope, multiple=multiple), the compact
+        engine and its predict(inputs, S, targets, map). One dict per fraction: fraction, tau (per layer), hidden, n_weights,
+        nll, accuracy, mean_draw_nll, mean_draw_accuracy, mutual_info (mean over rows). Every compact engine starts from THIS
+        engine's draw counter, which does not move: the points see the same draws (addressed by their own unit indices)."""
+        rows = []
+        for q in fractions:
+            res = self.prune_units(fraction=q, scope=scope, multiple=multiple)
+            p = self.compact(res).predict(inputs, S=S, targets=targets, map=map)
+            rows.append(dict(fraction=float(q), tau=res.tau, hidden=res.hidden, n_weights=res.n_weights, nll=p.nll,
+                             accuracy=p.accuracy, mean_draw_nll=p.mean_draw_nll, mean_draw_accuracy=p.mean_draw_accuracy,
+                             mutual_info=float(p.mutual_info.mean().item())))
+        return rows
 
     # ---- signal-to-noise pruning (mainviz.lua:20-27) and the pruned view of predict(). Nothing of the training step is
     # touched: the pruned operands are shadows of their own (PruneResult), read by predict() alone while the view is set.

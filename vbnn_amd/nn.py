@@ -585,6 +585,14 @@ class VBLinear(Linear):
         L.check(L.lib().vbnn_snr(self.ctx.h, _p(self.means), _p(self.lvars), self.W, _p(out)))
         return out
 
+    def unit_snr(self):
+        """||means[o, :]|| / ||sigma[o, :]|| per output unit (O floats): the key of structured pruning (FusedMLP.prune_units)."""
+        out = torch.empty(self.means.shape[0], dtype=torch.float32, device=self.means.device)
+        d = (L.UnitDesc * 1)(L.UnitDesc(means=_p(self.means), lvars=_p(self.lvars), O=self.means.shape[0], I=self.means.shape[1],
+                                        key=_p(out), keep=None, n_keep=None))
+        L.check(L.lib().vbnn_unit_snr(self.ctx.h, 1, d))
+        return out
+
     # -- VBLinear.lua:124-166: SGD on bias, compute_prior, likelihood + KL gradients, optim.adam on means (meanState)
     # and lvars (varState). Returns (mu_normratio, var_normratio), the two ratios the reference logs (:139,144);
     # its other twelve Log:add statistics (:149-164) are host-side logging and are not reproduced.
