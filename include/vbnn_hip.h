@@ -397,6 +397,34 @@ typedef struct vbnn_update_desc {
 } vbnn_update_desc;
 int vbnn_update(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_update_desc* layers, const vbnn_pack_desc* extra);
 
+/* ---- training under a held pruning mask (additive, ABI 6): the two parameter sweeps and the KL sum of the network that
+ * signal-to-noise pruning (below) leaves. The reference only counts what would go (mainviz.lua:20-27); it never trains on what
+ * is left. A mask is the byte tensor vbnn_prune_pack writes: O x I uint8_t, non-zero = pruned. `masks` is a HOST array of
+ * n_layers device pointers, a NULL entry = that layer is unmasked; masks == NULL or every entry NULL: the call IS vbnn_prepare /
+ * vbnn_update. The forward and both backward GEMMs read the operand shadows only, so with +0 in a pruned weight's shadow entries
+ * every GEMM of the step computes the pruned network; nothing else of the step changes. Per weight of a masked layer:
+ *   kept (mask 0)    exactly the arithmetic of vbnn_prepare / vbnn_update (one kernel definition, a template flag);
+ *   pruned           means, lvars and the four Adam moments keep their bits (the weight is frozen, not zeroed: dropping the mask
+ *                    brings it back); mu_s, var_s and, where asked for, muT_s, varT_s receive +0; it enters none of the sums,
+ *                    none of the 14 logged series, no min / max. Its values never reach the arithmetic; where the unmasked sweep
+ *                    loads four weights as one 16-byte vector, a group with at least one kept weight is still loaded whole and
+ *                    the pruned lanes are dropped, a group without one is not loaded. Stores touch kept weights only.
+ * Statistics of a masked layer: stats[0] = sum over KEPT of (exp(lvars) + means^2), stats[1] = sum over kept of lvars, stats[3] =
+ * n_kept (where W stands), stats[2] = stats[0] / n_kept: the prior variance of the network that exists, which is what the KL term of
+ * the accGradParameters epilogue, kl_add and vbnn_calc_lc_masked then read. log14's means and unbiased std divide by n_kept. n_kept
+ * is counted in the sweep (integer-valued doubles in the fixed partial order: two runs give the same bits). A mask that prunes
+ * NOTHING gives the unmasked call's bits in every output (stats[2] then as vbnn_prepare forms it, (1 / W) x stats[0]); a layer
+ * with no kept weight gets stats[0..3] = 0, +0 shadows and no log14. The bias step, `extra` and the Adam step sizes are untouched.
+ * vbnn_update_masked: `stats` must hold the MASKED statistics of the pre-update parameters on entry. */
+int vbnn_prepare_masked(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prep_desc* layers,
+                        const uint8_t* const* masks, const vbnn_pack_desc* extra);
+int vbnn_update_masked(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_update_desc* layers,
+                       const uint8_t* const* masks, const vbnn_pack_desc* extra);
+/* vbnn_calc_lc (from means / lvars, no caches) with the pruned weights left out of the sum and written as 0 in lc_elem; `stats`
+ * as the masked sweeps leave them. mask == NULL: vbnn_calc_lc. */
+int vbnn_calc_lc_masked(vbnn_ctx* ctx, const float* means, const float* lvars, const uint8_t* mask,
+                        const double* stats, float B, float* lc_elem, double* lc_sum_dev, int64_t W);
+
 /* ---- data-parallel exchange (north_star: "RCCL all-reduce over xGMI on the (mu, log sigma^2) gradients after
  * accGradParameters"; the reference itself is single-device, main.lua:142 sets BLAS threads only) ------------------
  * One process per GPU, one communicator per process. Rank 0 calls vbnn_comm_unique_id and the HOST side hands the

@@ -171,7 +171,8 @@ function FusedMLP:prepare()
     local w3 = ffi.new('vbnn_pack_desc[1]')
     w3[0].src, w3[0].rows, w3[0].cols, w3[0].ld_src = f32(self.weight3), self.n_classes, self.sizes[#self.sizes], self.sizes[#self.sizes]
     w3[0].dst, w3[0].ld_dst, w3[0].dstT, w3[0].ld_dstT = self.w3_s.p, self.w3_s.ld, nil, 0
-    check(C.vbnn_prepare(vb.ctx, self.dtype, n, d, w3))
+    if self.held then check(C.vbnn_prepare_masked(vb.ctx, self.dtype, n, d, self.held, w3))   -- a held pruning mask (:hold_pruned)
+    else check(C.vbnn_prepare(vb.ctx, self.dtype, n, d, w3)) end
 end
 
 function FusedMLP:sample()                                        -- mlp.lua:69-74: LRT draws its noise in the forward epilogue
@@ -417,15 +418,21 @@ function FusedMLP:update(opt, log14)
     local w3 = ffi.new('vbnn_pack_desc[1]')
     w3[0].src, w3[0].rows, w3[0].cols, w3[0].ld_src = f32(self.weight3), self.n_classes, H, H
     w3[0].dst, w3[0].ld_dst, w3[0].dstT, w3[0].ld_dstT = self.w3_s.p, self.w3_s.ld, nil, 0
-    check(C.vbnn_update(vb.ctx, self.dtype, n, d, w3))
+    if self.held then check(C.vbnn_update_masked(vb.ctx, self.dtype, n, d, self.held, w3))    -- the frozen weights keep every bit
+    else check(C.vbnn_update(vb.ctx, self.dtype, n, d, w3)) end
 end
 
 -- mlp:calc_lc (mlp.lua:109-115): sum over the VB layers of VBLinear:calc_lc (VBLinear.lua:99-103), fresh statistics
 function FusedMLP:calc_lc(opt)
     local lc, box, dev = 0, ffi.new('double[1]'), vb.alloc(8)
-    for _, v in ipairs(self.vb) do
-        check(C.vbnn_calc_lc(vb.ctx, f32(v.means), f32(v.lvars), nil, nil, ffi.cast('double*', v.stats), (opt or self.opt).B, nil,
-                             ffi.cast('double*', dev), v.O * v.I))
+    for li, v in ipairs(self.vb) do
+        if self.held then                                           -- the KL of the network that exists: the kept weights' sum
+            check(C.vbnn_calc_lc_masked(vb.ctx, f32(v.means), f32(v.lvars), self.held[li - 1], ffi.cast('double*', v.stats),
+                                        (opt or self.opt).B, nil, ffi.cast('double*', dev), v.O * v.I))
+        else
+            check(C.vbnn_calc_lc(vb.ctx, f32(v.means), f32(v.lvars), nil, nil, ffi.cast('double*', v.stats), (opt or self.opt).B, nil,
+                                 ffi.cast('double*', dev), v.O * v.I))
+        end
         check(C.vbnn_buf_download(vb.ctx, box, dev, 8))
         lc = lc + box[0]
     end
@@ -450,6 +457,7 @@ end
 -- n_weights_before. :compact(result) builds the smaller network.
 function FusedMLP:prune_units(fraction, threshold, scope, multiple)
     assert((fraction == nil) ~= (threshold == nil), 'prune_units: exactly one of fraction and threshold')
+    assert(not self.held, 'prune_units: a pruning mask is held (:release_pruned first)')
     scope, multiple = scope or 'global', multiple or 1
     assert(scope == 'global' or scope == 'layer', "prune_units: scope 'global' or 'layer'")
     assert(fraction == nil or (fraction >= 0 and fraction <= 1), 'prune_units: fraction in 0 .. 1')
@@ -610,12 +618,52 @@ function FusedMLP:use_pruned(result)
     self.pruned_view = result
 end
 
+-- Training the network a pruning leaves (engine.py:FusedMLP.hold_pruned, tools/c_host.c:fm_hold_pruned): the weights `result` (a
+-- table from :prune, of the current version) prunes are out of the network AND frozen from now on -- :prepare / :update / :calc_lc
+-- take the masked entry points (+0 in the shadows, parameters and Adam moments untouched, the kept weights' prior statistics); :run
+-- is unchanged. The byte masks come from one more vbnn_prune_pack per layer at the result's own tau. Returns the held counts per
+-- layer. One pruning at a time here: the library has no call that ORs two masks, so an iterative schedule (hold, train, prune
+-- again, hold the union) is the Python engine's; :release_pruned first. Not with the sharded update; a layer must keep a weight.
+-- :prune_units / :compact / :compress read the fp32 parameters, which still hold the frozen values: release before them.
+function FusedMLP:hold_pruned(result)
+    assert(result and result.owner == self and not result.sparse, 'hold_pruned: a (dense) result of this :prune')
+    assert(result.version == (self.version or 0), 'hold_pruned: the parameters changed since this result was taken')
+    assert(not self.sharded, 'hold_pruned: not with the sharded update')
+    assert(not self.held, 'hold_pruned: a mask is held already (:release_pruned first)')
+    local n = #self.vb
+    -- (bufs owns the masks: vb.alloc's cdata frees its buffer when collected, and neither a cast nor the pointer array keeps it alive)
+    local held, counts, bufs = ffi.new('const uint8_t*[?]', n), {}, {}
+    local stats = vb.alloc(32)
+    for li, v in ipairs(self.vb) do
+        assert(result.layers[li].n_pruned < v.O * v.I, 'hold_pruned: a layer would be left without a kept weight')
+        local mask = vb.alloc(v.O * v.I)
+        local d = ffi.new('vbnn_prune_desc[1]')
+        d[0].means, d[0].lvars, d[0].O, d[0].I = f32(v.means), f32(v.lvars), v.O, v.I
+        d[0].mu_p, d[0].var_p, d[0].ld_w = result.mu_p[li].p, result.var_p[li].p, result.mu_p[li].ld   -- the same sweep: the same bits
+        d[0].stats, d[0].mask = ffi.cast('double*', stats), ffi.cast('uint8_t*', mask)
+        check(C.vbnn_prune_pack(vb.ctx, self.dtype, 1, d, nil, result.tau[li]))
+        held[li - 1], counts[li], bufs[li] = ffi.cast('const uint8_t*', mask), result.layers[li].n_pruned, mask
+    end
+    self.held, self.held_counts, self.held_bufs = held, counts, bufs
+    self.version = (self.version or 0) + 1                          -- shadows and statistics change: earlier results are void
+    self:prepare()
+    return counts
+end
+
+-- drops the held mask and runs the ordinary :prepare: the frozen weights are back with the values they were held with
+function FusedMLP:release_pruned()
+    self.held, self.held_counts, self.held_bufs = nil, nil, nil
+    self.version = (self.version or 0) + 1
+    self:prepare()
+end
+
 -- The compressed form of a :prune result (engine.py:FusedMLP._compress, tools/c_host.c:fm_compress): the kept weights only, CSR per
 -- layer over output rows (include/vbnn_hip.h: vbnn_sparse_desc), built on the device at the result's own tau; the entry count is
 -- W - n_pruned, known from the result. Returns a result :use_pruned takes like any other; under it predict() multiplies by the
 -- entries directly (:_predict_forward_sparse). It owns no dense shadows.
 function FusedMLP:compress(result)
     assert(result and result.owner == self, 'compress: a result of this :prune')
+    assert(not self.held, 'compress: a pruning mask is held (:release_pruned first)')
     assert(result.version == (self.version or 0), 'compress: the parameters changed since this result was taken')
     if result.sparse then return result end
     local n = #self.vb

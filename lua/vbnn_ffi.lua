@@ -146,6 +146,12 @@ typedef struct vbnn_update_desc {
     float kl_add;
 } vbnn_update_desc;
 int vbnn_update(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_update_desc* layers, const vbnn_pack_desc* extra);
+int vbnn_prepare_masked(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prep_desc* layers,
+                        const uint8_t* const* masks, const vbnn_pack_desc* extra);
+int vbnn_update_masked(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_update_desc* layers,
+                       const uint8_t* const* masks, const vbnn_pack_desc* extra);
+int vbnn_calc_lc_masked(vbnn_ctx* ctx, const float* means, const float* lvars, const uint8_t* mask,
+                        const double* stats, float B, float* lc_elem, double* lc_sum_dev, int64_t W);
 typedef struct vbnn_comm vbnn_comm;
 int vbnn_comm_unique_id(void* id_out );
 int vbnn_comm_create(vbnn_ctx* ctx, int rank, int world, const void* id, vbnn_comm** out);

@@ -13,7 +13,7 @@
  * vbnn_amd/engine.py:FusedMLP on the same configuration.
  *
  *   c_host --dtype f32|bf16 --input 784 --hidden 400,400 --classes 10 --batch 256 [--S 1] [--steps 2] [--update]
- *          [--comm [--sharded]] [--graph] [--kl-shadows] [--seed 3] --out arena.bin
+ *          [--comm [--sharded]] [--graph] [--kl-shadows] [--hold Q] [--seed 3] --out arena.bin
  *          [--predict S [--predict-rows 32768] [--predict-stacked -1|0|1] [--prune Q | --prune-threshold T [--sparse]]
  *                       [--prune-units Q [--unit-multiple M]]]
  *   --predict S: after the steps, the posterior predictive of the minibatch over S draws (fm_predict), appended to the file:
@@ -29,6 +29,9 @@
  *   the predictive of THAT network, appended: int32 layers, float tau, per layer int32 kept count, per layer the kept list (int32),
  *   per layer the compact means, lvars (O' x I' floats each) and bias (O'), the compact final weight (C x H') and bias (C), then a
  *   second predict block as above (S more draws of the compact network's own counter).
+ *   --hold Q: before step 0 the fraction Q of all VB weights is pruned by signal-to-noise (fm_prune, with byte masks) and the mask
+ *   is HELD through the steps (engine.py:FusedMLP.hold_pruned): vbnn_prepare_masked rewrites shadows and statistics, every update
+ *   is vbnn_update_masked -- the pruned weights stay out of the network and keep their parameter bits. The file is unchanged.
  *   --graph: the context gets a stream of its own (vbnn_ctx_create_cu_budget), the draw counter lives on the device
  *   (vbnn_fwd_args.draw_dev, vbnn_sample), step 2 is CAPTURED (vbnn_capture_begin / _end) and steps 2.. are replays of it.
  *   arena.bin: int64 n_grads, double loss, int32 correct, int32 flags, then n_grads floats (the arena after the last
@@ -120,6 +123,8 @@ typedef struct {
     const packed_t *view_mu, *view_var;   /* the pruned view (fm_prune): per layer, read by fm_predict_forward in place of mu_s / var_s; NULL: none */
     struct sparse_out* sparse;            /* the compressed pruned view (fm_compress): fm_predict_forward then runs fm_predict_forward_sparse; NULL: none */
     int64_t pred_rows;                    /* operand rows of fm_predict's buffers (the K-major buffers of the sparse forward match them) */
+    const uint8_t* held[MAX_LAYERS];      /* --hold: the held pruning masks (O x I bytes per layer, 1 = pruned and frozen), read by */
+    int holding;                          /* fm_prepare / fm_update while `holding` is set */
 } fused_mlp;
 
 /* ---- FusedMLP.new (lua/FusedMLP.lua; engine.py:FusedMLP.__init__ + init_parameters) */
@@ -272,7 +277,8 @@ static void fm_prepare(fused_mlp* m) {
     const int64_t H = m->sizes[m->n_layers];
     w3.src = m->weight3; w3.rows = m->n_classes; w3.cols = H; w3.ld_src = H;
     w3.dst = m->w3_s.p; w3.ld_dst = m->w3_s.ld; w3.dstT = NULL; w3.ld_dstT = 0;
-    CHECK(vbnn_prepare(g_ctx, m->dtype, m->n_layers, d, &w3));
+    if (m->holding) CHECK(vbnn_prepare_masked(g_ctx, m->dtype, m->n_layers, d, m->held, &w3));
+    else CHECK(vbnn_prepare(g_ctx, m->dtype, m->n_layers, d, &w3));
 }
 
 static void fm_sample(fused_mlp* m) {                          /* mlp.lua:69-74: LRT draws its noise in the forward epilogue */
@@ -516,7 +522,8 @@ static void fm_update(fused_mlp* m, float lr, float lr_mu, float lr_lv) {
     memset(&w3, 0, sizeof w3);
     w3.src = m->weight3; w3.rows = m->n_classes; w3.cols = H; w3.ld_src = H;
     w3.dst = m->w3_s.p; w3.ld_dst = m->w3_s.ld; w3.dstT = NULL; w3.ld_dstT = 0;
-    CHECK(vbnn_update(g_ctx, m->dtype, m->n_layers, d, &w3));
+    if (m->holding) CHECK(vbnn_update_masked(g_ctx, m->dtype, m->n_layers, d, m->held, &w3));
+    else CHECK(vbnn_update(g_ctx, m->dtype, m->n_layers, d, &w3));
 }
 
 /* error (mean NLL over the GLOBAL batch, this rank's share) and hit count of the last run(s); synchronises */
@@ -608,9 +615,10 @@ typedef struct {
     packed_t mu_p[MAX_LAYERS], var_p[MAX_LAYERS];
     float tau;
     double stats[MAX_LAYERS][4];                                           /* per layer: pruned, sum of pruned vars, sum of vars, W */
+    uint8_t* mask[MAX_LAYERS];                                             /* with_mask: the `pruned` tensors (mainviz.lua:21), O x I bytes */
 } prune_out;
 
-static void fm_prune(fused_mlp* m, double fraction, float threshold, prune_out* o) {
+static void fm_prune(fused_mlp* m, double fraction, float threshold, prune_out* o, int with_mask) {
     const int n = m->n_layers;
     vbnn_prune_desc d[MAX_LAYERS];
     double* stats = (double*)dev_alloc((size_t)n * 4 * 8);
@@ -622,7 +630,8 @@ static void fm_prune(fused_mlp* m, double fraction, float threshold, prune_out* 
         o->mu_p[li] = packed(v->O, v->I, m->esize); o->var_p[li] = packed(v->O, v->I, m->esize);
         d[li].means = v->means; d[li].lvars = v->lvars; d[li].O = v->O; d[li].I = v->I;
         d[li].mu_p = o->mu_p[li].p; d[li].var_p = o->var_p[li].p; d[li].ld_w = o->mu_p[li].ld;
-        d[li].stats = stats + 4 * li; d[li].mask = NULL;
+        o->mask[li] = with_mask ? (uint8_t*)dev_alloc((size_t)(v->O * v->I)) : NULL;
+        d[li].stats = stats + 4 * li; d[li].mask = o->mask[li];
         W += v->O * v->I;
     }
     size_t nbytes = 0;
@@ -638,6 +647,17 @@ static void fm_prune(fused_mlp* m, double fraction, float threshold, prune_out* 
     CHECK(vbnn_prune_pack(g_ctx, m->dtype, n, d, tau_dev, o->tau));
     CHECK(vbnn_buf_download(g_ctx, o->stats, stats, (size_t)n * 4 * 8));
     if (tau_dev) CHECK(vbnn_buf_download(g_ctx, &o->tau, tau, 4));
+}
+/* engine.py:FusedMLP.hold_pruned: the pruning's masks held through training -- fm_prepare / fm_update take the masked entry points
+   from here on; the masked prepare rewrites shadows and statistics now. A layer must keep at least one weight. */
+static void fm_hold_pruned(fused_mlp* m, const prune_out* o) {
+    if (m->sharded) { fprintf(stderr, "c_host: --hold: not with the sharded update\n"); exit(1); }
+    for (int li = 0; li < m->n_layers; ++li) {
+        if (o->stats[li][0] >= o->stats[li][3]) { fprintf(stderr, "c_host: --hold: layer %d would be left without a kept weight\n", li); exit(1); }
+        m->held[li] = o->mask[li];
+    }
+    m->holding = 1;
+    fm_prepare(m);
 }
 static void fm_use_pruned(fused_mlp* m, const prune_out* o) {
     m->view_mu = o ? o->mu_p : NULL; m->view_var = o ? o->var_p : NULL;
@@ -821,7 +841,7 @@ static int arg_flag(int argc, char** argv, const char* name) {
 int main(int argc, char** argv) {
     const char* out_path = arg_value(argc, argv, "--out", NULL);
     if (!out_path) {
-        fprintf(stderr, "usage: c_host --dtype f32|bf16 --input I --hidden h1,h2 --classes C --batch N [--S s] [--steps k] [--update] [--comm] --out file\n");
+        fprintf(stderr, "usage: c_host --dtype f32|bf16 --input I --hidden h1,h2 --classes C --batch N [--S s] [--steps k] [--update] [--comm] [--hold Q] --out file\n");
         return 1;
     }
     if (vbnn_abi_version() != VBNN_ABI_VERSION) { fprintf(stderr, "c_host: header / library ABI mismatch\n"); return 2; }
@@ -858,6 +878,15 @@ int main(int argc, char** argv) {
         net.stat_parts = (double*)dev_alloc((size_t)net.world * n_layers * 4 * 8);
     }    /* A/B: the KL gradient fused into the accGradParameters epilogue, from the bf16 shadows */
     if (with_graph) net.draw_dev = (uint32_t*)dev_alloc(4);
+    const char* hold_q = arg_value(argc, argv, "--hold", NULL);
+    static prune_out held;
+    if (hold_q) {                                                /* select, pack with a mask, masked prepare: before step 0 */
+        fm_prune(&net, atof(hold_q), 0.f, &held, 1);
+        fm_hold_pruned(&net, &held);
+        double np = 0;
+        for (int li = 0; li < n_layers; ++li) np += held.stats[li][0];
+        printf("c_host: holding %.0f pruned weights (snr below %.9g) through the steps\n", np, (double)held.tau);
+    }
 
     /* the synthetic minibatch of the parity tests: x ~ N(0,1) from the Philox contract (stream DATA), targets by row */
     float* x = (float*)dev_alloc((size_t)N * sizes[0] * 4);
@@ -953,7 +982,7 @@ int main(int argc, char** argv) {
             for (int li = 0; li < n_layers; ++li) printf("-%d", un.n_keep[li]);
             printf("-%d\n", n_classes);
         } else if (pass == 1) {
-            fm_prune(&net, prune_q ? atof(prune_q) : -1.0, prune_t ? (float)atof(prune_t) : 0.f, &pr);
+            fm_prune(&net, prune_q ? atof(prune_q) : -1.0, prune_t ? (float)atof(prune_t) : 0.f, &pr, 0);
             fm_use_pruned(&net, &pr);
             if (arg_flag(argc, argv, "--sparse")) {               /* the same pruning, compressed: predict multiplies by the entries */
                 fm_compress(&net, &pr, &sp);

@@ -166,6 +166,9 @@ _SIGS = {
     "vbnn_adam_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i64, _vp], _i),
     "vbnn_sgd_step": ([_vp, _vp, _vp, _i64, _f], _i),
     "vbnn_update": ([_vp, _i, _i, _vp, _vp], _i),
+    "vbnn_prepare_masked": ([_vp, _i, _i, _vp, _vp, _vp], _i),
+    "vbnn_update_masked": ([_vp, _i, _i, _vp, _vp, _vp], _i),
+    "vbnn_calc_lc_masked": ([_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i64], _i),
     "vbnn_comm_unique_id": ([_vp], _i),
     "vbnn_comm_create": ([_vp, _i, _i, _vp, C.POINTER(_vp)], _i),
     "vbnn_comm_destroy": ([_vp], _i),

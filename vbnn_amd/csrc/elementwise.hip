@@ -134,6 +134,57 @@ __device__ __forceinline__ void prior_finish(const double* partial, int nblocks,
     const double r2 = block_sum(s2, sh);
     if (threadIdx.x == 0) { stats[0] = r1; stats[1] = r2; stats[2] = (1.0 / (double)W) * r1; stats[3] = (double)W; }
 }
+// ---- a held pruning mask in the parameter sweeps (vbnn_prepare_masked / vbnn_update_masked): O x I bytes, non-zero = pruned.
+// The mask bytes of four consecutive weights as one word, byte e = weight e (bytes past `valid` read as kept). Read once: nontemporal.
+__device__ __forceinline__ uint32_t mask_word4(const uint8_t* p, int valid, bool vec) {
+    if (vec && valid == 4) return __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p));
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < valid) w |= (uint32_t)__builtin_nontemporal_load(p + j) << (8 * j);
+    return w;
+}
+// bit e set: weight e of the group exists (e < valid) and is kept
+__device__ __forceinline__ int keep_bits4(uint32_t w, int valid) {
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < valid && ((w >> (8 * j)) & 0xffu) == 0) k |= 1 << j;
+    return k;
+}
+// the four values of a group of which only the kept ones may be touched, one by one. NT: the stream is the update sweep's own
+// (VBNN_NT_UPDATE) and keeps its nontemporal treatment weight by weight; the prepare sweep's loads are plain, as its vectors are.
+template <bool NT>
+__device__ __forceinline__ void load4_kept(const float* p, float (&v)[4], int keep) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = ((keep >> j) & 1) ? (NT ? __builtin_nontemporal_load(p + j) : p[j]) : 0.f;
+}
+template <bool NT>
+__device__ __forceinline__ void store4_kept(float* p, const float (&v)[4], int keep) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if ((keep >> j) & 1) {
+            if (NT) __builtin_nontemporal_store(v[j], p + j);
+            else p[j] = v[j];
+        }
+}
+// scratch of the masked sweeps' kept counts: behind the partial sums of all eight layers (8 x 2048 x UPD_NSUM doubles at most)
+constexpr size_t MASK_CNT_BASE = (size_t)8 * 2048 * 16, MASK_CNT_STRIDE = 2048;
+// The statistics of a masked layer: the sums run over the kept weights, n_kept stands where W stands, var_hat is the kept
+// network's. n_kept is a sum of integer-valued doubles: exact, whatever the order. A mask that prunes nothing leaves the
+// unmasked sweep's bits, var_hat included (which that sweep forms as (1 / W) x sum); no kept weight: four zeros.
+__device__ __forceinline__ void masked_stats(double r1, double r2, double n, int64_t W, double* stats) {
+    if (n == 0.0) { stats[0] = 0.0; stats[1] = 0.0; stats[2] = 0.0; stats[3] = 0.0; return; }
+    stats[0] = r1; stats[1] = r2; stats[2] = (n == (double)W) ? (1.0 / (double)W) * r1 : r1 / n; stats[3] = n;
+}
+__device__ __forceinline__ void prior_finish_masked(const double* partial, const double* cnt, int nblocks, int64_t W, double* stats, double* sh) {
+    double s1 = 0.0, s2 = 0.0, c = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 256) { s1 += partial[b * 2]; s2 += partial[b * 2 + 1]; c += cnt[b]; }
+    const double r1 = block_sum(s1, sh);
+    const double r2 = block_sum(s2, sh);
+    const double n = block_sum(c, sh);
+    if (threadIdx.x == 0) masked_stats(r1, r2, n, W, stats);
+}
 __global__ __launch_bounds__(256) void k_prior_finish(const double* partial, int nblocks, int64_t W, double* stats) {
     __shared__ double sh[4];
     prior_finish(partial, nblocks, W, stats, sh);
@@ -317,10 +368,13 @@ extern "C" int vbnn_compute_vargrads(vbnn_ctx* ctx, const float* lvars, const fl
 
 // ---------------------------------------------------------------------------------- calc_lc
 // VBLinear.lua:99-103 + mlp.lua:112 (:sum()).
+// MASKED (vbnn_calc_lc_masked): a weight whose mask byte is set is left out of the sum and written as 0; its parameters are
+// not read. The mask is read once: nontemporally.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_lc_partial(const float* __restrict__ means, const float* __restrict__ lvars,
                                                     const float* __restrict__ vars, const float* __restrict__ mu_sqe,
                                                     const double* __restrict__ stats, float B, float* lc_elem, int64_t W,
-                                                    double* partial) {
+                                                    double* partial, const uint8_t* __restrict__ mask) {
     __shared__ double sh[4];
     const double var_hat = stats[2];
     const float lvh = (float)log(sqrt(var_hat));
@@ -328,6 +382,12 @@ __global__ __launch_bounds__(256) void k_lc_partial(const float* __restrict__ me
     const float invB = 1.0f / B;
     double s = 0.0;
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < W; t += (int64_t)gridDim.x * 256) {
+        if constexpr (MASKED) {
+            if (__builtin_nontemporal_load(mask + t)) {
+                if (lc_elem) lc_elem[t] = 0.f;
+                continue;
+            }
+        }
         const float v = vars ? vars[t] : expf(lvars[t]);
         const float q = mu_sqe ? mu_sqe[t] : means[t] * means[t];
         const float first = -logf(sqrtf(v)) + lvh;
@@ -355,9 +415,26 @@ extern "C" int vbnn_calc_lc(vbnn_ctx* ctx, const float* means, const float* lvar
     VBNN_REQUIRE(W > 0 && B > 0, "W, B");
     const int nb = grid_for(W, 1024);
     VBNN_REQUIRE((size_t)nb <= ctx->scratch_doubles, "scratch");
-    hipLaunchKernelGGL(k_lc_partial, dim3(nb), dim3(256), 0, ctx->stream, means, lvars, vars, mu_sqe, stats, B, lc_elem, W, ctx->scratch);
+    hipLaunchKernelGGL(k_lc_partial<false>, dim3(nb), dim3(256), 0, ctx->stream, means, lvars, vars, mu_sqe, stats, B, lc_elem, W, ctx->scratch,
+                       (const uint8_t*)nullptr);
     hipLaunchKernelGGL(k_sum_finish, dim3(1), dim3(256), 0, ctx->stream, ctx->scratch, nb, lc_sum_dev);
     return vbnn_check_launch("k_lc");
+    VBNN_API_END
+}
+// calc_lc of the network a held pruning mask leaves: `stats` are the masked statistics (vbnn_prepare_masked / vbnn_update_masked),
+// so var_hat is the kept weights' own.
+extern "C" int vbnn_calc_lc_masked(vbnn_ctx* ctx, const float* means, const float* lvars, const uint8_t* mask, const double* stats,
+                                   float B, float* lc_elem, double* lc_sum_dev, int64_t W) {
+    if (!mask) return vbnn_calc_lc(ctx, means, lvars, nullptr, nullptr, stats, B, lc_elem, lc_sum_dev, W);
+    VBNN_API_BEGIN
+    VBNN_REQUIRE(ctx && means && lvars && stats && lc_sum_dev, "null argument");
+    VBNN_REQUIRE(W > 0 && B > 0, "W, B");
+    const int nb = grid_for(W, 1024);
+    VBNN_REQUIRE((size_t)nb <= ctx->scratch_doubles, "scratch");
+    hipLaunchKernelGGL(k_lc_partial<true>, dim3(nb), dim3(256), 0, ctx->stream, means, lvars, (const float*)nullptr, (const float*)nullptr,
+                       stats, B, lc_elem, W, ctx->scratch, mask);
+    hipLaunchKernelGGL(k_sum_finish, dim3(1), dim3(256), 0, ctx->stream, ctx->scratch, nb, lc_sum_dev);
+    return vbnn_check_launch("k_lc_masked");
     VBNN_API_END
 }
 
@@ -637,10 +714,14 @@ extern "C" int vbnn_logsoftmax_backward(vbnn_ctx* ctx, const float* out, const f
 // The per-step parameter sweep of the fused path: ONE read of means/lvars (8 B per weight) produces
 //   - the GEMM shadows mu, sigma^2 = exp(lvars) (and their transposes for the gradInput GEMM),
 //   - the prior statistics of VBLinear:compute_prior (VBLinear.lua:77-88) as block partials.
-template <typename T>
+// MASKED (vbnn_prepare_masked): a pruned weight's parameters take no part -- +0 in all four shadows, nothing in the sums; a
+// group of four with no kept weight is not loaded at all, a mixed group is loaded whole when it is a 16-byte vector and the
+// pruned lanes are dropped. Kept weights go through the very statements of the unmasked instantiation.
+template <typename T, bool MASKED>
 __global__ __launch_bounds__(256) void k_prep_layer(const float* __restrict__ means, const float* __restrict__ lvars,
                                                     int64_t O, int64_t I, T* mu_s, T* var_s, int64_t ld_w, T* muT_s, T* varT_s,
-                                                    int64_t ld_wT, double* partial) {
+                                                    int64_t ld_wT, double* partial, const uint8_t* __restrict__ mask,
+                                                    double* cnt_partial) {
     __shared__ float tm[64][65];
     __shared__ float tv[64][65];
     __shared__ double sh[4];
@@ -653,22 +734,36 @@ __global__ __launch_bounds__(256) void k_prep_layer(const float* __restrict__ me
     // the shadows, and -- after the LDS transpose -- 4 consecutive rows of one column for the transposed shadows
     const bool vec_in = ((I & 3) == 0) && ((((uintptr_t)means | (uintptr_t)lvars) & 15u) == 0);
     const bool vec_t = muT_s && ((ld_wT & 3) == 0);
+    const bool vec_m = MASKED && vec_in && (((uintptr_t)mask & 3u) == 0);
+    double nk = 0.0;          // MASKED: kept weights seen by this thread
+    (void)vec_m; (void)nk;
     if (!muT_s && vec_in && (int64_t)gridDim.x * 1024 <= O * I) {
         // FLAT form (no transposed shadows to build), as k_vb_update's: a wave-instruction is one contiguous KiB of means / lvars
         const int64_t total = O * I;
         for (int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; base < total; base += (int64_t)gridDim.x * 1024) {
             const int64_t r = base / I, c = base - r * I;
             float m[4], l[4], v[4];
-            load4<float>(means + base, m, 4, true);
-            load4<float>(lvars + base, l, 4, true);
+            int keep = 15;
+            if constexpr (MASKED) { keep = keep_bits4(mask_word4(mask + base, 4, vec_m), 4); nk += (double)__popc(keep); }
+            if (!MASKED || keep != 0) {
+                load4<float>(means + base, m, 4, true);
+                load4<float>(lvars + base, l, 4, true);
+            }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { v[e] = expf(l[e]); s1 += (double)__fadd_rn(v[e], __fmul_rn(m[e], m[e])); s2 += (double)l[e]; }
+            for (int e = 0; e < 4; ++e) {
+                if (!MASKED || ((keep >> e) & 1)) { v[e] = expf(l[e]); s1 += (double)__fadd_rn(v[e], __fmul_rn(m[e], m[e])); s2 += (double)l[e]; }
+                else { m[e] = 0.f; v[e] = 0.f; }
+            }
             store4<T>(mu_s + r * ld_w + c, m[0], m[1], m[2], m[3], 4, true);
             store4<T>(var_s + r * ld_w + c, v[0], v[1], v[2], v[3], 4, true);
         }
         const double r1 = block_sum(s1, sh);
         const double r2 = block_sum(s2, sh);
         if (threadIdx.x == 0) { partial[blockIdx.x * 2] = r1; partial[blockIdx.x * 2 + 1] = r2; }
+        if constexpr (MASKED) {
+            const double rn = block_sum(nk, sh);
+            if (threadIdx.x == 0) cnt_partial[blockIdx.x] = rn;
+        }
         return;
     }
     for (int64_t tI = blockIdx.x; tI < ntiles; tI += gridDim.x) {
@@ -681,13 +776,22 @@ __global__ __launch_bounds__(256) void k_prep_layer(const float* __restrict__ me
             float m[4] = {0.f, 0.f, 0.f, 0.f}, l[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f};
             const int valid = (r < O) ? (int)min((int64_t)4, I - c) : 0;
             if (valid > 0) {
-                load4<float>(means + r * I + c, m, valid, vec_in);
-                load4<float>(lvars + r * I + c, l, valid, vec_in);
+                int keep = (1 << valid) - 1;
+                if constexpr (MASKED) { keep = keep_bits4(mask_word4(mask + r * I + c, valid, vec_m), valid); nk += (double)__popc(keep); }
+                if (!MASKED || (vec_in && valid == 4 && keep != 0)) {
+                    load4<float>(means + r * I + c, m, valid, vec_in);
+                    load4<float>(lvars + r * I + c, l, valid, vec_in);
+                } else if (keep != 0) {
+                    load4_kept<false>(means + r * I + c, m, keep);
+                    load4_kept<false>(lvars + r * I + c, l, keep);
+                }
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
+                for (int e = 0; e < 4; ++e) {
                     // (vars + mu_sqe as the fp32 tensors of VBLinear.lua:82-86: the square and the sum rounded separately, whatever
                     // the compiler would contract -- the update sweep forms the same terms in another order of elements)
-                    if (e < valid) { v[e] = expf(l[e]); s1 += (double)__fadd_rn(v[e], __fmul_rn(m[e], m[e])); s2 += (double)l[e]; }
+                    if ((keep >> e) & 1) { v[e] = expf(l[e]); s1 += (double)__fadd_rn(v[e], __fmul_rn(m[e], m[e])); s2 += (double)l[e]; }
+                    else if (MASKED) { m[e] = 0.f; v[e] = 0.f; }
+                }
                 store4<T>(mu_s + r * ld_w + c, m[0], m[1], m[2], m[3], valid, true);
                 store4<T>(var_s + r * ld_w + c, v[0], v[1], v[2], v[3], valid, true);
             }
@@ -713,6 +817,10 @@ __global__ __launch_bounds__(256) void k_prep_layer(const float* __restrict__ me
     const double r1 = block_sum(s1, sh);
     const double r2 = block_sum(s2, sh);
     if (threadIdx.x == 0) { partial[blockIdx.x * 2] = r1; partial[blockIdx.x * 2 + 1] = r2; }
+    if constexpr (MASKED) {
+        const double rn = block_sum(nk, sh);
+        if (threadIdx.x == 0) cnt_partial[blockIdx.x] = rn;
+    }
 }
 
 extern "C" int vbnn_prep_layer(vbnn_ctx* ctx, int dtype, const float* means, const float* lvars, int64_t O, int64_t I,
@@ -726,11 +834,11 @@ extern "C" int vbnn_prep_layer(vbnn_ctx* ctx, int dtype, const float* means, con
     const int nb = (int)(ntiles < 2048 ? ntiles : 2048);
     VBNN_REQUIRE((size_t)nb * 2 <= ctx->scratch_doubles, "scratch");
     if (dtype == VBNN_F32)
-        hipLaunchKernelGGL(k_prep_layer<float>, dim3(nb), dim3(256), 0, ctx->stream, means, lvars, O, I, (float*)mu_s,
-                           (float*)var_s, ld_w, (float*)muT_s, (float*)varT_s, ld_wT, ctx->scratch);
+        hipLaunchKernelGGL((k_prep_layer<float, false>), dim3(nb), dim3(256), 0, ctx->stream, means, lvars, O, I, (float*)mu_s,
+                           (float*)var_s, ld_w, (float*)muT_s, (float*)varT_s, ld_wT, ctx->scratch, (const uint8_t*)nullptr, (double*)nullptr);
     else if (dtype == VBNN_BF16)
-        hipLaunchKernelGGL(k_prep_layer<bf16_t>, dim3(nb), dim3(256), 0, ctx->stream, means, lvars, O, I, (bf16_t*)mu_s,
-                           (bf16_t*)var_s, ld_w, (bf16_t*)muT_s, (bf16_t*)varT_s, ld_wT, ctx->scratch);
+        hipLaunchKernelGGL((k_prep_layer<bf16_t, false>), dim3(nb), dim3(256), 0, ctx->stream, means, lvars, O, I, (bf16_t*)mu_s,
+                           (bf16_t*)var_s, ld_w, (bf16_t*)muT_s, (bf16_t*)varT_s, ld_wT, ctx->scratch, (const uint8_t*)nullptr, (double*)nullptr);
     else { vbnn_set_error("unsupported dtype %d", dtype); return VBNN_ERR_UNSUPPORTED; }
     hipLaunchKernelGGL(k_prior_finish, dim3(1), dim3(256), 0, ctx->stream, ctx->scratch, nb, O * I, stats);
     return vbnn_check_launch("k_prep_layer");
@@ -741,12 +849,19 @@ extern "C" int vbnn_prep_layer(vbnn_ctx* ctx, int dtype, const float* means, con
 // after them copy-pack the extra matrix (and its transpose).
 struct PrepFinishArgs {
     const double* partial[8]; int nb[8]; int64_t W[8]; double* stats[8]; int n;
+    const double* cnt[8];      // masked call: the layer's kept-count partials (NULL: an unmasked layer)
     const float* src; int64_t rows, cols, ld_src; void* dst; int64_t ld_dst; void* dstT; int64_t ld_dstT;
 };
-template <typename T>
+template <typename T, bool MASKED>
 __global__ __launch_bounds__(256) void k_prepare_finish(PrepFinishArgs a) {
     __shared__ double sh[4];
     if ((int)blockIdx.x < a.n) {
+        if constexpr (MASKED) {
+            if (a.cnt[blockIdx.x]) {
+                prior_finish_masked(a.partial[blockIdx.x], a.cnt[blockIdx.x], a.nb[blockIdx.x], a.W[blockIdx.x], a.stats[blockIdx.x], sh);
+                return;
+            }
+        }
         prior_finish(a.partial[blockIdx.x], a.nb[blockIdx.x], a.W[blockIdx.x], a.stats[blockIdx.x], sh);
         return;
     }
@@ -761,7 +876,18 @@ __global__ __launch_bounds__(256) void k_prepare_finish(PrepFinishArgs a) {
     }
 }
 
-extern "C" int vbnn_prepare(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prep_desc* layers, const vbnn_pack_desc* extra) {
+template <typename T>
+static void launch_prep_layer(vbnn_ctx* ctx, int nb, const vbnn_prep_desc& d, double* partial, const uint8_t* mask, double* cnt) {
+    if (mask)
+        hipLaunchKernelGGL((k_prep_layer<T, true>), dim3(nb), dim3(256), 0, ctx->stream, d.means, d.lvars, d.O, d.I, (T*)d.mu_s,
+                           (T*)d.var_s, d.ld_w, (T*)d.muT_s, (T*)d.varT_s, d.ld_wT, partial, mask, cnt);
+    else
+        hipLaunchKernelGGL((k_prep_layer<T, false>), dim3(nb), dim3(256), 0, ctx->stream, d.means, d.lvars, d.O, d.I, (T*)d.mu_s,
+                           (T*)d.var_s, d.ld_w, (T*)d.muT_s, (T*)d.varT_s, d.ld_wT, partial, (const uint8_t*)nullptr, (double*)nullptr);
+}
+// vbnn_prepare and vbnn_prepare_masked: one body. masks == NULL or no entry set: the launches of vbnn_prepare, kernel for kernel.
+static int prepare_impl(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prep_desc* layers, const uint8_t* const* masks,
+                        const vbnn_pack_desc* extra) {
     VBNN_API_BEGIN
     VBNN_REQUIRE(ctx && (layers || n_layers == 0), "null argument");
     VBNN_REQUIRE(n_layers >= 0 && n_layers <= 8, "n_layers (0..8)");
@@ -769,21 +895,22 @@ extern "C" int vbnn_prepare(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_p
     VBNN_REQUIRE((size_t)n_layers * 4096 <= ctx->scratch_doubles, "scratch");
     PrepFinishArgs fa{};
     fa.n = n_layers;
+    bool any_mask = false;
     for (int l = 0; l < n_layers; ++l) {
         const vbnn_prep_desc& d = layers[l];
+        const uint8_t* mask = masks ? masks[l] : nullptr;
+        VBNN_REQUIRE(!mask || MASK_CNT_BASE + 8 * MASK_CNT_STRIDE <= ctx->scratch_doubles, "scratch (kept counts)");
+        double* cnt = mask ? ctx->scratch + MASK_CNT_BASE + (size_t)l * MASK_CNT_STRIDE : nullptr;
+        any_mask = any_mask || mask;
         VBNN_REQUIRE(d.means && d.lvars && d.mu_s && d.var_s && d.stats, "null layer argument");
         VBNN_REQUIRE((d.muT_s == nullptr) == (d.varT_s == nullptr), "muT_s and varT_s go together");
         VBNN_REQUIRE(d.O > 0 && d.I > 0 && d.ld_w >= d.I && (!d.muT_s || d.ld_wT >= d.O), "layer shape");
         const int64_t ntiles = ((d.O + 63) / 64) * ((d.I + 63) / 64);
         const int nb = (int)(ntiles < 2048 ? ntiles : 2048);
         double* partial = ctx->scratch + (size_t)l * 4096;
-        if (dtype == VBNN_F32)
-            hipLaunchKernelGGL(k_prep_layer<float>, dim3(nb), dim3(256), 0, ctx->stream, d.means, d.lvars, d.O, d.I, (float*)d.mu_s,
-                               (float*)d.var_s, d.ld_w, (float*)d.muT_s, (float*)d.varT_s, d.ld_wT, partial);
-        else
-            hipLaunchKernelGGL(k_prep_layer<bf16_t>, dim3(nb), dim3(256), 0, ctx->stream, d.means, d.lvars, d.O, d.I,
-                               (bf16_t*)d.mu_s, (bf16_t*)d.var_s, d.ld_w, (bf16_t*)d.muT_s, (bf16_t*)d.varT_s, d.ld_wT, partial);
-        fa.partial[l] = partial; fa.nb[l] = nb; fa.W[l] = d.O * d.I; fa.stats[l] = d.stats;
+        if (dtype == VBNN_F32) launch_prep_layer<float>(ctx, nb, d, partial, mask, cnt);
+        else launch_prep_layer<bf16_t>(ctx, nb, d, partial, mask, cnt);
+        fa.partial[l] = partial; fa.nb[l] = nb; fa.W[l] = d.O * d.I; fa.stats[l] = d.stats; fa.cnt[l] = cnt;
     }
     int pack_blocks = 0;
     if (extra) {
@@ -795,11 +922,24 @@ extern "C" int vbnn_prepare(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_p
         pack_blocks = grid_for(extra->rows * extra->cols, 1024);
     }
     if (n_layers + pack_blocks > 0) {
-        if (dtype == VBNN_F32) hipLaunchKernelGGL(k_prepare_finish<float>, dim3(n_layers + pack_blocks), dim3(256), 0, ctx->stream, fa);
-        else hipLaunchKernelGGL(k_prepare_finish<bf16_t>, dim3(n_layers + pack_blocks), dim3(256), 0, ctx->stream, fa);
+        const dim3 grid(n_layers + pack_blocks);
+        if (dtype == VBNN_F32) {
+            if (any_mask) hipLaunchKernelGGL((k_prepare_finish<float, true>), grid, dim3(256), 0, ctx->stream, fa);
+            else hipLaunchKernelGGL((k_prepare_finish<float, false>), grid, dim3(256), 0, ctx->stream, fa);
+        } else {
+            if (any_mask) hipLaunchKernelGGL((k_prepare_finish<bf16_t, true>), grid, dim3(256), 0, ctx->stream, fa);
+            else hipLaunchKernelGGL((k_prepare_finish<bf16_t, false>), grid, dim3(256), 0, ctx->stream, fa);
+        }
     }
     return vbnn_check_launch("vbnn_prepare");
     VBNN_API_END
+}
+extern "C" int vbnn_prepare(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prep_desc* layers, const vbnn_pack_desc* extra) {
+    return prepare_impl(ctx, dtype, n_layers, layers, nullptr, extra);
+}
+extern "C" int vbnn_prepare_masked(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prep_desc* layers, const uint8_t* const* masks,
+                                   const vbnn_pack_desc* extra) {
+    return prepare_impl(ctx, dtype, n_layers, layers, masks, extra);
 }
 
 // ---------------------------------------------------------------------------------- update (+ next step's sweep)
@@ -810,6 +950,7 @@ extern "C" int vbnn_prepare(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_p
 #define VBNN_NT_UPDATE 1
 #endif
 constexpr int UPD_NSUM = 16;      // per-block partials: 12 sums, then min / max of the new variances and of the new means
+static_assert(MASK_CNT_BASE == (size_t)8 * 2048 * UPD_NSUM, "the kept counts lie behind the update sweep's partial sums");
 struct UpdLayer {
     float* means; float* lvars; int64_t O, I;
     void* mu_s; void* var_s; int64_t ld_w; void* muT_s; void* varT_s; int64_t ld_wT;
@@ -818,6 +959,8 @@ struct UpdLayer {
     float b1_mu, b2_mu, eps_mu, step_mu, b1_lv, b2_lv, eps_lv, step_lv, B;
     float kl_add;          // weight of the KL gradient added HERE, from the fp32 parameters (vbnn_update_desc.kl_add); 0: the gradients are totals
     double* partial;
+    const uint8_t* mask;   // vbnn_update_masked: the layer's held pruning mask (O x I bytes, non-zero = pruned) and
+    double* cnt_partial;   // the per-block kept counts; both NULL in the unmasked instantiation
 };
 __device__ __forceinline__ double wave_min(double v) {
 #pragma unroll
@@ -844,7 +987,12 @@ __device__ __forceinline__ void upd_block_reduce(double (&a)[UPD_NSUM], double* 
         out[k] = (k < 12) ? v[0] + v[1] + v[2] + v[3] : ((k & 1) ? fmax(fmax(v[0], v[1]), fmax(v[2], v[3])) : fmin(fmin(v[0], v[1]), fmin(v[2], v[3])));
     }
 }
-template <typename T>
+// MASKED (vbnn_update_masked): a pruned weight is frozen -- parameters and Adam moments keep their bits, all four shadows get +0,
+// nothing of it enters a sum or a min / max. A group of four with no kept weight moves nothing but its mask word and its shadows; a
+// mixed group is LOADED whole where the unmasked sweep loads it whole (the 16 bytes share their memory transactions anyway; the
+// pruned lanes are dropped unseen) and STORED weight by weight, kept ones only. A kept weight runs the statements below, the very
+// ones of the unmasked instantiation: one definition, one rounding.
+template <typename T, bool MASKED>
 __global__ __launch_bounds__(256) void k_vb_update(UpdLayer a) {
     __shared__ float tm[64][65];
     __shared__ float tv[64][65];
@@ -856,6 +1004,9 @@ __global__ __launch_bounds__(256) void k_vb_update(UpdLayer a) {
     const bool vec_in = ((I & 3) == 0) && ((((uintptr_t)a.means | (uintptr_t)a.lvars | (uintptr_t)a.g_mu | (uintptr_t)a.g_lv |
                                              (uintptr_t)a.m_mu | (uintptr_t)a.v_mu | (uintptr_t)a.m_lv | (uintptr_t)a.v_lv) & 15u) == 0);
     const bool vec_t = muT_s && ((a.ld_wT & 3) == 0);
+    const bool vec_m = MASKED && vec_in && (((uintptr_t)a.mask & 3u) == 0);
+    double nk = 0.0;          // MASKED: kept weights seen by this thread
+    (void)vec_m; (void)nk;
     // the KL parts of the logged norms, from the pre-update parameters and statistics (VBLinear.lua:91,96)
     const float var_hat = (float)a.stats[2];
     const float k_mu = 1.0f / (a.B * var_hat), k_lv = 1.0f / (2.0f * a.B), inv_vh = 1.0f / var_hat;
@@ -866,13 +1017,23 @@ __global__ __launch_bounds__(256) void k_vb_update(UpdLayer a) {
     // four consecutive weights of row r (columns c .. c + valid - 1, flat index base): everything the sweep does with them.
     // (VBNN_NT_UPDATE: parameters, gradients and Adam moments are this sweep's alone -- nontemporal both ways -- so that what it
     // leaves in the caches is the operand shadows the next forward reads.)
-    auto ld4 = [&](const float* p, float (&o)[4], int valid) {
+    auto ld4 = [&](const float* p, float (&o)[4], int valid, int keep) {
+        if constexpr (MASKED) {
+            if (keep == 0) { o[0] = o[1] = o[2] = o[3] = 0.f; return; }
+            if (!(vec_in && valid == 4)) { load4_kept<VBNN_NT_UPDATE != 0>(p, o, keep); return; }
+        }
 #if VBNN_NT_UPDATE
         if (vec_in && valid == 4) { const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3]; return; }
 #endif
         load4<float>(p, o, valid, vec_in);
     };
-    auto st4 = [&](float* p, const float (&o)[4], int valid) {
+    auto st4 = [&](float* p, const float (&o)[4], int valid, int keep) {
+        if constexpr (MASKED) {
+            // PLAIN stores, the one place where the sweep's own streams lose their nontemporal treatment: 4-byte nontemporal stores
+            // are not merged into whole lines on their way out (measured on the 784-4096-4096 sweep, 50 % held: 2.65x the unmasked
+            // sweep with nontemporal weight-by-weight stores, 1.44x with plain ones, which the L2 combines; LAB_NOTES section 13)
+            if (keep != 15) { store4_kept<false>(p, o, keep); return; }
+        }
 #if VBNN_NT_UPDATE
         if (vec_in && valid == 4) { __builtin_nontemporal_store(f32x4{o[0], o[1], o[2], o[3]}, reinterpret_cast<f32x4*>(p)); return; }
 #endif
@@ -880,17 +1041,20 @@ __global__ __launch_bounds__(256) void k_vb_update(UpdLayer a) {
     };
     auto elem4 = [&](const int64_t base, const int64_t r, const int64_t c, const int valid, float (&m)[4], float (&v)[4]) {
                 float l[4], gm[4], gl[4], mm[4], vm[4], ml[4], vl[4];
-                ld4(a.means + base, m, valid);
-                ld4(a.lvars + base, l, valid);
-                ld4(a.g_mu + base, gm, valid);
-                ld4(a.g_lv + base, gl, valid);
-                ld4(a.m_mu + base, mm, valid);
-                ld4(a.v_mu + base, vm, valid);
-                ld4(a.m_lv + base, ml, valid);
-                ld4(a.v_lv + base, vl, valid);
+                int keep = (1 << valid) - 1;
+                if constexpr (MASKED) { keep = keep_bits4(mask_word4(a.mask + base, valid, vec_m), valid); nk += (double)__popc(keep); }
+                ld4(a.means + base, m, valid, keep);
+                ld4(a.lvars + base, l, valid, keep);
+                ld4(a.g_mu + base, gm, valid, keep);
+                ld4(a.g_lv + base, gl, valid, keep);
+                ld4(a.m_mu + base, mm, valid, keep);
+                ld4(a.v_mu + base, vm, valid, keep);
+                ld4(a.m_lv + base, ml, valid, keep);
+                ld4(a.v_lv + base, vl, valid, keep);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (e < valid) {
+                    if (MASKED && !((keep >> e) & 1)) { m[e] = 0.f; v[e] = 0.f; }       // pruned (or past the row's end): +0 to the shadows
+                    else if (e < valid) {
                         // the two parts of each total gradient (logging only)
                         const float mlc = k_mu * m[e], vlc = k_lv * fmaf(expf(l[e]), inv_vh, -1.0f);
                         if (a.kl_add != 0.f) {            // likelihood-only gradients in: the KL part joins them here, in fp32
@@ -917,12 +1081,12 @@ __global__ __launch_bounds__(256) void k_vb_update(UpdLayer a) {
                         acc[12] = fmin(acc[12], (double)v[e]); acc[13] = fmax(acc[13], (double)v[e]);
                         acc[14] = fmin(acc[14], (double)m[e]); acc[15] = fmax(acc[15], (double)m[e]);
                     }
-                st4(a.means + base, m, valid);
-                st4(a.lvars + base, l, valid);
-                st4(a.m_mu + base, mm, valid);
-                st4(a.v_mu + base, vm, valid);
-                st4(a.m_lv + base, ml, valid);
-                st4(a.v_lv + base, vl, valid);
+                st4(a.means + base, m, valid, keep);
+                st4(a.lvars + base, l, valid, keep);
+                st4(a.m_mu + base, mm, valid, keep);
+                st4(a.v_mu + base, vm, valid, keep);
+                st4(a.m_lv + base, ml, valid, keep);
+                st4(a.v_lv + base, vl, valid, keep);
                 store4<T>(mu_s + r * a.ld_w + c, m[0], m[1], m[2], m[3], valid, true);
                 store4<T>(var_s + r * a.ld_w + c, v[0], v[1], v[2], v[3], valid, true);
     };
@@ -937,6 +1101,10 @@ __global__ __launch_bounds__(256) void k_vb_update(UpdLayer a) {
             elem4(base, r, c, 4, m, v);
         }
         upd_block_reduce(acc, a.partial + (size_t)blockIdx.x * UPD_NSUM, sh);
+        if constexpr (MASKED) {
+            const double rn = block_sum(nk, sh[0]);
+            if (threadIdx.x == 0) a.cnt_partial[blockIdx.x] = rn;
+        }
         return;
     }
     for (int64_t tI = blockIdx.x; tI < ntiles; tI += gridDim.x) {
@@ -971,14 +1139,19 @@ __global__ __launch_bounds__(256) void k_vb_update(UpdLayer a) {
         }
     }
     upd_block_reduce(acc, a.partial + (size_t)blockIdx.x * UPD_NSUM, sh);
+    if constexpr (MASKED) {
+        const double rn = block_sum(nk, sh[0]);
+        if (threadIdx.x == 0) a.cnt_partial[blockIdx.x] = rn;
+    }
 }
 
 struct UpdFinishArgs {
     const double* partial[8]; int nb[8]; int64_t W[8]; double* stats[8]; double* log14[8];
     float* bias[8]; const float* grad_bias[8]; int64_t O[8]; float lr_bias[8]; int n;
+    const double* cnt[8];      // masked call: the layer's kept-count partials (NULL: an unmasked layer)
     const float* src; int64_t rows, cols, ld_src; void* dst; int64_t ld_dst; void* dstT; int64_t ld_dstT;
 };
-template <typename T>
+template <typename T, bool MASKED>
 __global__ __launch_bounds__(256) void k_update_finish(UpdFinishArgs a) {
     __shared__ double sh[UPD_NSUM][4];
     if ((int)blockIdx.x < a.n) {
@@ -1013,10 +1186,21 @@ __global__ __launch_bounds__(256) void k_update_finish(UpdFinishArgs a) {
         __shared__ double tot[UPD_NSUM];
         upd_block_reduce(acc, tot, sh);
         __syncthreads();
+        // MASKED: the kept count stands where W stands -- the means and the unbiased std of the logged series are the kept weights'
+        double n_w = (double)a.W[l];
+        bool masked = false;
+        if constexpr (MASKED) {
+            if (a.cnt[l]) {
+                double c = 0.0;
+                for (int b = threadIdx.x; b < nb; b += 256) c += a.cnt[l][b];
+                n_w = block_sum(c, sh[0]);
+                masked = true;
+            }
+        }
         if (threadIdx.x == 0) {
-            const double W = (double)a.W[l];
+            const double W = n_w;
             const double var_hat_old = a.stats[l][2];
-            if (a.log14[l]) {                                   // VBLinear.lua:149-164, in the order of the Log:add calls
+            if (a.log14[l] && !(masked && W == 0.0)) {          // VBLinear.lua:149-164, in the order of the Log:add calls
                 double* g = a.log14[l];
                 const double nl = sqrt(tot[5]), nm = sqrt(tot[3]);
                 g[0] = sqrt(tot[8]) / nl; g[1] = sqrt(tot[9]) / nl; g[2] = sqrt(tot[6]) / nm; g[3] = sqrt(tot[7]) / nm;
@@ -1026,7 +1210,8 @@ __global__ __launch_bounds__(256) void k_update_finish(UpdFinishArgs a) {
                 g[10] = tot[14]; g[11] = tot[15]; g[12] = sqrt(tot[2]) / nm; g[13] = sqrt(tot[4]) / nl;
             }
             double* st = a.stats[l];                            // as prior_finish, of the NEW parameters
-            st[0] = tot[0]; st[1] = tot[1]; st[2] = (1.0 / W) * tot[0]; st[3] = W;
+            if (masked) masked_stats(tot[0], tot[1], W, a.W[l], st);
+            else { st[0] = tot[0]; st[1] = tot[1]; st[2] = (1.0 / W) * tot[0]; st[3] = W; }
         }
         if (a.bias[l] && (int)gridDim.x == a.n)                 // optim.sgd on the bias (VBLinear.lua:125-128): here only when there are no
             for (int64_t o = threadIdx.x; o < a.O[l]; o += 256) a.bias[l][o] = fmaf(-a.lr_bias[l], a.grad_bias[l][o], a.bias[l][o]);   // packing blocks to share it
@@ -1055,7 +1240,9 @@ static inline float adam_step_size(const vbnn_adam_cfg& c, float* b1_out) {
     return (float)((double)c.lr * sqrt(bc2) / bc1);
 }
 
-extern "C" int vbnn_update(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_update_desc* layers, const vbnn_pack_desc* extra) {
+// vbnn_update and vbnn_update_masked: one body. masks == NULL or no entry set: the launches of vbnn_update, kernel for kernel.
+static int update_impl(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_update_desc* layers, const uint8_t* const* masks,
+                       const vbnn_pack_desc* extra) {
     VBNN_API_BEGIN
     VBNN_REQUIRE(ctx && (layers || n_layers == 0), "null argument");
     VBNN_REQUIRE(n_layers >= 0 && n_layers <= 8, "n_layers (0..8)");
@@ -1064,6 +1251,7 @@ extern "C" int vbnn_update(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_up
     VBNN_REQUIRE((size_t)n_layers * MAXB * UPD_NSUM <= ctx->scratch_doubles, "scratch");
     UpdFinishArgs fa{};
     fa.n = n_layers;
+    bool any_mask = false;
     // (layer order. r05 A/B, two rounds on one box: the layer whose gradients were written LAST first -- they might still sit in the
     // Infinity Cache -- 1.025 / 1.029 ms per training step against 1.008 / 1.003; with accGradParameters' gradient stores plain instead
     // of nontemporal as well, 1.033 / 1.024, and the step without update 0.765 against 0.750: neither is kept.)
@@ -1090,8 +1278,18 @@ extern "C" int vbnn_update(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_up
         a.B = d.B;
         a.kl_add = d.kl_add;
         a.partial = ctx->scratch + (size_t)l * MAXB * UPD_NSUM;
-        if (dtype == VBNN_F32) hipLaunchKernelGGL(k_vb_update<float>, dim3(nb), dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(k_vb_update<bf16_t>, dim3(nb), dim3(256), 0, ctx->stream, a);
+        a.mask = masks ? masks[l] : nullptr;
+        VBNN_REQUIRE(!a.mask || MASK_CNT_BASE + 8 * MASK_CNT_STRIDE <= ctx->scratch_doubles, "scratch (kept counts)");
+        a.cnt_partial = a.mask ? ctx->scratch + MASK_CNT_BASE + (size_t)l * MASK_CNT_STRIDE : nullptr;
+        any_mask = any_mask || a.mask;
+        if (a.mask) {
+            if (dtype == VBNN_F32) hipLaunchKernelGGL((k_vb_update<float, true>), dim3(nb), dim3(256), 0, ctx->stream, a);
+            else hipLaunchKernelGGL((k_vb_update<bf16_t, true>), dim3(nb), dim3(256), 0, ctx->stream, a);
+        } else {
+            if (dtype == VBNN_F32) hipLaunchKernelGGL((k_vb_update<float, false>), dim3(nb), dim3(256), 0, ctx->stream, a);
+            else hipLaunchKernelGGL((k_vb_update<bf16_t, false>), dim3(nb), dim3(256), 0, ctx->stream, a);
+        }
+        fa.cnt[l] = a.cnt_partial;
         fa.partial[l] = a.partial; fa.nb[l] = nb; fa.W[l] = d.O * d.I; fa.stats[l] = d.stats; fa.log14[l] = d.log14;
         fa.bias[l] = d.bias; fa.grad_bias[l] = d.grad_bias; fa.O[l] = d.O; fa.lr_bias[l] = d.lr_bias;
     }
@@ -1105,11 +1303,24 @@ extern "C" int vbnn_update(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_up
         pack_blocks = grid_for(extra->rows * extra->cols, 1024);
     }
     if (n_layers + pack_blocks > 0) {
-        if (dtype == VBNN_F32) hipLaunchKernelGGL(k_update_finish<float>, dim3(n_layers + pack_blocks), dim3(256), 0, ctx->stream, fa);
-        else hipLaunchKernelGGL(k_update_finish<bf16_t>, dim3(n_layers + pack_blocks), dim3(256), 0, ctx->stream, fa);
+        const dim3 grid(n_layers + pack_blocks);
+        if (dtype == VBNN_F32) {
+            if (any_mask) hipLaunchKernelGGL((k_update_finish<float, true>), grid, dim3(256), 0, ctx->stream, fa);
+            else hipLaunchKernelGGL((k_update_finish<float, false>), grid, dim3(256), 0, ctx->stream, fa);
+        } else {
+            if (any_mask) hipLaunchKernelGGL((k_update_finish<bf16_t, true>), grid, dim3(256), 0, ctx->stream, fa);
+            else hipLaunchKernelGGL((k_update_finish<bf16_t, false>), grid, dim3(256), 0, ctx->stream, fa);
+        }
     }
     return vbnn_check_launch("vbnn_update");
     VBNN_API_END
+}
+extern "C" int vbnn_update(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_update_desc* layers, const vbnn_pack_desc* extra) {
+    return update_impl(ctx, dtype, n_layers, layers, nullptr, extra);
+}
+extern "C" int vbnn_update_masked(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_update_desc* layers, const uint8_t* const* masks,
+                                  const vbnn_pack_desc* extra) {
+    return update_impl(ctx, dtype, n_layers, layers, masks, extra);
 }
 
 // ---------------------------------------------------------------------------------- pack_input

@@ -412,6 +412,8 @@ class FusedMLP:
         self._pruned = None               # the pruned view predict() reads its operands from (use_pruned), or None
         self._pver = 0                    # parameter version: a pruned view is a snapshot of ONE version (prune / predict)
         self._prune_ws = None
+        self._held = None                 # the held pruning masks (hold_pruned): one O x I uint8 tensor per VB layer, 1 = frozen
+        self._held_counts = None
         self.init_parameters()
 
     # mlp.lua:47-55 (He rule for every weight, bias zero) + the bench's non-degenerate means
@@ -557,7 +559,10 @@ class FusedMLP:
                                       stats=_p(v.stats))
             w3 = L.PackDesc(src=_p(self.weight3), rows=self.n_classes, cols=self.sizes[-1], ld_src=self.sizes[-1],
                             dst=self.w3_s.ptr, ld_dst=self.w3_s.ld, dstT=self.w3T_s.ptr, ld_dstT=self.w3T_s.ld)
-            L.check(lib.vbnn_prepare(self.ctx.h, self.code, len(self.vb), descs, C.byref(w3)))
+            if self._held is not None:                        # a held pruning mask: +0 shadows, the kept network's statistics
+                L.check(lib.vbnn_prepare_masked(self.ctx.h, self.code, len(self.vb), descs, self._held_ptrs(), C.byref(w3)))
+            else:
+                L.check(lib.vbnn_prepare(self.ctx.h, self.code, len(self.vb), descs, C.byref(w3)))
             return
         for v in self.vb:
             L.check(lib.vbnn_compute_prior(self.ctx.h, _p(v.means), _p(v.lvars), v.O * v.I, None, None, None, _p(v.stats)))
@@ -1451,7 +1456,10 @@ class FusedMLP:
                                     kl_add=1.0 if self.kl_in_update else 0.0)
         w3 = L.PackDesc(src=_p(self.weight3), rows=self.n_classes, cols=self.sizes[-1], ld_src=self.sizes[-1],
                         dst=self.w3_s.ptr, ld_dst=self.w3_s.ld, dstT=self.w3T_s.ptr, ld_dstT=self.w3T_s.ld)
-        L.check(lib.vbnn_update(h, self.code, len(self.vb), descs, C.byref(w3)))
+        if self._held is not None:                            # a held pruning mask: the frozen weights keep every bit
+            L.check(lib.vbnn_update_masked(h, self.code, len(self.vb), descs, self._held_ptrs(), C.byref(w3)))
+        else:
+            L.check(lib.vbnn_update(h, self.code, len(self.vb), descs, C.byref(w3)))
         self._shadows_ready = True
 
     # ---- reporting (each of these synchronises)
@@ -1468,11 +1476,91 @@ class FusedMLP:
         self._need_gathered_parameters("calc_lc")
         lc = 0.0
         B = float((opt or self.opt).get("B", self.B))
-        for v in self.vb:
-            L.check(L.lib().vbnn_calc_lc(self.ctx.h, _p(v.means), _p(v.lvars), None, None, _p(v.stats), B, None,
-                                         _p(self._lc), v.O * v.I))
+        for li, v in enumerate(self.vb):
+            if self._held is not None:                        # the KL of the network that exists: the kept weights' sum
+                L.check(L.lib().vbnn_calc_lc_masked(self.ctx.h, _p(v.means), _p(v.lvars), _p(self._held[li]), _p(v.stats), B, None,
+                                                    _p(self._lc), v.O * v.I))
+            else:
+                L.check(L.lib().vbnn_calc_lc(self.ctx.h, _p(v.means), _p(v.lvars), None, None, _p(v.stats), B, None,
+                                             _p(self._lc), v.O * v.I))
             lc += float(self._lc[0].item())
         return lc
+
+    # ---- fine-tuning a pruned network: a pruning mask HELD through training. The GEMMs of a step read the operand shadows only,
+    # so the whole feature is the parameter sweep: while a mask is held prepare() / update() / calc_lc() go through
+    # vbnn_prepare_masked / vbnn_update_masked / vbnn_calc_lc_masked -- +0 in a pruned weight's shadow entries, its fp32 parameters
+    # and Adam moments frozen bit for bit, the prior statistics those of the kept weights. run / test / predict are unchanged.
+    def _held_ptrs(self):
+        return (C.c_void_p * len(self.vb))(*[m.data_ptr() for m in self._held])
+
+    def _refuse_held(self, what):
+        if self._held is not None:
+            raise RuntimeError(f"{what}: a pruning mask is held, and {what} keys on the fp32 parameters, which still hold the frozen "
+                               "weights' values -- release_pruned() first")
+
+    @property
+    def held(self):
+        """Per VB layer the number of weights the held mask freezes, or None when nothing is held."""
+        return None if self._held is None else list(self._held_counts)
+
+    def held_mask(self, li):
+        """The held mask of VB layer li as an O x I bool tensor (True = pruned and frozen)."""
+        if self._held is None:
+            raise RuntimeError("held_mask: no pruning mask is held")
+        return self._held[li].bool()
+
+    @_ordered
+    def hold_pruned(self, result):
+        """Train the network `result` leaves: from now on the weights it prunes are out of the network AND frozen. `result`: a
+        PruneResult or SparsePruneResult of this engine at the current parameter version. Its byte masks (the vbnn_prune_pack
+        route of PruneResult.mask) are ORed into whatever is already held -- the held set only grows, which is what an iterative
+        schedule needs -- the shadows and statistics are rewritten by the masked prepare (a parameter-version change: `result`
+        and any other snapshot are void afterwards), and the per-layer held counts are returned (synchronises once).
+        prune() stays legal under a held mask and reads the raw fp32 parameters, frozen values included: prune(q) followed by
+        hold_pruned gives gradual pruning, but a frozen weight may rank above the new threshold, so the held fraction can exceed
+        the requested one -- the returned counts are the true ones.
+        Refused: weight-noise mode (sample() packs drawn weights and would need a masked draw), the sharded update, an engine
+        with fuse_kl = False (its parameters are stepped by the module-level update, which knows no mask: the frozen weights would
+        move), and a mask that leaves a layer without a kept weight.
+        The mask tensors are allocated by the FIRST hold and updated in place by later ones, so their device addresses are stable
+        while a mask is held; a step captured by capture_step whose issue() contained prepare() or update() replays the calls it
+        recorded -- masked with those addresses if it was captured under a held mask, unmasked if not. Capture such a step again
+        after the first hold_pruned and after release_pruned. prune_units / compact / compress are refused while a mask is held; compressing
+        a held network by its mask is the follow-up. The data-parallel all-reduce mode works as it stands: the update is
+        rank-local and identical on every rank (hold the same result on every rank)."""
+        if not isinstance(result, PruneResult) or result.engine is not self:
+            raise ValueError("hold_pruned: a PruneResult of this engine")
+        if self.mode == "wn":
+            raise RuntimeError("hold_pruned: weight-noise mode packs drawn weights in sample(), which knows no mask -- LRT only")
+        if self.sharded:
+            raise RuntimeError("hold_pruned: not with the sharded update (every rank sweeps a slice of the rows)")
+        if not self.fuse_kl:
+            raise RuntimeError("hold_pruned: needs opt.fuse_kl = True (FusedMLP.update is the only update that carries the mask)")
+        if result.version != self._pver:
+            raise RuntimeError("hold_pruned: the parameters changed since this result was taken (prune() again)")
+        masks = []
+        for li in range(len(self.vb)):
+            m = result.mask(li).to(torch.uint8)
+            masks.append(m if self._held is None else torch.bitwise_or(m, self._held[li]))
+        counts = torch.stack([m.sum(dtype=torch.int64) for m in masks]).cpu().tolist()
+        for li, (v, n) in enumerate(zip(self.vb, counts)):
+            if n >= v.O * v.I:
+                raise RuntimeError(f"hold_pruned: VB layer {li} would be left without a kept weight")
+        if self._held is None:
+            self._held = [m.contiguous() for m in masks]
+        else:                                                 # in place: the addresses a captured update holds stay valid
+            for old, m in zip(self._held, masks):
+                old.copy_(m)
+        self._held_counts = [int(n) for n in counts]
+        self.prepare()
+        return self.held
+
+    @_ordered
+    def release_pruned(self):
+        """Drops the held mask and runs the ordinary prepare(): the frozen weights are back, with the values (and Adam moments)
+        they had when they were held."""
+        self._held = self._held_counts = None
+        self.prepare()
 
     # ---- structured pruning (csrc/units.hip): whole hidden units by the group form of mainviz.lua:20-21, and the compact engine
     # that is left -- a smaller DENSE network for the ordinary kernels. Nothing of this engine changes: prune_units reads the
@@ -1512,6 +1600,7 @@ class FusedMLP:
             raise ValueError(f"prune_units: fraction = {fraction} (0 .. 1)")
         if int(multiple) != multiple or int(multiple) < 1:
             raise ValueError(f"prune_units: multiple = {multiple} (an integer >= 1)")
+        self._refuse_held("prune_units")
         self._need_gathered_parameters("prune_units")
         if not self._shadows_ready:            # (prepare() counts as a parameter change: do it before the snapshot is versioned)
             self.prepare()
@@ -1547,6 +1636,7 @@ class FusedMLP:
         opt_overrides: options of the new engine that differ from this one's."""
         if not isinstance(result, UnitPruneResult) or result.engine is not self:
             raise ValueError("compact: a UnitPruneResult of this engine")
+        self._refuse_held("compact")
         if result.version != self._pver:
             raise RuntimeError("compact: the parameters changed since this result was taken (prune_units() again)")
         self._need_gathered_parameters("compact")
@@ -1617,7 +1707,8 @@ class FusedMLP:
         threshold (tau itself; the reference uses 0.005) and fraction in [0, 1] (tau = the exact k-th smallest key,
         k = floor(fraction W), so at most k weights go -- fewer when keys tie at tau; fraction = 1: tau = +inf, everything).
         scope = "global": one tau over all VB layers; "layer": the fraction applies to each layer (one tau per layer).
-        Returns a PruneResult (synchronises to read tau and the counts); nothing changes for predict() until use_pruned."""
+        Returns a PruneResult (synchronises to read tau and the counts); nothing changes for predict() until use_pruned.
+        Under a held mask (hold_pruned) the keys are still those of the raw fp32 parameters, frozen weights included."""
         if (fraction is None) == (threshold is None):
             raise ValueError("prune: exactly one of fraction and threshold")
         if scope not in ("global", "layer"):
@@ -1664,7 +1755,8 @@ class FusedMLP:
 
     def use_pruned(self, result):
         """predict() reads the pruned operands of `result` (a PruneResult of this engine) from now on; None: the unpruned
-        shadows again. Nothing else looks at the view: run / test / update / prepare and their operands are untouched."""
+        shadows again. Nothing else looks at the view: run / test / update / prepare and their operands are untouched
+        (hold_pruned is what trains a pruned network)."""
         if result is not None and (not isinstance(result, PruneResult) or result.engine is not self):
             raise ValueError("use_pruned: a PruneResult of this engine, or None")
         self._pruned = result
@@ -1715,6 +1807,7 @@ class FusedMLP:
     def _compress(self, res):
         if not isinstance(res, PruneResult) or res.engine is not self:
             raise ValueError("compress: a PruneResult of this engine")
+        self._refuse_held("compress")
         if res.version != self._pver:
             raise RuntimeError("compress: the parameters changed since this result was taken (prune() again)")
         if isinstance(res, SparsePruneResult):

@@ -11,6 +11,13 @@ directory's `parameters/means`, `parameters/vars`, `opt` (the files mainviz.lua:
 vbnn_amd.t7file with utils.safe_save's keep-the-old-file rule (main.lua:181 saves the whole Lua `net` table, methods
 included; Lua byte code cannot be produced here, so the data is what is saved).
 
+opt.prune_schedule = [(epoch, fraction), ...] (off by default; epochs count from 0 over the life of this Main): at the start of
+each listed epoch the trainer prunes that fraction of the weights by signal-to-noise (FusedMLP.prune, opt.prune_scope, default
+"global") and HOLDS the mask through the training that follows (FusedMLP.hold_pruned) -- prune, retrain, prune again. The masks
+are ORed, and prune() ranks the frozen weights by the values they were frozen with, so the held fraction can exceed the listed
+one; the series `held fraction` logs the true one, and `lc` is then the kept weights' sum. The reference only counts what
+would go (mainviz.lua:20-27).
+
 Differences from main.lua, all deliberate: the loop ends after `epochs` (the reference loops forever, :164); a last
 short minibatch is skipped rather than padded with uninitialised rows (data.lua:9-20); targets are 0-based.
 """
@@ -52,6 +59,7 @@ class Main:
         self.device = self.net.device
         self.rng = np.random.RandomState(int(opt.get("seed", 3)))                         # torch.manualSeed(3), config.lua:40
         self.indices = None
+        self.epoch = 0                                                                    # epochs run so far (opt.prune_schedule counts them)
         self.log = Logger(opt["network_name"], append=bool(opt.get("network_to_load"))) if opt.get("log") else None
 
     def _to_device(self, inputs, targets):
@@ -138,6 +146,16 @@ class Main:
                 rec[f"devacc_pruned@{q:g}"] = a / len(starts)
         return rec
 
+    def start_epoch(self):
+        """What run() does before an epoch's training: opt.prune_schedule's entries for the epoch about to start --
+        prune(fraction, opt.prune_scope), then hold_pruned -- and the epoch counter. Public so that a caller that drives train()
+        itself (tools/finetune_bench.py measures between the pruning and the training) follows the same schedule."""
+        for epoch, fraction in (self.opt.get("prune_schedule") or []):
+            if int(epoch) == self.epoch:
+                res = self.net.prune(fraction=float(fraction), scope=self.opt.get("prune_scope", "global"))
+                self.net.hold_pruned(res)
+        self.epoch += 1
+
     def save(self):
         """The run directory's data files (mainviz.lua:11-15): every VB layer's means / vars flattened and
         concatenated in layer order -- the order of the reference's flat `parameters` vector (mlp.lua:37)."""
@@ -151,6 +169,7 @@ class Main:
     def run(self, trainSet, testSet, epochs=1):                                           # main.lua:138-184
         history = []
         for _ in range(epochs):
+            self.start_epoch()                                                             # opt.prune_schedule (off by default)
             trainAccuracy, trainError = self.train(trainSet)
             testAccuracy, testError = self.test(testSet)
             rec = {"devacc": testAccuracy, "trainacc": trainAccuracy, "deverr": testError, "trainerr": trainError}
@@ -160,13 +179,16 @@ class Main:
                 self.net.gather_parameters()              # collective (every rank runs this loop): calc_lc and save read fp32 rows
             if self.opt.get("type", "vb") == "vb":
                 rec["lc"] = self.net.calc_lc(self.opt)
+            if self.opt.get("prune_schedule"):
+                held = self.net.held
+                rec["held fraction"] = (sum(held) / sum(v.O * v.I for v in self.net.vb)) if held else 0.0
             rec.update(self._prune_series(testSet))       # opt.prune_report / opt.prune_eval (both off by default)
             if self.log:
                 for k in ("devacc", "trainacc", "deverr", "trainerr", "lc", "devacc_pred", "devnll_pred", "dev_mi"):   # main.lua:169-177 (+ opt.predictive)
                     if k in rec:
                         self.log.add(k, rec[k])
                 for k in rec:
-                    if k in ("pruned count", "pruned var mean") or k.startswith("devacc_pruned@"):
+                    if k in ("pruned count", "pruned var mean", "held fraction") or k.startswith("devacc_pruned@"):
                         self.log.add(k, rec[k])
                 self.log.flush()
                 self.save()                                                                # main.lua:181
