@@ -682,6 +682,51 @@ typedef struct vbnn_predict_args {
 } vbnn_predict_args;
 int vbnn_head_predict(vbnn_ctx* ctx, int dtype, const vbnn_predict_args* a);
 
+/* Regression posterior predictive (additive, ABI 6): the moments over S draws of the final Linear's f32 outputs y_s (R x D per
+ * draw) -- the predictive mean, the spread of the draws per output (the epistemic variance) -- and, with targets, the squared
+ * errors and the log density of the equal-weight mixture of N(y_s, tau^2 I) at the target. All arithmetic is fp32, operation
+ * by operation as written here (the file is compiled without floating-point contraction; divisions are correctly rounded).
+ * Per element (r, d), from mean = M2 = 0, over the draws s = 0 .. S-1 in order (Welford):
+ *   delta = y - mean;   mean = mean + delta / float(s + 1);   M2 = M2 + delta * (y - mean)
+ * Finish per element: mean is stored as it stands; var = M2 / float(S) -- the variance of the mixture's components (S = 1
+ * gives exactly 0, equal draws give exactly 0). The total predictive variance of an output is var + noise_var.
+ * Per row and draw, with a target: e_s = sum_d (t - y_s)^2; sum_s e_s is kept as a running sum (draw 0 starts it); with
+ * noise_var > 0 the running single-value online logsumexp L of a_s = -e_s * c, c = 0.5f / noise_var: draw 0 sets L = a_0,
+ * every later draw L = max(L, a) + log1p(exp(-|L - a|)).
+ * Finish per row: row_sq_err = sum_d (t - mean)^2;  row_var = (sum_d var) / float(D);
+ *   row_log_lik = L - log(float(S)) - (0.5f * float(D)) * log(6.2831855f * noise_var).
+ * Every row sum (e_s, row_sq_err, sum_d var) is formed in an order that depends on D alone: a row is worked by T = 64 threads
+ * (D <= 256) or T = 256 (above); thread i adds, in ascending order, the columns 4 q .. 4 q + 3 of its quads q = i, i + T, ...;
+ * the threads of a wave are added by the xor butterfly 32, 16, .. 1; the four waves in wave order. The same assignment holds
+ * on the 16-byte and on the scalar access path (chosen per launch from D, the leading dimensions and the base addresses), in
+ * both forms, for every R and row position. Pad columns are never read. A NaN in y reaches its element, its row's row values
+ * and the totals, and no other row.
+ * VBNN_MOMENTS_STACKED: y holds all S draws (draw s = rows [s R, (s+1) R)); one call walks them with the running moments in
+ * registers (D <= VBNN_MOMENTS_STACKED_MAX_D; draw / state ignored). VBNN_MOMENTS_ACCUMULATE: y holds ONE draw, number `draw`;
+ * the running values live in `state` between the S calls and every call rewrites it. Both forms run one device function per
+ * draw: given the same y per draw, every output and total is bitwise equal between them. */
+enum { VBNN_MOMENTS_STACKED = 0, VBNN_MOMENTS_ACCUMULATE = 1 };
+#define VBNN_MOMENTS_STACKED_MAX_D 4096   /* largest D the STACKED form takes */
+typedef struct vbnn_moments_args {
+    const float* y; int64_t ld_y;       /* f32 outputs of the final Linear: S R x D (STACKED; draw s = rows [s R, (s+1) R)) or R x D (ACCUMULATE) */
+    const float* target; int64_t ld_t;  /* R x D regression targets, or NULL */
+    int64_t R, D, S;                    /* minibatch rows, outputs per row (>= 1, any), draws of the WHOLE prediction (>= 1) */
+    int32_t form;
+    int32_t draw;                       /* ACCUMULATE: 0-based index of this draw; 0 starts the state (nothing is read from it), S - 1 finishes */
+    float noise_var;                    /* tau^2 > 0: the log-likelihood is produced; 0: skipped */
+    float* state;                       /* ACCUMULATE: R x (2 D + 2) floats, row r = { mean[D], M2[D], sum_s e_s, L } */
+    /* outputs of the finish, each optional (NULL to skip) */
+    float* mean; float* var; int64_t ld_out;   /* R x D each */
+    float* row_var;                     /* R: mean over d of var */
+    float* row_sq_err;                  /* R: sum_d (t - mean)^2 (needs target) */
+    float* row_log_lik;                 /* R (needs target and noise_var > 0) */
+    /* with target: 4 doubles WRITTEN by the finish, { sum_r row_sq_err, sum_{r,s} e_s, sum_r row_log_lik (0 when noise_var is 0),
+     * sum_{r,d} var }, each summed over rows in double in a fixed order (workgroup partials, one finish block; no float
+     * atomics). NULL to skip. */
+    double* totals;
+} vbnn_moments_args;
+int vbnn_predict_moments(vbnn_ctx* ctx, const vbnn_moments_args* a);
+
 /* ---- signal-to-noise pruning (additive, ABI 6): mainviz.lua:20-27 on the device, and the pruned operand shadows that let
  * vbnn_forward / vbnn_head_predict evaluate the pruned network ---------------------------------------------------------------
  * The key of a weight is snr = |means / sqrt(exp(lvars))| in fp32, operation for operation as mainviz.lua:20 forms

@@ -254,6 +254,22 @@ typedef struct vbnn_predict_args {
     double* totals;
 } vbnn_predict_args;
 int vbnn_head_predict(vbnn_ctx* ctx, int dtype, const vbnn_predict_args* a);
+enum { VBNN_MOMENTS_STACKED = 0, VBNN_MOMENTS_ACCUMULATE = 1 };
+typedef struct vbnn_moments_args {
+    const float* y; int64_t ld_y;
+    const float* target; int64_t ld_t;
+    int64_t R, D, S;
+    int32_t form;
+    int32_t draw;
+    float noise_var;
+    float* state;
+    float* mean; float* var; int64_t ld_out;
+    float* row_var;
+    float* row_sq_err;
+    float* row_log_lik;
+    double* totals;
+} vbnn_moments_args;
+int vbnn_predict_moments(vbnn_ctx* ctx, const vbnn_moments_args* a);
 typedef struct vbnn_prune_desc {
     const float* means; const float* lvars; int64_t O, I;
     void* mu_p; void* var_p; int64_t ld_w;

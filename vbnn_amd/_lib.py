@@ -98,6 +98,16 @@ class PredictArgs(C.Structure):       # vbnn_predict_args
 PREDICT_STACKED, PREDICT_ACCUMULATE = 0, 1
 
 
+class MomentsArgs(C.Structure):       # vbnn_moments_args
+    _fields_ = [("y", _vp), ("ld_y", _i64), ("target", _vp), ("ld_t", _i64), ("R", _i64), ("D", _i64), ("S", _i64),
+                ("form", C.c_int32), ("draw", C.c_int32), ("noise_var", _f), ("state", _vp), ("mean", _vp), ("var", _vp),
+                ("ld_out", _i64), ("row_var", _vp), ("row_sq_err", _vp), ("row_log_lik", _vp), ("totals", _vp)]
+
+
+MOMENTS_STACKED, MOMENTS_ACCUMULATE = 0, 1
+MOMENTS_STACKED_MAX_D = 4096          # VBNN_MOMENTS_STACKED_MAX_D
+
+
 class PruneDesc(C.Structure):         # vbnn_prune_desc
     _fields_ = [("means", _vp), ("lvars", _vp), ("O", _i64), ("I", _i64), ("mu_p", _vp), ("var_p", _vp), ("ld_w", _i64),
                 ("stats", _vp), ("mask", _vp)]
@@ -157,6 +167,7 @@ _SIGS = {
     "vbnn_backward_pair": ([_vp, _i, C.POINTER(DxArgs), C.POINTER(DwArgs)], _i),
     "vbnn_head_forward_backward": ([_vp, _i, C.POINTER(HeadArgs)], _i),
     "vbnn_head_predict": ([_vp, _i, C.POINTER(PredictArgs)], _i),
+    "vbnn_predict_moments": ([_vp, C.POINTER(MomentsArgs)], _i),
     "vbnn_acc_grad_bias": ([_vp, _i, _vp, _i64, _i64, _i64, _f, _i, _vp], _i),
     "vbnn_prep_layer": ([_vp, _i, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp], _i),
     "vbnn_compute_mugrads": ([_vp, _vp, _vp, _f, _f, _vp, _vp, _i64], _i),

@@ -91,6 +91,22 @@ class PredictResult:
         self.S, self.stacked, self.chunks = None, None, None
 
 
+class RegressionPredictResult:
+    """FusedMLP.predict_regression's outputs for R minibatch rows of D outputs. Device tensors: mean (R x D: 1/S sum_s f_s(x)),
+    var (R x D: the population variance of the S draws per output, the epistemic part -- the total predictive variance is
+    var + noise_var), row_var (R: its mean over the outputs); with targets row_sq_err (R: sum_d (t - mean)^2) and, with
+    noise_var, row_log_lik (R: the log density of the equal-weight mixture of N(f_s(x), noise_var I) at t); draws (S x R x D)
+    with keep_draws. With targets also Python floats: totals (the library's four sums), mse (of the predictive mean),
+    mean_draw_mse (the mean over draws of each draw's MSE: test()'s number), log_lik (mean row_log_lik; None without noise_var)
+    and mean_var."""
+
+    def __init__(self, mean, var, row_var, row_sq_err, row_log_lik, draws):
+        self.mean, self.var, self.row_var = mean, var, row_var
+        self.row_sq_err, self.row_log_lik, self.draws = row_sq_err, row_log_lik, draws
+        self.totals = self.mse = self.mean_draw_mse = self.log_lik = self.mean_var = None
+        self.S, self.stacked, self.chunks = None, None, None
+
+
 class PruneResult:
     """FusedMLP.prune's outcome: the signal-to-noise pruning of mainviz.lua:20-27 at one threshold per VB layer, and the pruned
     operand shadows (mu_p / var_p per layer, owned here) that predict() reads while this result is the engine's pruned view
@@ -823,6 +839,125 @@ class FusedMLP:
                 L.check(lib.vbnn_pack(self.ctx.h, self.code, L.PACK_COPY, _p(v.weight), None, v.I, v.O, v.I,
                                       v.mu_s.ptr, v.mu_s.ld, v.muT_s.ptr if v.muT_s else None,
                                       v.muT_s.ld if v.muT_s else 0))
+
+    # ---- the regression criterion's posterior predictive (vbnn_predict_moments): predict()'s contract and buffers, the final
+    # Linear as _generic_head runs it (f32 outputs), then the moments of the S draws -- mean, spread, and with targets the
+    # squared errors and the mixture's log-likelihood. Nothing of the training step is written.
+    @_ordered
+    def predict_regression(self, inputs, S=None, targets=None, noise_var=None, map=False, row0=None, keep_draws=False):
+        """E[y | x, D] ~ 1/S sum_s f_s(x) over draws self.draw + 1 .. self.draw + S, with the draws' variance per output; S, map
+        and row0 as predict(), and `self.draw` advances by S likewise. targets: R x D fp32. noise_var (tau^2 > 0, or None): the
+        observation noise of the predictive log-likelihood. keep_draws: the S x R x D outputs are returned too. Returns a
+        RegressionPredictResult of this rank's rows (no collective, as test())."""
+        lib, ctx, code = L.lib(), self.ctx.h, self.code
+        D = self.n_classes
+        if self.criterion != "mse":
+            raise ValueError("predict_regression: the regression predictive needs the MSE criterion (criterion = 'nll': use predict)")
+        if noise_var is not None:
+            noise_var = float(noise_var)
+            if not (noise_var > 0.0 and math.isfinite(noise_var)):
+                raise ValueError(f"predict_regression: noise_var = {noise_var} (a finite variance above zero, or None)")
+        map = bool(map or self.opt.get("quicktest"))
+        S = 1 if map else int(self.opt["testSamples"] if S is None else S)
+        if S < 1:
+            raise ValueError(f"predict_regression: S = {S} draws (at least one)")
+        x = inputs.reshape(inputs.shape[0], -1)
+        R = x.shape[0]
+        assert x.shape[1] == self.sizes[0] and x.dtype == torch.float32 and x.is_cuda and R > 0
+        if targets is not None:
+            assert targets.dtype == torch.float32 and targets.is_cuda and tuple(targets.shape) == (R, D)
+            targets = targets.contiguous()
+        row0 = self.rank * R if row0 is None else int(row0)
+        if not self._shadows_ready:
+            self.prepare()
+        if self._pruned is not None:
+            if self.mode == "wn" and not map:
+                raise ValueError("predict_regression: weight-noise draws under a pruned view are not supported (use map=True, or "
+                                 "mode = 'lrt')")
+            if self._pruned.version != self._pver:
+                raise RuntimeError("predict_regression: the pruned view was taken from older parameters (update / prepare / "
+                                   "init_parameters ran since): prune() again, or use_pruned(None)")
+        lrt = self.mode == "lrt" and not map
+        stacked = self._predict_stacked(R, S, lrt)
+        cap = max(1, int(self.opt.get("predict_rows", 32768)))
+        Rc = max(1, min(R, cap // S if stacked else cap))
+        op_rows = S * Rc if stacked else Rc
+        bufs = self._predict_buffers(op_rows, lrt)
+        wts = self._predict_weights() if self.mode == "wn" else None
+        f32 = dict(dtype=torch.float32, device=self.device)
+        n_chunks = (R + Rc - 1) // Rc
+        has_t = targets is not None
+        res = RegressionPredictResult(torch.empty(R, D, **f32), torch.empty(R, D, **f32), torch.empty(R, **f32),
+                                      torch.empty(R, **f32) if has_t else None,
+                                      torch.empty(R, **f32) if (has_t and noise_var is not None) else None,
+                                      torch.empty(S, R, D, **f32) if keep_draws else None)
+        direct = keep_draws and (not stacked or n_chunks == 1)      # the final Linear writes into res.draws itself
+        ybuf = None
+        if not direct:                                               # the y buffer: kept with the predict buffers
+            ybuf = getattr(bufs, "y_reg", None)
+            if ybuf is None or tuple(ybuf.shape) != (op_rows, D):
+                ybuf = bufs.y_reg = torch.empty(op_rows, D, **f32)
+        one_call = stacked and D <= L.MOMENTS_STACKED_MAX_D         # else: one ACCUMULATE call per draw
+        state = None if one_call else torch.empty(Rc, 2 * D + 2, **f32)
+        totals = torch.zeros(n_chunks, 4, dtype=torch.float64, device=self.device) if has_t else None
+        d0 = self.draw + 1
+        nl, H = len(self.vb), self.sizes[-1]
+        a = L.MomentsArgs(ld_y=D, ld_t=D, D=D, S=S, form=L.MOMENTS_STACKED if one_call else L.MOMENTS_ACCUMULATE,
+                          noise_var=noise_var or 0.0, state=_p(state), ld_out=D)
+
+        def off(t, row):
+            return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
+
+        def final_linear(N, y_ptr):
+            fa = L.FwdArgs(w=self.w3_s.ptr, w2=None, x=bufs[nl].x.ptr, x2=None, ld_w=self.w3_s.ld, ld_x=bufs[nl].x.ld,
+                           N=N, I=H, O=D, bias=_p(self.bias3), y=y_ptr, ld_y=D)
+            L.check(lib.vbnn_forward(ctx, code, C.byref(fa)))
+
+        for k in range(n_chunks):
+            c0 = k * Rc
+            rows = min(Rc, R - c0)
+            xc = x[c0:c0 + rows]
+            a.R = rows
+            a.target = off(targets, c0 * D)
+            a.totals = C.c_void_p(totals[k].data_ptr()) if has_t else None
+            a.mean, a.var = off(res.mean, c0 * D), off(res.var, c0 * D)
+            a.row_var, a.row_sq_err, a.row_log_lik = off(res.row_var, c0), off(res.row_sq_err, c0), off(res.row_log_lik, c0)
+            if stacked:                        # every draw in one forward: draw s = rows [s rows, (s+1) rows) of y
+                if wts is not None:
+                    self._predict_wn_sample(wts, None if map else d0)
+                self._predict_forward(bufs, wts, xc, S * rows, rows if S > 1 else 0, d0, row0 + c0, lrt)
+                y = res.draws if direct else ybuf
+                final_linear(S * rows, _p(y))
+                if one_call:
+                    a.y = _p(y)
+                    L.check(lib.vbnn_predict_moments(ctx, C.byref(a)))
+                else:
+                    for s in range(S):
+                        a.y, a.draw = off(y, s * rows * D), s
+                        L.check(lib.vbnn_predict_moments(ctx, C.byref(a)))
+                if keep_draws and not direct:
+                    res.draws[:, c0:c0 + rows].copy_(ybuf[:S * rows].view(S, rows, D))
+                continue
+            for s in range(S):                 # one draw per forward, the running moments in `state` between the launches
+                if wts is not None:
+                    self._predict_wn_sample(wts, d0 + s)
+                self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
+                yp = off(res.draws, (s * R + c0) * D) if direct else _p(ybuf)
+                final_linear(rows, yp)
+                a.y, a.draw = yp, s
+                L.check(lib.vbnn_predict_moments(ctx, C.byref(a)))
+        if not map:
+            self.draw += S
+            if self.device_draw:
+                L.check(lib.vbnn_sample(ctx, _p(self._draw_dev), S))
+        if has_t:
+            tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
+            res.totals = tot
+            res.mse, res.mean_draw_mse = tot[0] / (R * D), tot[1] / (R * S * D)
+            res.log_lik = tot[2] / R if noise_var is not None else None
+            res.mean_var = tot[3] / (R * D)
+        res.S, res.stacked, res.chunks = S, stacked, n_chunks
+        return res
 
     # ---- final Linear + criterion through the generic GEMM kernels (class counts above 16)
     def _generic_head(self, N, targets, inv_n, accumulate, backward=True):
