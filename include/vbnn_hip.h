@@ -584,6 +584,23 @@ int vbnn_mse_forward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* t
 int vbnn_mse_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
                       float inv_nd, float* g, int64_t ld_g);
 
+/* The heteroscedastic Gaussian likelihood (additive, ABI 6; not in the reference): the final Linear has 2 D outputs per row,
+ * columns [0, D) the mean m, columns [D, 2 D) s = the log of the noise variance; target is N x D. criterion:forward + :backward
+ * in ONE pass over y and target, the shape of vbnn_mse_forward: ld_y >= 2 D, g is N x 2 D (ld_g >= 2 D; optional in the forward),
+ * inv_nd = 1 / (GLOBAL rows x D). All element arithmetic is fp32, operation by operation as written (compiled without
+ * floating-point contraction; expf is the library function, not the fast intrinsic). Per element, with s_min <= s_max:
+ *   s_c = min(max(s, s_min), s_max) (a NaN s stays NaN);   w = expf(-s_c);   d = t - m;   e = 0.5f * (s_c + (d * d) * w)
+ *   loss_sum_dev[0] (+)= inv_nd * sum e      -- the negative log density WITHOUT its constant 0.5 log(2 pi) per element;
+ *   g_m = (inv_nd * (m - t)) * w;
+ *   g_s = (0.5f * inv_nd) * (1 - (d * d) * w), and exactly +0 where s < s_min or s > s_max (the clamp has no slope there).
+ * The sum is formed in double in a fixed order (block partials + one finish block, no float atomics: bitwise reproducible);
+ * accumulate = 0 stores it, 1 adds to it. A NaN in y reaches the loss and the two gradient elements of its own (row, output),
+ * and nothing else. vbnn_gauss_nll_backward: g alone, the same bits. */
+int vbnn_gauss_nll_forward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
+                           float inv_nd, float s_min, float s_max, float* g, int64_t ld_g, int accumulate, double* loss_sum_dev);
+int vbnn_gauss_nll_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
+                            float inv_nd, float s_min, float s_max, float* g, int64_t ld_g);
+
 /* mlp.lua:29-32 fused for a small class count (C <= 16): final nn.Linear + nn.LogSoftMax +
  * nn.ClassNLLCriterion as streaming kernels over the packed N x H activation `h` (dtype) and the packed
  * final weight `w3` (C x ld_w, dtype). Forward: logits = h w3^T + bias, out = logsoftmax,
@@ -726,6 +743,44 @@ typedef struct vbnn_moments_args {
     double* totals;
 } vbnn_moments_args;
 int vbnn_predict_moments(vbnn_ctx* ctx, const vbnn_moments_args* a);
+
+/* The heteroscedastic regression predictive (additive, ABI 6): vbnn_predict_moments for the Gaussian likelihood head of
+ * vbnn_gauss_nll_forward. A draw's row holds 2 D floats: columns [0, D) the mean m, columns [D, 2 D) s, the log of the noise
+ * variance. Everything stated for vbnn_predict_moments holds here -- fp32 op by op, the row-to-thread assignment, the butterfly
+ * and wave-order row sums (their order depends on D alone), the two forms bitwise equal, NaN containment -- with the element
+ * and row operations below. Each half of a row (m at column 0, s at column D) takes the 16-byte or the scalar access path on
+ * its own alignment. Per element (r, d) and draw, with s_c = min(max(s, s_min), s_max) (a NaN s stays NaN):
+ *   Welford on m, exactly as above:  delta = m - mean;  mean = mean + delta / float(s + 1);  M2 = M2 + delta * (m - mean)
+ *   v = expf(s_c);   V = v on draw 0, V = V + v on every later draw
+ *   with a target:  w = expf(-s_c);  d = t - m;  the element's term of q_s is  s_c + (d * d) * w
+ * Per row and draw, with a target: q_s = sum_d (s_c + (d * d) * w);  nll_s = 0.5f * q_s (the draw's negative log density without
+ * its constant); sum_s nll_s is kept as a running sum (draw 0 starts it); a_s = -nll_s goes into the online logsumexp: draw 0
+ * sets L = a_0, every later draw L = max(L, a) + log1p(exp(-|L - a|)).
+ * Finish per element: mean as it stands;  var = M2 / float(S) (the epistemic part);  noise_var = V / float(S) (the aleatoric
+ * part; the total predictive variance of an output is var + noise_var).
+ * Finish per row: row_var = (sum_d var) / float(D);  row_noise_var = (sum_d noise_var) / float(D);
+ *   row_sq_err = sum_d (t - mean)^2;  row_log_lik = L - log(float(S)) - (0.5f * float(D)) * log(6.2831855f)
+ * -- the log density of the equal-weight mixture of N(m_s, diag v_s) at the target. */
+#define VBNN_GAUSS_MOMENTS_STACKED_MAX_D 8192   /* largest D the STACKED form takes */
+typedef struct vbnn_gauss_moments_args {
+    const float* y; int64_t ld_y;       /* f32 outputs of the final Linear: S R x 2 D (STACKED) or R x 2 D (ACCUMULATE); ld_y >= 2 D */
+    const float* target; int64_t ld_t;  /* R x D regression targets, or NULL */
+    int64_t R, D, S;                    /* minibatch rows, outputs per row (the final Linear is 2 D wide), draws of the WHOLE prediction */
+    int32_t form;                       /* VBNN_MOMENTS_STACKED or VBNN_MOMENTS_ACCUMULATE */
+    int32_t draw;                       /* ACCUMULATE: as in vbnn_moments_args */
+    float s_min, s_max;                 /* the clamp of s (s_min <= s_max) */
+    float* state;                       /* ACCUMULATE: R x (3 D + 2) floats, row r = { mean[D], M2[D], V[D], sum_s nll_s, L } */
+    /* outputs of the finish, each optional (NULL to skip) */
+    float* mean; float* var; float* noise_var; int64_t ld_out;   /* R x D each */
+    float* row_var;                     /* R: mean over d of var */
+    float* row_noise_var;               /* R: mean over d of noise_var */
+    float* row_sq_err;                  /* R: sum_d (t - mean)^2 (needs target) */
+    float* row_log_lik;                 /* R (needs target) */
+    /* with target: 5 doubles WRITTEN by the finish, { sum_r row_sq_err, sum_{r,s} nll_s, sum_r row_log_lik, sum_{r,d} var,
+     * sum_{r,d} noise_var }, each summed over rows in double in a fixed order, as vbnn_moments_args.totals. NULL to skip. */
+    double* totals;
+} vbnn_gauss_moments_args;
+int vbnn_predict_gauss_moments(vbnn_ctx* ctx, const vbnn_gauss_moments_args* a);
 
 /* ---- signal-to-noise pruning (additive, ABI 6): mainviz.lua:20-27 on the device, and the pruned operand shadows that let
  * vbnn_forward / vbnn_head_predict evaluate the pruned network ---------------------------------------------------------------

@@ -202,6 +202,10 @@ int vbnn_mse_forward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* t
                      float inv_nd, float* g, int64_t ld_g, int accumulate, double* loss_sum_dev);
 int vbnn_mse_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
                       float inv_nd, float* g, int64_t ld_g);
+int vbnn_gauss_nll_forward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
+                           float inv_nd, float s_min, float s_max, float* g, int64_t ld_g, int accumulate, double* loss_sum_dev);
+int vbnn_gauss_nll_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
+                            float inv_nd, float s_min, float s_max, float* g, int64_t ld_g);
 int vbnn_head_forward(vbnn_ctx* ctx, int dtype, const void* h, int64_t ld_h, const void* w3, int64_t ld_w,
                       const float* bias, const int32_t* target, int64_t N, int64_t H, int64_t C, float inv_n,
                       float* logits, float* out, float* g_logits, int accumulate, double* loss_sum_dev,
@@ -270,6 +274,22 @@ typedef struct vbnn_moments_args {
     double* totals;
 } vbnn_moments_args;
 int vbnn_predict_moments(vbnn_ctx* ctx, const vbnn_moments_args* a);
+typedef struct vbnn_gauss_moments_args {
+    const float* y; int64_t ld_y;
+    const float* target; int64_t ld_t;
+    int64_t R, D, S;
+    int32_t form;
+    int32_t draw;
+    float s_min, s_max;
+    float* state;
+    float* mean; float* var; float* noise_var; int64_t ld_out;
+    float* row_var;
+    float* row_noise_var;
+    float* row_sq_err;
+    float* row_log_lik;
+    double* totals;
+} vbnn_gauss_moments_args;
+int vbnn_predict_gauss_moments(vbnn_ctx* ctx, const vbnn_gauss_moments_args* a);
 typedef struct vbnn_prune_desc {
     const float* means; const float* lvars; int64_t O, I;
     void* mu_p; void* var_p; int64_t ld_w;

@@ -108,6 +108,16 @@ MOMENTS_STACKED, MOMENTS_ACCUMULATE = 0, 1
 MOMENTS_STACKED_MAX_D = 4096          # VBNN_MOMENTS_STACKED_MAX_D
 
 
+class GaussMomentsArgs(C.Structure):  # vbnn_gauss_moments_args
+    _fields_ = [("y", _vp), ("ld_y", _i64), ("target", _vp), ("ld_t", _i64), ("R", _i64), ("D", _i64), ("S", _i64),
+                ("form", C.c_int32), ("draw", C.c_int32), ("s_min", _f), ("s_max", _f), ("state", _vp),
+                ("mean", _vp), ("var", _vp), ("noise_var", _vp), ("ld_out", _i64), ("row_var", _vp), ("row_noise_var", _vp),
+                ("row_sq_err", _vp), ("row_log_lik", _vp), ("totals", _vp)]
+
+
+GAUSS_MOMENTS_STACKED_MAX_D = 8192    # VBNN_GAUSS_MOMENTS_STACKED_MAX_D
+
+
 class PruneDesc(C.Structure):         # vbnn_prune_desc
     _fields_ = [("means", _vp), ("lvars", _vp), ("O", _i64), ("I", _i64), ("mu_p", _vp), ("var_p", _vp), ("ld_w", _i64),
                 ("stats", _vp), ("mask", _vp)]
@@ -221,6 +231,9 @@ _SIGS = {
                            _vp, _i64, _vp, _vp, _i64], _i),
     "vbnn_mse_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _vp, _i64, _i, _vp], _i),
     "vbnn_mse_backward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _vp, _i64], _i),
+    "vbnn_gauss_nll_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _f, _f, _vp, _i64, _i, _vp], _i),
+    "vbnn_gauss_nll_backward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _f, _f, _vp, _i64], _i),
+    "vbnn_predict_gauss_moments": ([_vp, C.POINTER(GaussMomentsArgs)], _i),
     "vbnn_snr": ([_vp, _vp, _vp, _i64, _vp], _i),
     "vbnn_prune_workspace_bytes": ([_i, _vp, C.POINTER(C.c_size_t)], _i),
     "vbnn_prune_select": ([_vp, _i, _vp, _i64, _vp, _vp, C.c_size_t], _i),

@@ -641,6 +641,87 @@ extern "C" int vbnn_mse_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, co
     VBNN_API_END
 }
 
+// ---------------------------------------------------------------------------------- Gaussian likelihood criterion
+// The heteroscedastic head (include/vbnn_hip.h): a row of y is { m[D], s[D] }, s the log of the noise variance. One pass over
+// y and target (12 B read + 8 B written per target element, two expf per element; measured against those bytes in
+// profiles/gauss_predict_bench.json): both gradient
+// halves and the block partials of sum 0.5 (s_c + d^2 w); k_mse_finish adds them in a fixed order. The two halves of a row
+// and of g take the 16-byte path each on its own alignment (the s half starts at column D).
+__device__ __forceinline__ float gauss_clamp(float s, float s_min, float s_max) {
+    return s != s ? s : fminf(fmaxf(s, s_min), s_max);     // fmaxf / fminf drop a NaN: keep it
+}
+__global__ __launch_bounds__(256) void k_gauss_nll(const float* __restrict__ y, int64_t ld_y, const float* __restrict__ t, int64_t ld_t,
+                                                   int64_t N, int64_t D, float inv_nd, float s_min, float s_max, float* g, int64_t ld_g,
+                                                   double* partial) {
+    __shared__ double sh[4];
+    double acc = 0.0;
+    const bool d4 = (D & 3) == 0;
+    const bool m_vec = d4 && ((ld_y & 3) == 0) && (((uintptr_t)y & 15u) == 0);
+    const bool s_vec = d4 && ((ld_y & 3) == 0) && ((((uintptr_t)y + 4 * (uintptr_t)D) & 15u) == 0);
+    const bool t_vec = d4 && ((ld_t & 3) == 0) && (((uintptr_t)t & 15u) == 0);
+    const bool gm_vec = d4 && ((ld_g & 3) == 0) && (((uintptr_t)g & 15u) == 0);
+    const bool gs_vec = d4 && ((ld_g & 3) == 0) && ((((uintptr_t)g + 4 * (uintptr_t)D) & 15u) == 0);
+    const float half_inv = 0.5f * inv_nd;
+    const int64_t D4 = (D + 3) >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N * D4; i += (int64_t)gridDim.x * 256) {
+        const int64_t n = i / D4, d = (i - n * D4) * 4;
+        const int valid = (int)min((int64_t)4, D - d);
+        float mv[4], sv[4], tv[4], gm[4], gs[4];
+        load4<float>(y + n * ld_y + d, mv, valid, m_vec);
+        load4<float>(y + n * ld_y + D + d, sv, valid, s_vec);
+        load4<float>(t + n * ld_t + d, tv, valid, t_vec);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            gm[j] = gs[j] = 0.f;
+            if (j < valid) {
+                const float sc = gauss_clamp(sv[j], s_min, s_max);
+                const float w = expf(-sc);
+                const float df = tv[j] - mv[j];
+                const float dw = (df * df) * w;
+                acc += (double)(0.5f * (sc + dw));
+                gm[j] = (inv_nd * (mv[j] - tv[j])) * w;
+                gs[j] = (sv[j] < s_min || sv[j] > s_max) ? 0.f : half_inv * (1.f - dw);
+            }
+        }
+        if (g) {
+            store4<float>(g + n * ld_g + d, gm[0], gm[1], gm[2], gm[3], valid, gm_vec);
+            store4<float>(g + n * ld_g + D + d, gs[0], gs[1], gs[2], gs[3], valid, gs_vec);
+        }
+    }
+    if (partial) {
+        const double r = block_sum(acc, sh);
+        if (threadIdx.x == 0) partial[blockIdx.x] = r;
+    }
+}
+static int gauss_nll_launch(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* t, int64_t ld_t, int64_t N, int64_t D,
+                            float inv_nd, float s_min, float s_max, float* g, int64_t ld_g, int accumulate, double* loss) {
+    const int nb = grid_for(N * ((D + 3) / 4), 256 * 4);
+    if ((size_t)nb > ctx->scratch_doubles) { vbnn_set_error("scratch"); return VBNN_ERR_INVALID; }
+    hipLaunchKernelGGL(k_gauss_nll, dim3(nb), dim3(256), 0, ctx->stream, y, ld_y, t, ld_t, N, D, inv_nd, s_min, s_max, g, ld_g,
+                       loss ? ctx->scratch : nullptr);
+    if (loss) hipLaunchKernelGGL(k_mse_finish, dim3(1), dim3(256), 0, ctx->stream, ctx->scratch, nb, (double)inv_nd, accumulate, loss);
+    return vbnn_check_launch("k_gauss_nll");
+}
+extern "C" int vbnn_gauss_nll_forward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N,
+                                      int64_t D, float inv_nd, float s_min, float s_max, float* g, int64_t ld_g, int accumulate,
+                                      double* loss_sum_dev) {
+    VBNN_API_BEGIN
+    VBNN_REQUIRE(ctx && y && target && loss_sum_dev, "null argument");
+    VBNN_REQUIRE(N > 0 && D > 0 && ld_y >= 2 * D && ld_t >= D && (!g || ld_g >= 2 * D), "shape");
+    VBNN_REQUIRE(s_min <= s_max, "the clamp: s_min <= s_max");
+    return gauss_nll_launch(ctx, y, ld_y, target, ld_t, N, D, inv_nd, s_min, s_max, g, ld_g, accumulate, loss_sum_dev);
+    VBNN_API_END
+}
+extern "C" int vbnn_gauss_nll_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N,
+                                       int64_t D, float inv_nd, float s_min, float s_max, float* g, int64_t ld_g) {
+    VBNN_API_BEGIN
+    VBNN_REQUIRE(ctx && y && target && g, "null argument");
+    VBNN_REQUIRE(N > 0 && D > 0 && ld_y >= 2 * D && ld_t >= D && ld_g >= 2 * D, "shape");
+    VBNN_REQUIRE(s_min <= s_max, "the clamp: s_min <= s_max");
+    return gauss_nll_launch(ctx, y, ld_y, target, ld_t, N, D, inv_nd, s_min, s_max, g, ld_g, 0, nullptr);
+    VBNN_API_END
+}
+
 // ---------------------------------------------------------------------------------- separate criterion modules
 // nn.ClassNLLCriterion (sizeAverage): forward value, backward gradient; nn.LogSoftMax:updateGradInput.
 // Used by the module-level path (mlp.lua:78-80 call order); the fused kernel above is the fast path.

@@ -47,7 +47,11 @@ class Dataset(dict):
         hi = min(index + batchSize, n)
         x = self["inputs"]
         inputs = np.zeros((batchSize, 1) + tuple(x.shape[1:]), dtype=np.float32)
-        targets = np.zeros(batchSize, dtype=np.int64)
+        t = np.asarray(self["targets"])
+        if t.ndim == 1:
+            targets = np.zeros(batchSize, dtype=np.int64)
+        else:                                               # regression targets (criterion "mse" / "gauss"): [n, D] floats
+            targets = np.zeros((batchSize,) + tuple(t.shape[1:]), dtype=np.float32)
         inputs[: hi - index, 0] = x[index:hi]
         targets[: hi - index] = self["targets"][index:hi]
         return inputs, targets

@@ -98,12 +98,18 @@ class RegressionPredictResult:
     noise_var, row_log_lik (R: the log density of the equal-weight mixture of N(f_s(x), noise_var I) at t); draws (S x R x D)
     with keep_draws. With targets also Python floats: totals (the library's four sums), mse (of the predictive mean),
     mean_draw_mse (the mean over draws of each draw's MSE: test()'s number), log_lik (mean row_log_lik; None without noise_var)
-    and mean_var."""
+    and mean_var.
+    criterion = "gauss" (the network predicts its own noise; None for "mse"): noise_var (R x D: 1/S sum_s exp(s_c), the
+    aleatoric part -- the total predictive variance is var + noise_var), row_noise_var (R: its mean over the outputs), and with
+    targets mean_noise_var and mean_draw_nll (the mean over draws of each draw's Gaussian criterion: test()'s number); totals
+    then has five sums, mean_draw_mse is None, draws is S x R x 2 D and row_log_lik / log_lik are those of the mixture of
+    N(m_s, diag exp(s_s))."""
 
     def __init__(self, mean, var, row_var, row_sq_err, row_log_lik, draws):
         self.mean, self.var, self.row_var = mean, var, row_var
         self.row_sq_err, self.row_log_lik, self.draws = row_sq_err, row_log_lik, draws
         self.totals = self.mse = self.mean_draw_mse = self.log_lik = self.mean_var = None
+        self.noise_var = self.row_noise_var = self.mean_noise_var = self.mean_draw_nll = None
         self.S, self.stacked, self.chunks = None, None, None
 
 
@@ -278,9 +284,18 @@ class FusedMLP:
         self._dx_first_opt = opt.get("dx_first", None)      # None: decided from the layer sizes once they are known (below)
         self.fuse_kl = bool(opt.get("fuse_kl", True))
         # "nll": LogSoftMax + ClassNLLCriterion (mlp.lua:30-32); "mse": nn.MSECriterion on the final Linear's outputs
-        # (BASELINE.json configs[4], a regression target of n_classes dimensions -- not in the reference)
+        # (BASELINE.json configs[4], a regression target of n_classes dimensions -- not in the reference); "gauss": the
+        # heteroscedastic Gaussian likelihood (vbnn_gauss_nll_forward) -- the final Linear's n_classes = 2 D outputs are D means
+        # and D log noise variances, the targets R x D; opt.logvar_clamp = (s_min, s_max) clamps the log variance
         self.criterion = opt.get("criterion", "nll")
-        assert self.criterion in ("nll", "mse")
+        assert self.criterion in ("nll", "mse", "gauss")
+        self.logvar_clamp = tuple(float(v) for v in opt.get("logvar_clamp", (-20.0, 20.0)))
+        if self.criterion == "gauss":
+            if int(opt["n_classes"]) % 2:
+                raise ValueError(f"criterion = 'gauss': the final Linear holds D means and D log variances (n_classes = "
+                                 f"{opt['n_classes']} is odd)")
+            if not (len(self.logvar_clamp) == 2 and self.logvar_clamp[0] <= self.logvar_clamp[1]):
+                raise ValueError(f"opt.logvar_clamp = {self.logvar_clamp}: (s_min, s_max) with s_min <= s_max")
         self.kl_from_shadows = self.dtype == "bf16" and bool(opt.get("kl_from_shadows", True))
         # opt.kl_in_update: the gradient arena holds the LIKELIHOOD parts only (vbnn_dw_args.kl_scale = 0) and update() adds the
         # KL gradient from the fp32 means / lvars (vbnn_update_desc.kl_add) -- exact, where the epilogue's shadow form carries
@@ -668,7 +683,8 @@ class FusedMLP:
         if Cn > 16:
             raise ValueError(f"predict: the predictive head takes at most 16 classes (n_classes = {Cn})")
         if self.criterion != "nll":
-            raise ValueError("predict: a class-probability predictive needs the NLL criterion (criterion = 'mse' has none)")
+            raise ValueError(f"predict: a class-probability predictive needs the NLL criterion (criterion = '{self.criterion}' has "
+                             "none: use predict_regression)")
         map = bool(map or self.opt.get("quicktest"))
         S = 1 if map else int(self.opt["testSamples"] if S is None else S)
         if S < 1:
@@ -848,11 +864,18 @@ class FusedMLP:
         """E[y | x, D] ~ 1/S sum_s f_s(x) over draws self.draw + 1 .. self.draw + S, with the draws' variance per output; S, map
         and row0 as predict(), and `self.draw` advances by S likewise. targets: R x D fp32. noise_var (tau^2 > 0, or None): the
         observation noise of the predictive log-likelihood. keep_draws: the S x R x D outputs are returned too. Returns a
-        RegressionPredictResult of this rank's rows (no collective, as test())."""
+        RegressionPredictResult of this rank's rows (no collective, as test()).
+        criterion = "gauss": D = n_classes / 2, the network supplies the noise (noise_var must be None), the result carries the
+        aleatoric noise_var beside the epistemic var, and keep_draws returns the S x R x 2 D outputs (means, log variances)."""
         lib, ctx, code = L.lib(), self.ctx.h, self.code
-        D = self.n_classes
-        if self.criterion != "mse":
-            raise ValueError("predict_regression: the regression predictive needs the MSE criterion (criterion = 'nll': use predict)")
+        if self.criterion not in ("mse", "gauss"):
+            raise ValueError("predict_regression: the regression predictive needs the MSE criterion or the Gaussian one "
+                             "(criterion = 'nll': use predict)")
+        gauss = self.criterion == "gauss"
+        Wd = self.n_classes                                          # the final Linear's width: D, or { m[D], s[D] }
+        D = Wd // 2 if gauss else Wd
+        if gauss and noise_var is not None:
+            raise ValueError("predict_regression: criterion = 'gauss' predicts its own noise variance (noise_var must be None)")
         if noise_var is not None:
             noise_var = float(noise_var)
             if not (noise_var > 0.0 and math.isfinite(noise_var)):
@@ -865,6 +888,9 @@ class FusedMLP:
         R = x.shape[0]
         assert x.shape[1] == self.sizes[0] and x.dtype == torch.float32 and x.is_cuda and R > 0
         if targets is not None:
+            if gauss and tuple(targets.shape) != (R, D):
+                raise ValueError(f"predict_regression: targets of shape {tuple(targets.shape)} (criterion = 'gauss' takes R x D = "
+                                 f"{R} x {D}: one target per mean)")
             assert targets.dtype == torch.float32 and targets.is_cuda and tuple(targets.shape) == (R, D)
             targets = targets.contiguous()
         row0 = self.rank * R if row0 is None else int(row0)
@@ -889,28 +915,36 @@ class FusedMLP:
         has_t = targets is not None
         res = RegressionPredictResult(torch.empty(R, D, **f32), torch.empty(R, D, **f32), torch.empty(R, **f32),
                                       torch.empty(R, **f32) if has_t else None,
-                                      torch.empty(R, **f32) if (has_t and noise_var is not None) else None,
-                                      torch.empty(S, R, D, **f32) if keep_draws else None)
+                                      torch.empty(R, **f32) if (has_t and (gauss or noise_var is not None)) else None,
+                                      torch.empty(S, R, Wd, **f32) if keep_draws else None)
+        if gauss:
+            res.noise_var, res.row_noise_var = torch.empty(R, D, **f32), torch.empty(R, **f32)
         direct = keep_draws and (not stacked or n_chunks == 1)      # the final Linear writes into res.draws itself
         ybuf = None
         if not direct:                                               # the y buffer: kept with the predict buffers
             ybuf = getattr(bufs, "y_reg", None)
-            if ybuf is None or tuple(ybuf.shape) != (op_rows, D):
-                ybuf = bufs.y_reg = torch.empty(op_rows, D, **f32)
-        one_call = stacked and D <= L.MOMENTS_STACKED_MAX_D         # else: one ACCUMULATE call per draw
-        state = None if one_call else torch.empty(Rc, 2 * D + 2, **f32)
-        totals = torch.zeros(n_chunks, 4, dtype=torch.float64, device=self.device) if has_t else None
+            if ybuf is None or tuple(ybuf.shape) != (op_rows, Wd):
+                ybuf = bufs.y_reg = torch.empty(op_rows, Wd, **f32)
+        one_call = stacked and D <= (L.GAUSS_MOMENTS_STACKED_MAX_D if gauss else L.MOMENTS_STACKED_MAX_D)   # else: ACCUMULATE per draw
+        state = None if one_call else torch.empty(Rc, (3 if gauss else 2) * D + 2, **f32)
+        totals = torch.zeros(n_chunks, 5 if gauss else 4, dtype=torch.float64, device=self.device) if has_t else None
         d0 = self.draw + 1
         nl, H = len(self.vb), self.sizes[-1]
-        a = L.MomentsArgs(ld_y=D, ld_t=D, D=D, S=S, form=L.MOMENTS_STACKED if one_call else L.MOMENTS_ACCUMULATE,
-                          noise_var=noise_var or 0.0, state=_p(state), ld_out=D)
+        form = L.MOMENTS_STACKED if one_call else L.MOMENTS_ACCUMULATE
+        if gauss:
+            a = L.GaussMomentsArgs(ld_y=Wd, ld_t=D, D=D, S=S, form=form, s_min=self.logvar_clamp[0], s_max=self.logvar_clamp[1],
+                                   state=_p(state), ld_out=D)
+            moments = lib.vbnn_predict_gauss_moments
+        else:
+            a = L.MomentsArgs(ld_y=D, ld_t=D, D=D, S=S, form=form, noise_var=noise_var or 0.0, state=_p(state), ld_out=D)
+            moments = lib.vbnn_predict_moments
 
         def off(t, row):
             return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
 
         def final_linear(N, y_ptr):
             fa = L.FwdArgs(w=self.w3_s.ptr, w2=None, x=bufs[nl].x.ptr, x2=None, ld_w=self.w3_s.ld, ld_x=bufs[nl].x.ld,
-                           N=N, I=H, O=D, bias=_p(self.bias3), y=y_ptr, ld_y=D)
+                           N=N, I=H, O=Wd, bias=_p(self.bias3), y=y_ptr, ld_y=Wd)
             L.check(lib.vbnn_forward(ctx, code, C.byref(fa)))
 
         for k in range(n_chunks):
@@ -922,6 +956,8 @@ class FusedMLP:
             a.totals = C.c_void_p(totals[k].data_ptr()) if has_t else None
             a.mean, a.var = off(res.mean, c0 * D), off(res.var, c0 * D)
             a.row_var, a.row_sq_err, a.row_log_lik = off(res.row_var, c0), off(res.row_sq_err, c0), off(res.row_log_lik, c0)
+            if gauss:
+                a.noise_var, a.row_noise_var = off(res.noise_var, c0 * D), off(res.row_noise_var, c0)
             if stacked:                        # every draw in one forward: draw s = rows [s rows, (s+1) rows) of y
                 if wts is not None:
                     self._predict_wn_sample(wts, None if map else d0)
@@ -930,22 +966,22 @@ class FusedMLP:
                 final_linear(S * rows, _p(y))
                 if one_call:
                     a.y = _p(y)
-                    L.check(lib.vbnn_predict_moments(ctx, C.byref(a)))
+                    L.check(moments(ctx, C.byref(a)))
                 else:
                     for s in range(S):
-                        a.y, a.draw = off(y, s * rows * D), s
-                        L.check(lib.vbnn_predict_moments(ctx, C.byref(a)))
+                        a.y, a.draw = off(y, s * rows * Wd), s
+                        L.check(moments(ctx, C.byref(a)))
                 if keep_draws and not direct:
-                    res.draws[:, c0:c0 + rows].copy_(ybuf[:S * rows].view(S, rows, D))
+                    res.draws[:, c0:c0 + rows].copy_(ybuf[:S * rows].view(S, rows, Wd))
                 continue
             for s in range(S):                 # one draw per forward, the running moments in `state` between the launches
                 if wts is not None:
                     self._predict_wn_sample(wts, d0 + s)
                 self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
-                yp = off(res.draws, (s * R + c0) * D) if direct else _p(ybuf)
+                yp = off(res.draws, (s * R + c0) * Wd) if direct else _p(ybuf)
                 final_linear(rows, yp)
                 a.y, a.draw = yp, s
-                L.check(lib.vbnn_predict_moments(ctx, C.byref(a)))
+                L.check(moments(ctx, C.byref(a)))
         if not map:
             self.draw += S
             if self.device_draw:
@@ -953,8 +989,12 @@ class FusedMLP:
         if has_t:
             tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
             res.totals = tot
-            res.mse, res.mean_draw_mse = tot[0] / (R * D), tot[1] / (R * S * D)
-            res.log_lik = tot[2] / R if noise_var is not None else None
+            res.mse = tot[0] / (R * D)
+            if gauss:
+                res.mean_draw_nll, res.mean_noise_var = tot[1] / (R * S * D), tot[4] / (R * D)
+            else:
+                res.mean_draw_mse = tot[1] / (R * S * D)
+            res.log_lik = tot[2] / R if (gauss or noise_var is not None) else None
             res.mean_var = tot[3] / (R * D)
         res.S, res.stacked, res.chunks = S, stacked, n_chunks
         return res
@@ -971,6 +1011,13 @@ class FusedMLP:
             assert targets.dtype == torch.float32 and tuple(targets.shape) == (N, Cn) and targets.is_contiguous()
             L.check(lib.vbnn_mse_forward(ctx, _p(self.logits), Cn, _p(targets), Cn, N, Cn, inv_n / Cn, _p(self.g_logits), Cn,
                                          accumulate, _p(self._acc)))
+            if not accumulate:
+                L.check(lib.vbnn_buf_zero(ctx, _p(self._corr), 4))
+        elif self.criterion == "gauss":
+            D = Cn // 2
+            assert targets.dtype == torch.float32 and tuple(targets.shape) == (N, D) and targets.is_contiguous()
+            L.check(lib.vbnn_gauss_nll_forward(ctx, _p(self.logits), Cn, _p(targets), D, N, D, inv_n / D, self.logvar_clamp[0],
+                                               self.logvar_clamp[1], _p(self.g_logits), Cn, accumulate, _p(self._acc)))
             if not accumulate:
                 L.check(lib.vbnn_buf_zero(ctx, _p(self._corr), 4))
         else:
@@ -1520,11 +1567,12 @@ class FusedMLP:
 
     def synthetic_targets(self, x, row0=0):
         """bench / tests: class targets uniform in 0..n_classes-1 by GLOBAL row (data.lua:16 convention, 0-based); for the
-        regression criterion y* = x R / sqrt(I) with a fixed Philox-drawn R -- data
-        preparation outside the timed step, so a plain torch matmul."""
+        regression criteria y* = x R / sqrt(I) with a fixed Philox-drawn R (D columns: n_classes
+        for "mse", n_classes / 2 for "gauss") -- data preparation outside the timed step, so a plain torch matmul."""
         N = x.shape[0]
-        if self.criterion == "mse":
-            R = torch.empty(x.shape[1], self.n_classes, dtype=torch.float32, device=x.device)
+        if self.criterion in ("mse", "gauss"):
+            D = self.n_classes if self.criterion == "mse" else self.n_classes // 2
+            R = torch.empty(x.shape[1], D, dtype=torch.float32, device=x.device)
             fill_normal(R, self.seed, L.STREAM_DATA, 1, 0)
             return (x @ R / math.sqrt(x.shape[1])).contiguous()
         return ((torch.arange(N, device=x.device, dtype=torch.int64) + row0) * 2654435761 % self.n_classes).to(torch.int32)

@@ -64,7 +64,8 @@ class Main:
 
     def _to_device(self, inputs, targets):
         x = torch.from_numpy(np.ascontiguousarray(inputs, dtype=np.float32)).to(self.device)
-        t = torch.from_numpy(np.ascontiguousarray(targets)).to(self.device, dtype=torch.int32)
+        regression = getattr(self.net, "criterion", "nll") in ("mse", "gauss")           # R x D fp32 targets; class labels otherwise
+        t = torch.from_numpy(np.ascontiguousarray(targets)).to(self.device, dtype=torch.float32 if regression else torch.int32)
         return x, t
 
     def train(self, dataset):                                                             # main.lua:12-50
@@ -109,14 +110,32 @@ class Main:
         bs, n = int(opt["testBatchSize"]), int(opt["testSize"])
         starts = list(range(0, n - bs + 1, bs))
         accuracy = error = 0.0
+        criterion = getattr(net, "criterion", "nll")
+        regression = criterion in ("mse", "gauss")
+        # opt.predictive with a regression criterion: the predictive log-likelihood (gauss: the network's own noise; mse: only
+        # with opt.noise_var), the epistemic variance and, for gauss, the aleatoric one -- FusedMLP.predict_regression
+        tau2 = opt.get("noise_var") if criterion == "mse" else None
         pred = {"devacc_pred": 0.0, "devnll_pred": 0.0, "dev_mi": 0.0}
+        if regression:
+            pred = {"dev_epi_var": 0.0}
+            if criterion == "gauss":
+                pred.update(devll_pred=0.0, dev_noise_var=0.0)
+            elif tau2 is not None:
+                pred["devll_pred"] = 0.0
         for t0 in starts:
             inputs, targets = dataset.create_minibatch(t0, bs, n, opt.get("geometry"))
             x, t = self._to_device(inputs, targets)
             err, acc = net.test(x, t)
             accuracy += acc
             error += err
-            if opt.get("predictive"):      # the S-draw model average on the same minibatch (its own draws, after test()'s)
+            if opt.get("predictive") and regression:
+                r = net.predict_regression(x, targets=t, noise_var=tau2)
+                pred["dev_epi_var"] += r.mean_var
+                if "devll_pred" in pred:
+                    pred["devll_pred"] += r.log_lik
+                if "dev_noise_var" in pred:
+                    pred["dev_noise_var"] += r.mean_noise_var
+            elif opt.get("predictive"):    # the S-draw model average on the same minibatch (its own draws, after test()'s)
                 r = net.predict(x, targets=t)
                 pred["devacc_pred"] += r.accuracy
                 pred["devnll_pred"] += r.nll
@@ -184,7 +203,8 @@ class Main:
                 rec["held fraction"] = (sum(held) / sum(v.O * v.I for v in self.net.vb)) if held else 0.0
             rec.update(self._prune_series(testSet))       # opt.prune_report / opt.prune_eval (both off by default)
             if self.log:
-                for k in ("devacc", "trainacc", "deverr", "trainerr", "lc", "devacc_pred", "devnll_pred", "dev_mi"):   # main.lua:169-177 (+ opt.predictive)
+                for k in ("devacc", "trainacc", "deverr", "trainerr", "lc", "devacc_pred", "devnll_pred", "dev_mi", "devll_pred", "dev_epi_var",
+                          "dev_noise_var"):   # main.lua:169-177 (+ opt.predictive)
                     if k in rec:
                         self.log.add(k, rec[k])
                 for k in rec:
