@@ -58,9 +58,9 @@ def test_predict_surface():
     assert r.nll is None and r.mean_draw_accuracy is None
 
 
-# ---- the three hosts' predict: lua/FusedMLP.lua (no interpreter here: linted), tools/c_host.c (run by the GPU tests), engine.py
-HOST_ONLY_WN = ("vbnn_wn_sample", "vbnn_pack")        # engine.py's weight-noise draws: the Lua and C hosts are LRT hosts
-READ_BACK = ("vbnn_buf_download",)                    # the totals' read-back, which engine.py does through torch (.cpu())
+# ---- the three hosts' predict: lua/FusedMLP.lua (no interpreter here: linted), tools/c_host.c (run by the GPU tests), FusedMLP
+HOST_ONLY_WN = ("vbnn_wn_sample", "vbnn_pack")        # the engine's weight-noise draws: the Lua and C hosts are LRT hosts
+READ_BACK = ("vbnn_buf_download",)                    # the totals' read-back, which the engine does through torch (.cpu())
 
 
 def _section(txt, start, end):
@@ -68,13 +68,21 @@ def _section(txt, start, end):
     return txt[i:txt.index(end, i + len(start))]
 
 
+def _src(name):
+    """The text of FusedMLP.<name>, whichever module of the engine defines it (through the stream-ordering wrapper)."""
+    import inspect
+    from vbnn_amd.engine import FusedMLP
+    return inspect.getsource(getattr(FusedMLP, name))
+
+
 def _ordered_calls(body, call_re, helpers, drop=()):
-    """Library calls of `body` in source order, a helper's calls in place of each call of it, consecutive repeats folded."""
+    """Library calls of `body` in source order, a helper's calls (and its helpers') in place of each call of it, consecutive
+    repeats folded."""
     pat = "|".join([call_re] + [re.escape(h) for h in helpers])
     out = []
     for m in re.finditer(pat, body):
         tok = m.group(0)
-        names = _ordered_calls(helpers[tok], call_re, {}) if tok in helpers else [m.group(1)]
+        names = _ordered_calls(helpers[tok], call_re, helpers) if tok in helpers else [m.group(1)]
         for n in names:
             if n not in drop and (not out or out[-1] != n):
                 out.append(n)
@@ -96,10 +104,8 @@ def _c_fn(c, name):
 
 
 def _host_orders():
-    eng = open(os.path.join(ROOT, "vbnn_amd", "engine.py")).read()
-    py = _ordered_calls(_section(eng, "    def predict(", "    def _predict_stacked("), r"lib\.(vbnn_[a-z0-9_]+)\(",
-                        {"self._predict_forward(": _section(eng, "    def _predict_forward(", "    # ---- mlp.lua:69-74"),
-                         "self._predict_wn_sample(": _section(eng, "    def _predict_wn_sample(", "    def _predict_forward(")},
+    py = _ordered_calls(_src("predict"), r"lib\.(vbnn_[a-z0-9_]+)\(",
+                        {"self.%s(" % h: _src(h) for h in ("_predictive_plan", "_predict_wn_sample", "_predict_forward", "_consume_draws")},
                         drop=HOST_ONLY_WN)
     _, lua = _lua()
     lu = _ordered_calls(_section(lua, "function FusedMLP:predict(", "function FusedMLP:_predict_forward("), r"\bC\.(vbnn_[a-z0-9_]+)\s*\(",
@@ -111,7 +117,7 @@ def _host_orders():
 
 
 def test_the_three_hosts_issue_predict_calls_in_the_same_order():
-    """engine.predict, lua FusedMLP:predict and c_host's fm_predict: the same library calls in the same order (the stacked
+    """FusedMLP.predict, lua FusedMLP:predict and c_host's fm_predict: the same library calls in the same order (the stacked
     branch, the one-draw branch, the device counter), so what the GPU test proves of the C program holds for the Lua file."""
     py, lu, cc = _host_orders()
     assert py == lu == cc, (py, lu, cc)

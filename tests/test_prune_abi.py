@@ -58,23 +58,22 @@ def test_prune_entry_points_are_exported_and_declared_everywhere():
 
 
 def test_the_three_hosts_issue_prune_calls_in_the_same_order():
-    """engine.prune, lua FusedMLP:prune and c_host's fm_prune: the same library calls in the same order, so what the GPU test
+    """FusedMLP.prune, lua FusedMLP:prune and c_host's fm_prune: the same library calls in the same order, so what the GPU test
     proves of the C program holds for the Lua file."""
     sys.path.insert(0, ROOT)
-    from tests.test_predict_abi import READ_BACK, _c_fn, _lua, _ordered_calls, _section
-    eng = open(os.path.join(ROOT, "vbnn_amd", "engine.py")).read()
-    py = _ordered_calls(_section(eng, "    def prune(", "    def _prune_mask("), r"lib\.(vbnn_[a-z0-9_]+)\(", {})
+    from tests.test_predict_abi import READ_BACK, _c_fn, _lua, _ordered_calls, _section, _src
+    py = _ordered_calls(_src("prune"), r"lib\.(vbnn_[a-z0-9_]+)\(", {})
     raw, lua = _lua()
     lu = _ordered_calls(_section(lua, "function FusedMLP:prune(", "function FusedMLP:use_pruned("), r"\bC\.(vbnn_[a-z0-9_]+)\s*\(",
                         {}, drop=READ_BACK)
     c = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "tools", "c_host.c")).read(), flags=re.S)
     cc = _ordered_calls(_c_fn(c, "fm_prune"), r"\b(vbnn_[a-z0-9_]+)\s*\(", {}, drop=READ_BACK)
     assert py == lu == cc == ["vbnn_prune_workspace_bytes", "vbnn_prune_select", "vbnn_prune_pack"], (py, lu, cc)
-    # placement: outside the ranges the predict lints slice, and outside run .. finish
+    # placement: outside the ranges the predict lints slice, and outside run .. finish; the predict functions do not prune
     assert raw.index("function FusedMLP:loss_and_accuracy") < raw.index("function FusedMLP:prune(") < \
         raw.index("function FusedMLP:use_pruned(") < raw.index("function FusedMLP:predict(")
-    for a, b in (("    def predict(", "    def _predict_stacked("), ("    def _predict_forward(", "    # ---- mlp.lua:69-74")):
-        assert "vbnn_prune" not in _section(eng, a, b) and "vbnn_snr" not in _section(eng, a, b)
+    for fn in ("predict", "_predictive_plan", "_consume_draws", "_predict_forward"):
+        assert "vbnn_prune" not in _src(fn) and "vbnn_snr" not in _src(fn), fn
     for fn in ("fm_predict", "fm_predict_forward"):
         assert "vbnn_prune" not in _c_fn(c, fn)
     assert "vbnn_prune" not in raw[raw.index("function FusedMLP:predict("):]
@@ -94,8 +93,8 @@ def test_prune_surface():
     assert list(inspect.signature(FusedMLP.use_pruned).parameters) == ["self", "result"]
     assert list(inspect.signature(FusedMLP.pruned).parameters) == ["self", "result"]
     sig = inspect.signature(FusedMLP.prune_curve)
-    assert list(sig.parameters) == ["self", "inputs", "targets", "fractions", "S", "map", "scope"]
-    assert (sig.parameters["S"].default, sig.parameters["map"].default, sig.parameters["scope"].default) == (None, False, "global")
+    assert list(sig.parameters) == ["self", "inputs", "targets", "fractions", "S", "map", "scope", "compress"]
+    assert [sig.parameters[n].default for n in ("S", "map", "scope", "compress")] == [None, False, "global", False]
     r = PruneResult(None, "layer", [0.5, 0.25], [(1.0, 0.5, 8.0, 4.0), (0.0, 0.0, 6.0, 6.0)], ["m0", "m1"], ["v0", "v1"], 7)
     assert r.tau == [0.5, 0.25] and r.scope == "layer" and r.version == 7 and r.mu_p == ["m0", "m1"]
     assert (r.n_pruned, r.W, r.fraction_pruned, r.mean_var, r.mean_pruned_var) == (1, 10, 0.1, 1.4, 0.5)

@@ -67,30 +67,27 @@ def test_sparse_entry_points_are_exported_and_declared_everywhere():
 
 
 def test_the_three_hosts_issue_sparse_calls_in_the_same_order():
-    """engine._compress / _predict_forward_sparse, lua FusedMLP:compress / :_predict_forward_sparse and c_host's fm_compress /
-    fm_predict_forward_sparse: the same library calls in the same order, outside every range the predict and prune lints slice,
-    reached from each host's _predict_forward by an early return."""
-    from tests.test_predict_abi import READ_BACK, _c_fn, _lua, _ordered_calls, _section
-    eng = open(os.path.join(ROOT, "vbnn_amd", "engine.py")).read()
+    """FusedMLP._compress / _predict_forward_sparse, lua FusedMLP:compress / :_predict_forward_sparse and c_host's fm_compress /
+    fm_predict_forward_sparse: the same library calls in the same order, in no function (Python) or range (Lua, C) the predict and
+    prune lints read, reached from each host's _predict_forward by an early return."""
+    from tests.test_predict_abi import READ_BACK, _c_fn, _lua, _ordered_calls, _section, _src
     raw, lua = _lua()
     c = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "tools", "c_host.c")).read(), flags=re.S)
     py_re, lua_re, c_re = r"lib\.(vbnn_[a-z0-9_]+)\(", r"\bC\.(vbnn_[a-z0-9_]+)\s*\(", r"\b(vbnn_[a-z0-9_]+)\s*\("
     # compress
-    py = _ordered_calls(_section(eng, "    def _compress(", "    def _sparse_buffers("), py_re, {})
+    py = _ordered_calls(_src("_compress"), py_re, {})
     lu = _ordered_calls(_section(lua, "function FusedMLP:compress(", "function FusedMLP:_predict_forward_sparse("), lua_re, {}, drop=READ_BACK)
     cc = _ordered_calls(_c_fn(c, "fm_compress"), c_re, {}, drop=READ_BACK)
     assert py == lu == cc == ["vbnn_prune_compress"], (py, lu, cc)
     # the forward
-    py = _ordered_calls(eng[eng.index("    def _predict_forward_sparse("):], py_re, {})
+    py = _ordered_calls(_src("_predict_forward_sparse"), py_re, {})
     lu = _ordered_calls(_section(lua, "function FusedMLP:_predict_forward_sparse(", "function FusedMLP:predict("), lua_re, {})
     cc = _ordered_calls(_c_fn(c, "fm_predict_forward_sparse"), c_re, {})
     assert py == lu == cc == ["vbnn_pack_input", "vbnn_forward_sparse"], (py, lu, cc)
-    # placement: outside the sliced ranges
-    for a, b in (("    def predict(", "    def _predict_stacked("), ("    def _predict_forward(", "    # ---- mlp.lua:69-74"),
-                 ("    def prune(", "    def _prune_mask(")):
-        sec = _section(eng, a, b)
-        assert "vbnn_prune_compress" not in sec and "vbnn_forward_sparse" not in sec
-    assert "self._predict_forward_sparse(" in _section(eng, "    def _predict_forward(", "    # ---- mlp.lua:69-74")
+    # placement: the dense functions make no sparse call
+    for fn in ("predict", "_predictive_plan", "_consume_draws", "_predict_forward", "prune"):
+        assert "vbnn_prune_compress" not in _src(fn) and "vbnn_forward_sparse" not in _src(fn), fn
+    assert "self._predict_forward_sparse(" in _src("_predict_forward")
     assert raw.index("function FusedMLP:use_pruned(") < raw.index("function FusedMLP:compress(") < \
         raw.index("function FusedMLP:_predict_forward_sparse(") < raw.index("function FusedMLP:predict(")
     tail = raw[raw.index("function FusedMLP:predict("):]

@@ -48,35 +48,35 @@ def test_unit_entry_points_are_exported_and_declared_everywhere():
 
 
 def test_the_three_hosts_issue_unit_calls_in_the_same_order():
-    """engine.prune_units / compact, lua FusedMLP:prune_units / :compact and c_host's fm_prune_units / fm_compact: the same
-    library calls in the same order, placed outside every range the predict, prune and sparse lints slice."""
-    from tests.test_predict_abi import READ_BACK, _c_fn, _lua, _ordered_calls, _section
-    eng = open(os.path.join(ROOT, "vbnn_amd", "engine.py")).read()
+    """FusedMLP.prune_units / compact, lua FusedMLP:prune_units / :compact and c_host's fm_prune_units / fm_compact: the same
+    library calls in the same order, in no function (Python) or range (Lua, C) the predict, prune and sparse lints read."""
+    from tests.test_predict_abi import READ_BACK, _c_fn, _lua, _ordered_calls, _section, _src
+    from vbnn_amd.engine import FusedMLP
     raw, lua = _lua()
     c = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "tools", "c_host.c")).read(), flags=re.S)
     py_re, lua_re, c_re = r"lib\.(vbnn_[a-z0-9_]+)\(", r"\bC\.(vbnn_[a-z0-9_]+)\s*\(", r"\b(vbnn_[a-z0-9_]+)\s*\("
-    py = _ordered_calls(_section(eng, "    def prune_units(", "    def compact("), py_re, {})
+    py = _ordered_calls(_src("prune_units"), py_re, {})
     lu = _ordered_calls(_section(lua, "function FusedMLP:prune_units(", "function FusedMLP:compact("), lua_re, {}, drop=READ_BACK)
     cc = _ordered_calls(_c_fn(c, "fm_prune_units"), c_re, {}, drop=READ_BACK)
     assert py == lu == cc == ["vbnn_unit_snr", "vbnn_unit_select", "vbnn_unit_index"], (py, lu, cc)
-    py = _ordered_calls(_section(eng, "    def compact(", "    def prune_units_curve("), py_re, {})
+    py = _ordered_calls(_src("compact"), py_re, {})
     lu = _ordered_calls(_section(lua, "function FusedMLP:compact(", "function FusedMLP:prune("), lua_re, {}, drop=READ_BACK)
     cc = _ordered_calls(_c_fn(c, "fm_compact"), c_re, {}, drop=READ_BACK)
     assert py == lu == cc == ["vbnn_unit_gather", "vbnn_sample"], (py, lu, cc)   # (the counter: device_draw engines only)
     # each host builds the compact network's engine first and prepares it after the gather
-    sec = _section(eng, "    def compact(", "    def prune_units_curve(")
+    sec = _src("compact")
     assert sec.index("FusedMLP(opt") < sec.index("vbnn_unit_gather") < sec.index("new.prepare()")
     sec = _section(lua, "function FusedMLP:compact(", "function FusedMLP:prune(")
     assert sec.index("FusedMLP.new(") < sec.index("vbnn_unit_gather") < sec.index(":prepare()")
     sec = _c_fn(c, "fm_compact")
     assert sec.index("fm_new(") < sec.index("vbnn_unit_gather") < sec.index("fm_prepare(")
-    # placement
-    assert eng.index("    def unit_snr(") < eng.index("    def prune_units(") < eng.index("    def compact(") < \
-        eng.index("    def prune_units_curve(") < eng.index("    def _prune_descs(")
-    assert "vbnn_unit_" not in eng[eng.index("    def _prune_descs("):]
-    for a, b in (("    def predict(", "    def _predict_stacked("), ("    def _predict_wn_sample(", "    def _predict_forward("),
-                 ("    def _predict_forward(", "    # ---- mlp.lua:69-74")):
-        assert "vbnn_unit_" not in _section(eng, a, b)
+    # placement: the unit functions exist; the weight-pruning, sparse and predict functions make no unit call
+    for fn in ("unit_snr", "prune_units", "compact", "prune_units_curve"):
+        assert callable(getattr(FusedMLP, fn)), fn
+    for fn in ("_prune_descs", "snr", "prune", "_prune_mask", "use_pruned", "pruned", "prune_curve", "prune_curve_sparse", "_compress",
+               "_sparse_buffers", "_predict_forward_sparse", "predict", "_predictive_plan", "_consume_draws", "_predict_wn_sample",
+               "_predict_forward"):
+        assert "vbnn_unit_" not in _src(fn), fn
     assert raw.index("function FusedMLP:loss_and_accuracy") < raw.index("function FusedMLP:prune_units(") < \
         raw.index("function FusedMLP:compact(") < raw.index("function FusedMLP:prune(")
     assert "vbnn_unit_" not in raw[raw.index("function FusedMLP:prune("):]

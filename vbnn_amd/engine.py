@@ -8,35 +8,23 @@ epilogue), final Linear + LogSoftMax + ClassNLL, backward (gradInput GEMMs with 
 dL/dv hand-off in the epilogue, accGradParameters GEMMs with the gradSum / KL-gradient epilogue).
 
 Everything here is argument plumbing around include/vbnn_hip.h; torch is device memory, the
-stream and torch.distributed.
+stream and torch.distributed. The posterior predictives (predictive.py) and pruning (pruning.py) are mixins of FusedMLP.
 """
 import contextlib
 import ctypes as C
-import functools
 import math
+import os
 
 import torch
 
 from . import _lib as L
 from . import partition
-from .nn import Context, _DT, _Packed, _p, fill_normal
-
-
-class _VB:
-    pass
+from .nn import Context, _DT, _Packed, _VB, _ordered, _p, fill_normal
+from .predictive import PredictResult, RegressionPredictResult, _Predictive       # noqa: F401  (the result classes: re-exported)
+from .pruning import PruneResult, SparsePruneResult, UnitPruneResult, _Pruning      # noqa: F401
 
 
 _NULL_CM = contextlib.nullcontext()
-
-
-def _ordered(fn):
-    """Engine entry points that launch or allocate: the body runs with the engine's stream as torch's current stream, that
-    stream ordered behind whatever the caller queued on ITS current stream before the call (FusedMLP._on_stream)."""
-    @functools.wraps(fn)
-    def wrapped(self, *args, **kwargs):
-        with self._on_stream():
-            return fn(self, *args, **kwargs)
-    return wrapped
 
 
 class _View:
@@ -72,155 +60,7 @@ class _StepGraph:
             self.h = None
 
 
-class _PredictBuffers(list):
-    """predict's operands per layer input (+ .r, the sequential bf16 forwards' throwaway noise factor)."""
-    r = None
-
-
-class PredictResult:
-    """FusedMLP.predict's outputs for R minibatch rows. Device tensors: probs / log_probs (R x C fp32: the S-draw average
-    1/S sum_s softmax(f_s(x)) and its log), entropy (H[p]), expected_entropy (1/S sum_s H(p_s)), mutual_info (their difference:
-    the epistemic part), pred (int32, argmax p). With targets also Python floats: nll (mean -log p[t]) and accuracy (percent)
-    of the averaged prediction, and mean_draw_nll / mean_draw_accuracy -- the mean over draws of each draw's NLL and accuracy,
-    the two numbers test() returns. None without targets."""
-
-    def __init__(self, probs, log_probs, entropy, expected_entropy, mutual_info, pred):
-        self.probs, self.log_probs, self.entropy = probs, log_probs, entropy
-        self.expected_entropy, self.mutual_info, self.pred = expected_entropy, mutual_info, pred
-        self.nll = self.accuracy = self.mean_draw_nll = self.mean_draw_accuracy = None
-        self.S, self.stacked, self.chunks = None, None, None
-
-
-class RegressionPredictResult:
-    """FusedMLP.predict_regression's outputs for R minibatch rows of D outputs. Device tensors: mean (R x D: 1/S sum_s f_s(x)),
-    var (R x D: the population variance of the S draws per output, the epistemic part -- the total predictive variance is
-    var + noise_var), row_var (R: its mean over the outputs); with targets row_sq_err (R: sum_d (t - mean)^2) and, with
-    noise_var, row_log_lik (R: the log density of the equal-weight mixture of N(f_s(x), noise_var I) at t); draws (S x R x D)
-    with keep_draws. With targets also Python floats: totals (the library's four sums), mse (of the predictive mean),
-    mean_draw_mse (the mean over draws of each draw's MSE: test()'s number), log_lik (mean row_log_lik; None without noise_var)
-    and mean_var.
-    criterion = "gauss" (the network predicts its own noise; None for "mse"): noise_var (R x D: 1/S sum_s exp(s_c), the
-    aleatoric part -- the total predictive variance is var + noise_var), row_noise_var (R: its mean over the outputs), and with
-    targets mean_noise_var and mean_draw_nll (the mean over draws of each draw's Gaussian criterion: test()'s number); totals
-    then has five sums, mean_draw_mse is None, draws is S x R x 2 D and row_log_lik / log_lik are those of the mixture of
-    N(m_s, diag exp(s_s))."""
-
-    def __init__(self, mean, var, row_var, row_sq_err, row_log_lik, draws):
-        self.mean, self.var, self.row_var = mean, var, row_var
-        self.row_sq_err, self.row_log_lik, self.draws = row_sq_err, row_log_lik, draws
-        self.totals = self.mse = self.mean_draw_mse = self.log_lik = self.mean_var = None
-        self.noise_var = self.row_noise_var = self.mean_noise_var = self.mean_draw_nll = None
-        self.S, self.stacked, self.chunks = None, None, None
-
-
-class PruneResult:
-    """FusedMLP.prune's outcome: the signal-to-noise pruning of mainviz.lua:20-27 at one threshold per VB layer, and the pruned
-    operand shadows (mu_p / var_p per layer, owned here) that predict() reads while this result is the engine's pruned view
-    (FusedMLP.use_pruned / pruned). Per layer (lists, VB layer order): tau (the threshold: key < tau is pruned; one value
-    repeated when scope = "global"), layers[li] = dict(n_pruned, W, fraction_pruned, mean_var, mean_pruned_var); the same five
-    names as attributes are the totals over all layers -- n_pruned and mean_pruned_var are what mainviz.lua:22-27 prints
-    (`pruned count`, `pruned var mean`; mean_pruned_var is nan when nothing was pruned, as the mean of an empty tensor).
-    mask(li): the layer's `pruned` tensor (mainviz.lua:21) as an O x I bool tensor, produced on request by one more pack
-    sweep of that layer. A result is a snapshot of the parameters it was taken from (version)."""
-
-    def __init__(self, engine, scope, tau, stats, mu_p, var_p, version):
-        self.engine, self.scope, self.version = engine, scope, version
-        self.tau = [float(t) for t in tau]
-        self.mu_p, self.var_p = mu_p, var_p
-        self.stats = [tuple(float(x) for x in st) for st in stats]         # per layer: pruned, sum pruned vars, sum vars, W
-        self.layers = [self._summary(*st) for st in self.stats]
-        tot = self._summary(*[sum(col) for col in zip(*self.stats)]) if self.stats else self._summary(0.0, 0.0, 0.0, 0.0)
-        self.n_pruned, self.W, self.fraction_pruned = tot["n_pruned"], tot["W"], tot["fraction_pruned"]
-        self.mean_var, self.mean_pruned_var = tot["mean_var"], tot["mean_pruned_var"]
-
-    @staticmethod
-    def _summary(n, s_pruned, s_all, W):
-        return dict(n_pruned=int(n), W=int(W), fraction_pruned=n / W if W else 0.0, mean_var=s_all / W if W else float("nan"),
-                    mean_pruned_var=s_pruned / n if n else float("nan"))
-
-    def mask(self, li):
-        return self.engine._prune_mask(self, li)
-
-    def compress(self):
-        """The same pruning in compressed form (a SparsePruneResult: the kept weights only, CSR per layer): under that view
-        predict() multiplies by the entries directly (vbnn_forward_sparse). Synchronises to check the entry counts."""
-        return self.engine._compress(self)
-
-
-class SparsePruneResult(PruneResult):
-    """PruneResult.compress()'s outcome: a PruneResult (use_pruned / pruned take it unchanged; tau, layers, totals and the
-    version guard are the dense result's) whose weights are per-layer CSR over output rows instead of dense shadows -- lists in
-    VB layer order: row_ptr[li] (O + 1 offsets, int32 storage of the library's uint32), cols[li] (ascending within a row;
-    int16 storage of uint16 when idx_bytes[li] == 2, int32 otherwise), mu_v[li] / var_v[li] (the packed dtype), nnz[li]
-    (= W - n_pruned: a kept weight that is zero is still an entry). nbytes / dense_nbytes: device bytes of this form and of
-    the dense shadows it replaces. It owns no dense shadows (mu_p / var_p are None): dropping the dense result frees them.
-    to_dense(li) rebuilds them (for checking), mask(li) the layer's `pruned` tensor."""
-
-    def __init__(self, base, row_ptr, cols, mu_v, var_v, nnz, idx_bytes, dense_nbytes):
-        super().__init__(base.engine, base.scope, base.tau, base.stats, None, None, base.version)
-        self.row_ptr, self.cols, self.mu_v, self.var_v = row_ptr, cols, mu_v, var_v
-        self.nnz, self.idx_bytes = [int(n) for n in nnz], list(idx_bytes)
-        self.nbytes = sum(t[li].numel() * t[li].element_size() for t in (row_ptr, cols, mu_v, var_v) for li in range(len(nnz)))
-        self.dense_nbytes = int(dense_nbytes)
-
-    def _coords(self, li):
-        rp = self.row_ptr[li].to(torch.int64)
-        rows = torch.repeat_interleave(torch.arange(rp.numel() - 1, device=rp.device), rp[1:] - rp[:-1])
-        mask = 0xffff if self.idx_bytes[li] == 2 else 0xffffffff
-        return rows, self.cols[li][:self.nnz[li]].to(torch.int64) & mask
-
-    def to_dense(self, li):
-        """(mu_p, var_p) of layer li as vbnn_prune_pack writes them: O x ld_w of the packed dtype, +0 wherever no entry is."""
-        v = self.engine.vb[li]
-        rows, cols = self._coords(li)
-        out = []
-        for vals in (self.mu_v[li], self.var_v[li]):
-            d = torch.zeros(v.O, L.pad_ld(v.I), dtype=vals.dtype, device=vals.device)
-            d[rows, cols] = vals[:self.nnz[li]]
-            out.append(d)
-        return tuple(out)
-
-    def mask(self, li):
-        v = self.engine.vb[li]
-        m = torch.ones(v.O, v.I, dtype=torch.bool, device=self.row_ptr[li].device)
-        rows, cols = self._coords(li)
-        m[rows, cols] = False
-        return m
-
-    def compress(self):
-        return self
-
-
-class UnitPruneResult:
-    """FusedMLP.prune_units' outcome: structured signal-to-noise pruning, whole hidden units by ||mu_o|| / ||sigma_o|| (the group
-    form of mainviz.lua:20-21). Lists in VB layer order: tau (the threshold: a unit with key < tau goes; one value repeated when
-    scope = "global"), keep[li] (the kept units, an ascending int32 device tensor), hidden (their counts: the widths of the
-    compact network), layers[li] = dict(n_units, n_pruned, fraction_pruned); the same three names as attributes are the totals.
-    n_weights / n_weights_before: weights of the VB layers plus the final Linear, after and before. A result is a snapshot of
-    the parameters it was taken from (version); FusedMLP.compact(result) builds the smaller dense engine."""
-
-    def __init__(self, engine, scope, multiple, tau, keep, sizes, n_classes, version):
-        self.engine, self.scope, self.multiple, self.version = engine, scope, int(multiple), version
-        self.tau = [float(t) for t in tau]
-        self.keep = list(keep)
-        self.hidden = [int(k.numel()) for k in self.keep]
-        units = [int(o) for o in sizes[1:]]
-        self.layers = [self._summary(o, o - n) for o, n in zip(units, self.hidden)]
-        tot = self._summary(sum(units), sum(units) - sum(self.hidden))
-        self.n_units, self.n_pruned, self.fraction_pruned = tot["n_units"], tot["n_pruned"], tot["fraction_pruned"]
-        self.n_weights_before = self._weights([int(sizes[0])] + units, n_classes)
-        self.n_weights = self._weights([int(sizes[0])] + self.hidden, n_classes)
-
-    @staticmethod
-    def _summary(n_units, n_pruned):
-        return dict(n_units=int(n_units), n_pruned=int(n_pruned), fraction_pruned=n_pruned / n_units if n_units else 0.0)
-
-    @staticmethod
-    def _weights(sizes, n_classes):
-        return sum(sizes[i] * sizes[i + 1] for i in range(len(sizes) - 1)) + sizes[-1] * int(n_classes)
-
-
-class FusedMLP:
+class FusedMLP(_Predictive, _Pruning):
     def __init__(self, opt, device=None, world_size=1, rank=0, process_group=None, force_reduce=False, stream=None):
         """stream: a torch.cuda.Stream for this engine's launches (a library context of its own, hence its own reduction
         scratch and tickets): two engines on two streams may compute on one device at the same time. Default: the
@@ -276,8 +116,7 @@ class FusedMLP:
         # all-reduce (partition.py): reduce-scatter of the likelihood gradients by layer rows, update() on this
         # rank's rows only (Adam state + fp32 master rows sharded), all-gather of the operand shadows + prior statistics. An option
         # beside the all-reduce, never its replacement: update() is then part of every step.
-        import os as _os
-        self.exchange_mode = str(opt.get("exchange_mode", _os.environ.get("VBNN_EXCHANGE_MODE", "")) or "allreduce")
+        self.exchange_mode = str(opt.get("exchange_mode", os.environ.get("VBNN_EXCHANGE_MODE", "")) or "allreduce")
         assert self.exchange_mode in ("allreduce", "sharded")
         self.sharded = self.reduce and self.exchange_mode == "sharded"
         self._params_stale = False            # sharded: the fp32 means / lvars of OTHER ranks' rows are stale after an update
@@ -345,7 +184,6 @@ class FusedMLP:
         self._lay = lay
         # opt.exchange = "p2p" (or VBNN_EXCHANGE=p2p): the direct reduce-scatter + all-gather over peer-mapped arenas
         # (vbnn_p2p_*, csrc/p2p.hip) instead of RCCL; that exchange owns the arena (an IPC-exportable allocation of the library's)
-        import os
         self.exchange_kind = str(opt.get("exchange", os.environ.get("VBNN_EXCHANGE", "")) or "")
         n_layers = len(hidden)
         self._plan = partition.sharded_plan(lay, world_size) if self.sharded else None
@@ -378,6 +216,7 @@ class FusedMLP:
             I, O = sizes[li], sizes[li + 1]
             v = _VB()
             v.I, v.O, v.layer_id = I, O, li
+            v.use_muT = v.early_ok = True                                          # until _alloc_batch knows the batch's kernels
             v.var_init = var_init if var_init is not None else 2.0 / I           # VBLinear.lua:12-16
             v.means = torch.zeros(O, I, **f32)                                     # :22-23
             v.lvars = torch.full((O, I), math.log(v.var_init), **f32)              # :18
@@ -445,6 +284,8 @@ class FusedMLP:
         self._prune_ws = None
         self._held = None                 # the held pruning masks (hold_pruned): one O x I uint8 tensor per VB layer, 1 = frozen
         self._held_counts = None
+        self._opt_state, self.update_log = {}, None           # Adam's moments and step counts (_adam_slot); update(log=True)'s series
+        self._pred_bufs = self._pred_key = self._pred_wts = self._sparse_bufs = self._sparse_key = None     # predictive.py, on first use
         self.init_parameters()
 
     # mlp.lua:47-55 (He rule for every weight, bias zero) + the bench's non-degenerate means
@@ -496,7 +337,7 @@ class FusedMLP:
             v.early_ok = (not v.dw_km) or bool(not v.bias_from_dw and lib.vbnn_ctx_kmajor_supported(self.ctx.h, v.I, v.O, N))
             v.dx_km = bool(km_ok and li > 0 and lib.vbnn_ctx_kmajor_supported(self.ctx.h, v.I, N, v.O))
             use_muT = (li > 0) and not v.dx_km
-            if use_muT and not getattr(v, "use_muT", True):
+            if use_muT and not v.use_muT:
                 need_prepare = True                            # the shadows' transposes were being skipped: refresh them
             v.use_muT = use_muT
         for v in self.vb:
@@ -575,7 +416,7 @@ class FusedMLP:
             # -- while the fp32 rows of other ranks are stale. No sweep, and NO collective hidden in here: only the
             # transposed shadows of a layer that did not keep them so far are rebuilt, locally, from the gathered ones.
             for v in self.vb:
-                if v.muT_s is not None and getattr(v, "use_muT", True):
+                if v.muT_s is not None and v.use_muT:
                     L.check(lib.vbnn_transpose_packed(self.ctx.h, self.code, v.mu_s.ptr, v.mu_s.ld, v.O, v.I, v.muT_s.ptr, v.muT_s.ld))
                     L.check(lib.vbnn_transpose_packed(self.ctx.h, self.code, v.var_s.ptr, v.var_s.ld, v.O, v.I, v.varT_s.ptr, v.varT_s.ld))
             return
@@ -584,12 +425,11 @@ class FusedMLP:
             descs = (L.PrepDesc * len(self.vb))()
             for k, v in enumerate(self.vb):
                 descs[k] = L.PrepDesc(means=_p(v.means), lvars=_p(v.lvars), O=v.O, I=v.I, mu_s=v.mu_s.ptr, var_s=v.var_s.ptr,
-                                      ld_w=v.mu_s.ld, muT_s=v.muT_s.ptr if (v.muT_s and getattr(v, "use_muT", True)) else None,
-                                      varT_s=v.varT_s.ptr if (v.varT_s and getattr(v, "use_muT", True)) else None,
+                                      ld_w=v.mu_s.ld, muT_s=v.muT_s.ptr if (v.muT_s and v.use_muT) else None,
+                                      varT_s=v.varT_s.ptr if (v.varT_s and v.use_muT) else None,
                                       ld_wT=v.muT_s.ld if v.muT_s else 0,
                                       stats=_p(v.stats))
-            w3 = L.PackDesc(src=_p(self.weight3), rows=self.n_classes, cols=self.sizes[-1], ld_src=self.sizes[-1],
-                            dst=self.w3_s.ptr, ld_dst=self.w3_s.ld, dstT=self.w3T_s.ptr, ld_dstT=self.w3T_s.ld)
+            w3 = self._w3_pack_desc()
             if self._held is not None:                        # a held pruning mask: +0 shadows, the kept network's statistics
                 L.check(lib.vbnn_prepare_masked(self.ctx.h, self.code, len(self.vb), descs, self._held_ptrs(), C.byref(w3)))
             else:
@@ -600,6 +440,11 @@ class FusedMLP:
         L.check(lib.vbnn_pack(self.ctx.h, self.code, L.PACK_COPY, _p(self.weight3), None, self.sizes[-1],
                               self.n_classes, self.sizes[-1], self.w3_s.ptr, self.w3_s.ld, self.w3T_s.ptr, self.w3T_s.ld))
 
+    def _w3_pack_desc(self):
+        """The final Linear's weight for vbnn_prepare / vbnn_update: packed, with its transpose."""
+        return L.PackDesc(src=_p(self.weight3), rows=self.n_classes, cols=self.sizes[-1], ld_src=self.sizes[-1],
+                          dst=self.w3_s.ptr, ld_dst=self.w3_s.ld, dstT=self.w3T_s.ptr, ld_dstT=self.w3T_s.ld)
+
     def _lrt(self):
         return self.mode == "lrt" and not self._map
 
@@ -609,7 +454,6 @@ class FusedMLP:
     probe = None
 
     def _probed(self, name, li):
-        import contextlib
         if self.probe is None or (self.probe[0] != li and self.probe[0] != "all"):
             return contextlib.nullcontext()
         if self.probe[0] == "all":                       # lab (tools/overlap_standin.py): every layer's launches, keyed by layer
@@ -665,181 +509,6 @@ class FusedMLP:
             acc += 100.0 * correct / N
         return err / draws, acc / draws
 
-    # ---- the posterior predictive (vbnn_head_predict): what mlp:test averages as per-draw criteria (mlp.lua:86-107, main.lua:55-74),
-    # averaged as PROBABILITIES, with the per-example uncertainty of visualize.lua:66-100 (show_uncertainties). A forward-only
-    # path on buffers of its own: no r, no transposed outputs, no head slots, no squares out of the last layer, and nothing of
-    # the training step (operands it produces, gradient arena, loss accumulators, batch buffers, argument cache) is written.
-    # It reads the operand shadows as prepare() / update() leave them -- on an engine that has had neither it calls prepare()
-    # first, as test() does; after changing the parameters by hand call prepare(), as before run() -- or draws its own weights
-    # from means / lvars (WN).
-    @_ordered
-    def predict(self, inputs, S=None, targets=None, map=False, row0=None):
-        """p(y | x, D) ~ 1/S sum_s softmax(f_s(x)) over draws self.draw + 1 .. self.draw + S -- the draws test() with
-        opt.testSamples = S consumes -- and `self.draw` advances by S (host and device counter). map=True (or opt.quicktest):
-        one pass on the means, S = 1, no draw consumed. row0: the global row of inputs[0] that addresses the noise (default:
-        this rank's first row, as run()). Returns a PredictResult of this rank's rows (no collective, as test())."""
-        lib, ctx, code = L.lib(), self.ctx.h, self.code
-        Cn = self.n_classes
-        if Cn > 16:
-            raise ValueError(f"predict: the predictive head takes at most 16 classes (n_classes = {Cn})")
-        if self.criterion != "nll":
-            raise ValueError(f"predict: a class-probability predictive needs the NLL criterion (criterion = '{self.criterion}' has "
-                             "none: use predict_regression)")
-        map = bool(map or self.opt.get("quicktest"))
-        S = 1 if map else int(self.opt["testSamples"] if S is None else S)
-        if S < 1:
-            raise ValueError(f"predict: S = {S} draws (at least one)")
-        x = inputs.reshape(inputs.shape[0], -1)
-        R = x.shape[0]
-        assert x.shape[1] == self.sizes[0] and x.dtype == torch.float32 and x.is_cuda and R > 0
-        if targets is not None:
-            assert targets.dtype == torch.int32 and targets.is_cuda and targets.numel() == R
-            targets = targets.contiguous()
-        row0 = self.rank * R if row0 is None else int(row0)
-        if not self._shadows_ready:            # a fresh engine: the shadows test() would have prepared
-            self.prepare()
-        if self._pruned is not None:           # a pruned view replaces the operand shadows: it must be of THESE parameters
-            if self.mode == "wn" and not map:
-                raise ValueError("predict: weight-noise draws under a pruned view are not supported -- they sample from the fp32 "
-                                 "means / lvars, which the view does not replace (use map=True, or mode = 'lrt')")
-            if self._pruned.version != self._pver:
-                raise RuntimeError("predict: the pruned view was taken from older parameters (update / prepare / init_parameters "
-                                   "ran since): prune() again, or use_pruned(None)")
-        lrt = self.mode == "lrt" and not map
-        stacked = self._predict_stacked(R, S, lrt)
-        cap = max(1, int(self.opt.get("predict_rows", 32768)))
-        Rc = max(1, min(R, cap // S if stacked else cap))           # minibatch rows per chunk: S Rc (stacked) or Rc operand rows
-        bufs = self._predict_buffers(S * Rc if stacked else Rc, lrt)
-        wts = self._predict_weights() if self.mode == "wn" else None
-        f32 = dict(dtype=torch.float32, device=self.device)
-        res = PredictResult(torch.empty(R, Cn, **f32), torch.empty(R, Cn, **f32), torch.empty(R, **f32), torch.empty(R, **f32),
-                            torch.empty(R, **f32), torch.empty(R, dtype=torch.int32, device=self.device))
-        n_chunks = (R + Rc - 1) // Rc
-        totals = torch.zeros(n_chunks, 4, dtype=torch.float64, device=self.device) if targets is not None else None
-        state = torch.empty(Rc, Cn + 3, **f32) if not stacked else None
-        d0 = self.draw + 1                                           # the first draw's counter (sample() then run())
-        nl = len(self.vb)
-        a = L.PredictArgs(w3=self.w3_s.ptr, ld_w=self.w3_s.ld, bias=_p(self.bias3), H=self.sizes[-1], C=Cn, S=S,
-                          form=L.PREDICT_STACKED if stacked else L.PREDICT_ACCUMULATE, state=_p(state))
-        for k in range(n_chunks):
-            c0 = k * Rc
-            rows = min(Rc, R - c0)
-            xc = x[c0:c0 + rows]
-            a.h, a.ld_h = bufs[nl].x.ptr, bufs[nl].x.ld
-            a.R = rows
-            a.target = C.c_void_p(targets.data_ptr() + 4 * c0) if targets is not None else None
-            a.totals = C.c_void_p(totals[k].data_ptr()) if totals is not None else None
-            for name, t in (("probs", res.probs), ("log_probs", res.log_probs)):
-                setattr(a, name, C.c_void_p(t.data_ptr() + 4 * Cn * c0))
-            for name, t in (("entropy", res.entropy), ("expected_entropy", res.expected_entropy), ("mutual_info", res.mutual_info),
-                            ("pred", res.pred)):
-                setattr(a, name, C.c_void_p(t.data_ptr() + 4 * c0))
-            if stacked:                        # every draw in one pass: the chunk stacked S times as rows, draw s = rows [s rows, (s+1) rows)
-                if wts is not None:            # (weight noise: S = 1)
-                    self._predict_wn_sample(wts, None if map else d0)
-                self._predict_forward(bufs, wts, xc, S * rows, rows if S > 1 else 0, d0, row0 + c0, lrt)
-                L.check(lib.vbnn_head_predict(ctx, code, C.byref(a)))
-                continue
-            for s in range(S):                 # one draw per forward, the running state between the head's launches
-                if wts is not None:
-                    self._predict_wn_sample(wts, d0 + s)
-                self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
-                a.first, a.final = int(s == 0), int(s == S - 1)
-                L.check(lib.vbnn_head_predict(ctx, code, C.byref(a)))
-        if not map:                            # the draws test() would have consumed
-            self.draw += S
-            if self.device_draw:
-                L.check(lib.vbnn_sample(ctx, _p(self._draw_dev), S))
-        if totals is not None:
-            tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
-            res.totals = tot
-            res.nll, res.accuracy = tot[0] / R, 100.0 * tot[1] / R
-            res.mean_draw_nll, res.mean_draw_accuracy = tot[2] / (R * S), 100.0 * tot[3] / (R * S)
-        res.S, res.stacked, res.chunks = S, stacked, n_chunks
-        return res
-
-    def _predict_stacked(self, R, S, lrt):
-        """opt.predict_stacked: True / False / "auto" (default). Weight noise draws a weight matrix per draw: sequential always.
-        "auto": stacked while one draw's widest forward is small (R I O < 2^32 multiply-adds: the reference's operating points,
-        launch-bound, where S launches become one), sequential above -- stacked rows never run on the two-pass 256 x 256 kernel
-        (vbnn_fwd_args.rows_per_draw), which is what the large bf16 forwards take one draw at a time (tools/predict_bench.py)."""
-        if not lrt or S == 1:
-            return S == 1 or lrt
-        ps = self.opt.get("predict_stacked", "auto")
-        if ps != "auto":
-            return bool(ps)
-        rows = min(R, max(1, int(self.opt.get("predict_rows", 32768))))
-        return rows * max(v.I * v.O for v in self.vb) < (1 << 32)
-
-    def _predict_buffers(self, rows, lrt):
-        """predict's operands: the packed input, then one ping-pong PAIR of activation (+ square) buffers per hidden width --
-        layer li writes slot (O, li % 2), so a layer never overwrites its own input and a buffer always holds one layout (its
-        pads stay zero). bufs[li] is layer li's input, bufs[len(vb)] the head's. Kept across calls while the row count holds."""
-        sq = lrt and self.dtype == "bf16"                       # (fp32: the forward forms x.x from x itself)
-        key = (rows, sq)
-        if getattr(self, "_pred_key", None) != key:
-            self._pred_bufs, self._pred_key = None, None
-            dev, tdt, nl = self.device, self.tdt, len(self.vb)
-            slots = {}
-
-            def slot(cols, parity, square):
-                b = slots.get((cols, parity))
-                if b is None:
-                    b = slots[(cols, parity)] = _VB()
-                    b.x, b.x2 = _Packed(rows, cols, tdt, dev), None
-                if square and b.x2 is None:
-                    b.x2 = _Packed(rows, cols, tdt, dev)
-                return b
-            bufs = _PredictBuffers([slot(self.sizes[0], "in", sq)])
-            for li, v in enumerate(self.vb):
-                bufs.append(slot(v.O, li % 2, sq and li < nl - 1))
-            bufs.r = _Packed(rows, max(v.O for v in self.vb), tdt, dev) if sq else None
-            self._pred_bufs, self._pred_key = bufs, key
-        return self._pred_bufs
-
-    def _predict_weights(self):
-        """WN: predict's own sampled weights (fp32) and their packed shadows, per layer (sample() keeps its draw in the training
-        operands; predict leaves them alone)."""
-        if getattr(self, "_pred_wts", None) is None:
-            self._pred_wts = [(torch.zeros(v.O, v.I, dtype=torch.float32, device=self.device), _Packed(v.O, v.I, self.tdt, self.device))
-                              for v in self.vb]
-        return self._pred_wts
-
-    def _predict_wn_sample(self, wts, draw):
-        """VBLinear:sample (VBLinear.lua:49-64) for `draw` into predict's weights; draw None: the means (clamp_to_map)."""
-        lib = L.lib()
-        for v, (w, ws) in zip(self.vb, wts):
-            if draw is not None:
-                L.check(lib.vbnn_wn_sample(self.ctx.h, _p(v.means), None, _p(v.lvars), _p(w), None, v.O, v.I, self.seed, v.layer_id, draw))
-            L.check(lib.vbnn_pack(self.ctx.h, self.code, L.PACK_COPY, _p(w if draw is not None else v.means), None, v.I, v.O, v.I,
-                                  ws.ptr, ws.ld, None, 0))
-
-    def _predict_forward(self, bufs, wts, x, N, rpd, draw, row0, lrt, pack=True):
-        """vbnn_pack_input + every VB layer's forward for predict: N operand rows (rpd > 0: stacked draws of rpd rows each)."""
-        if isinstance(self._pruned, SparsePruneResult):        # the compressed view: its own forward (below prune_curve)
-            return self._predict_forward_sparse(bufs, x, N, rpd, draw, row0, lrt, pack)
-        lib, ctx, code = L.lib(), self.ctx.h, self.code
-        if pack:
-            b0 = bufs[0]
-            L.check(lib.vbnn_pack_input(ctx, code, _p(x), x.stride(0), N, self.sizes[0], b0.x.ptr, b0.x2.ptr if b0.x2 else None,
-                                        b0.x.ld, None, None, 0, rpd))
-        nl = len(self.vb)
-        pv = self._pruned                      # a pruned view: ITS shadows in place of mu_s / var_s (or of WN's packed means)
-        for li, v in enumerate(self.vb):
-            xin, out = bufs[li], bufs[li + 1]
-            w = pv.mu_p[li] if pv is not None else (wts[li][1] if wts is not None else v.mu_s)
-            w2 = pv.var_p[li] if pv is not None else v.var_s
-            # r: nobody reads it. Only the sequential bf16 LRT forwards are handed a throwaway one -- the two-pass 256 x 256
-            # kernel, which the large one-draw forwards take, stores r as part of its fold and is not selected without it.
-            r = bufs.r if (lrt and rpd == 0 and bufs.r is not None) else None
-            a = L.FwdArgs(w=w.ptr, w2=w2.ptr if lrt else None, x=xin.x.ptr, x2=xin.x2.ptr if (lrt and xin.x2) else None,
-                          ld_w=w.ld, ld_x=xin.x.ld, N=N, I=v.I, O=v.O, bias=_p(v.bias), seed=self.seed, layer=v.layer_id,
-                          draw=draw, draw_dev=None, row0=row0, y=None, ld_y=0, r=r.ptr if r else None, ld_r=r.ld if r else 0,
-                          r_packed=1, relu=1,
-                          h=out.x.ptr, h2=out.x2.ptr if (lrt and li < nl - 1 and out.x2) else None, ld_h=out.x.ld,
-                          hT=None, h2T=None, ld_hT=0, rows_per_draw=rpd)
-            L.check(lib.vbnn_forward(ctx, code, C.byref(a)))
-
     # ---- mlp.lua:69-74
     @_ordered
     def sample(self, by=1):
@@ -855,149 +524,6 @@ class FusedMLP:
                 L.check(lib.vbnn_pack(self.ctx.h, self.code, L.PACK_COPY, _p(v.weight), None, v.I, v.O, v.I,
                                       v.mu_s.ptr, v.mu_s.ld, v.muT_s.ptr if v.muT_s else None,
                                       v.muT_s.ld if v.muT_s else 0))
-
-    # ---- the regression criterion's posterior predictive (vbnn_predict_moments): predict()'s contract and buffers, the final
-    # Linear as _generic_head runs it (f32 outputs), then the moments of the S draws -- mean, spread, and with targets the
-    # squared errors and the mixture's log-likelihood. Nothing of the training step is written.
-    @_ordered
-    def predict_regression(self, inputs, S=None, targets=None, noise_var=None, map=False, row0=None, keep_draws=False):
-        """E[y | x, D] ~ 1/S sum_s f_s(x) over draws self.draw + 1 .. self.draw + S, with the draws' variance per output; S, map
-        and row0 as predict(), and `self.draw` advances by S likewise. targets: R x D fp32. noise_var (tau^2 > 0, or None): the
-        observation noise of the predictive log-likelihood. keep_draws: the S x R x D outputs are returned too. Returns a
-        RegressionPredictResult of this rank's rows (no collective, as test()).
-        criterion = "gauss": D = n_classes / 2, the network supplies the noise (noise_var must be None), the result carries the
-        aleatoric noise_var beside the epistemic var, and keep_draws returns the S x R x 2 D outputs (means, log variances)."""
-        lib, ctx, code = L.lib(), self.ctx.h, self.code
-        if self.criterion not in ("mse", "gauss"):
-            raise ValueError("predict_regression: the regression predictive needs the MSE criterion or the Gaussian one "
-                             "(criterion = 'nll': use predict)")
-        gauss = self.criterion == "gauss"
-        Wd = self.n_classes                                          # the final Linear's width: D, or { m[D], s[D] }
-        D = Wd // 2 if gauss else Wd
-        if gauss and noise_var is not None:
-            raise ValueError("predict_regression: criterion = 'gauss' predicts its own noise variance (noise_var must be None)")
-        if noise_var is not None:
-            noise_var = float(noise_var)
-            if not (noise_var > 0.0 and math.isfinite(noise_var)):
-                raise ValueError(f"predict_regression: noise_var = {noise_var} (a finite variance above zero, or None)")
-        map = bool(map or self.opt.get("quicktest"))
-        S = 1 if map else int(self.opt["testSamples"] if S is None else S)
-        if S < 1:
-            raise ValueError(f"predict_regression: S = {S} draws (at least one)")
-        x = inputs.reshape(inputs.shape[0], -1)
-        R = x.shape[0]
-        assert x.shape[1] == self.sizes[0] and x.dtype == torch.float32 and x.is_cuda and R > 0
-        if targets is not None:
-            if gauss and tuple(targets.shape) != (R, D):
-                raise ValueError(f"predict_regression: targets of shape {tuple(targets.shape)} (criterion = 'gauss' takes R x D = "
-                                 f"{R} x {D}: one target per mean)")
-            assert targets.dtype == torch.float32 and targets.is_cuda and tuple(targets.shape) == (R, D)
-            targets = targets.contiguous()
-        row0 = self.rank * R if row0 is None else int(row0)
-        if not self._shadows_ready:
-            self.prepare()
-        if self._pruned is not None:
-            if self.mode == "wn" and not map:
-                raise ValueError("predict_regression: weight-noise draws under a pruned view are not supported (use map=True, or "
-                                 "mode = 'lrt')")
-            if self._pruned.version != self._pver:
-                raise RuntimeError("predict_regression: the pruned view was taken from older parameters (update / prepare / "
-                                   "init_parameters ran since): prune() again, or use_pruned(None)")
-        lrt = self.mode == "lrt" and not map
-        stacked = self._predict_stacked(R, S, lrt)
-        cap = max(1, int(self.opt.get("predict_rows", 32768)))
-        Rc = max(1, min(R, cap // S if stacked else cap))
-        op_rows = S * Rc if stacked else Rc
-        bufs = self._predict_buffers(op_rows, lrt)
-        wts = self._predict_weights() if self.mode == "wn" else None
-        f32 = dict(dtype=torch.float32, device=self.device)
-        n_chunks = (R + Rc - 1) // Rc
-        has_t = targets is not None
-        res = RegressionPredictResult(torch.empty(R, D, **f32), torch.empty(R, D, **f32), torch.empty(R, **f32),
-                                      torch.empty(R, **f32) if has_t else None,
-                                      torch.empty(R, **f32) if (has_t and (gauss or noise_var is not None)) else None,
-                                      torch.empty(S, R, Wd, **f32) if keep_draws else None)
-        if gauss:
-            res.noise_var, res.row_noise_var = torch.empty(R, D, **f32), torch.empty(R, **f32)
-        direct = keep_draws and (not stacked or n_chunks == 1)      # the final Linear writes into res.draws itself
-        ybuf = None
-        if not direct:                                               # the y buffer: kept with the predict buffers
-            ybuf = getattr(bufs, "y_reg", None)
-            if ybuf is None or tuple(ybuf.shape) != (op_rows, Wd):
-                ybuf = bufs.y_reg = torch.empty(op_rows, Wd, **f32)
-        one_call = stacked and D <= (L.GAUSS_MOMENTS_STACKED_MAX_D if gauss else L.MOMENTS_STACKED_MAX_D)   # else: ACCUMULATE per draw
-        state = None if one_call else torch.empty(Rc, (3 if gauss else 2) * D + 2, **f32)
-        totals = torch.zeros(n_chunks, 5 if gauss else 4, dtype=torch.float64, device=self.device) if has_t else None
-        d0 = self.draw + 1
-        nl, H = len(self.vb), self.sizes[-1]
-        form = L.MOMENTS_STACKED if one_call else L.MOMENTS_ACCUMULATE
-        if gauss:
-            a = L.GaussMomentsArgs(ld_y=Wd, ld_t=D, D=D, S=S, form=form, s_min=self.logvar_clamp[0], s_max=self.logvar_clamp[1],
-                                   state=_p(state), ld_out=D)
-            moments = lib.vbnn_predict_gauss_moments
-        else:
-            a = L.MomentsArgs(ld_y=D, ld_t=D, D=D, S=S, form=form, noise_var=noise_var or 0.0, state=_p(state), ld_out=D)
-            moments = lib.vbnn_predict_moments
-
-        def off(t, row):
-            return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
-
-        def final_linear(N, y_ptr):
-            fa = L.FwdArgs(w=self.w3_s.ptr, w2=None, x=bufs[nl].x.ptr, x2=None, ld_w=self.w3_s.ld, ld_x=bufs[nl].x.ld,
-                           N=N, I=H, O=Wd, bias=_p(self.bias3), y=y_ptr, ld_y=Wd)
-            L.check(lib.vbnn_forward(ctx, code, C.byref(fa)))
-
-        for k in range(n_chunks):
-            c0 = k * Rc
-            rows = min(Rc, R - c0)
-            xc = x[c0:c0 + rows]
-            a.R = rows
-            a.target = off(targets, c0 * D)
-            a.totals = C.c_void_p(totals[k].data_ptr()) if has_t else None
-            a.mean, a.var = off(res.mean, c0 * D), off(res.var, c0 * D)
-            a.row_var, a.row_sq_err, a.row_log_lik = off(res.row_var, c0), off(res.row_sq_err, c0), off(res.row_log_lik, c0)
-            if gauss:
-                a.noise_var, a.row_noise_var = off(res.noise_var, c0 * D), off(res.row_noise_var, c0)
-            if stacked:                        # every draw in one forward: draw s = rows [s rows, (s+1) rows) of y
-                if wts is not None:
-                    self._predict_wn_sample(wts, None if map else d0)
-                self._predict_forward(bufs, wts, xc, S * rows, rows if S > 1 else 0, d0, row0 + c0, lrt)
-                y = res.draws if direct else ybuf
-                final_linear(S * rows, _p(y))
-                if one_call:
-                    a.y = _p(y)
-                    L.check(moments(ctx, C.byref(a)))
-                else:
-                    for s in range(S):
-                        a.y, a.draw = off(y, s * rows * Wd), s
-                        L.check(moments(ctx, C.byref(a)))
-                if keep_draws and not direct:
-                    res.draws[:, c0:c0 + rows].copy_(ybuf[:S * rows].view(S, rows, Wd))
-                continue
-            for s in range(S):                 # one draw per forward, the running moments in `state` between the launches
-                if wts is not None:
-                    self._predict_wn_sample(wts, d0 + s)
-                self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
-                yp = off(res.draws, (s * R + c0) * Wd) if direct else _p(ybuf)
-                final_linear(rows, yp)
-                a.y, a.draw = yp, s
-                L.check(moments(ctx, C.byref(a)))
-        if not map:
-            self.draw += S
-            if self.device_draw:
-                L.check(lib.vbnn_sample(ctx, _p(self._draw_dev), S))
-        if has_t:
-            tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
-            res.totals = tot
-            res.mse = tot[0] / (R * D)
-            if gauss:
-                res.mean_draw_nll, res.mean_noise_var = tot[1] / (R * S * D), tot[4] / (R * D)
-            else:
-                res.mean_draw_mse = tot[1] / (R * S * D)
-            res.log_lik = tot[2] / R if (gauss or noise_var is not None) else None
-            res.mean_var = tot[3] / (R * D)
-        res.S, res.stacked, res.chunks = S, stacked, n_chunks
-        return res
 
     # ---- final Linear + criterion through the generic GEMM kernels (class counts above 16)
     def _generic_head(self, N, targets, inv_n, accumulate, backward=True):
@@ -1455,7 +981,6 @@ class FusedMLP:
         self._pver += 1
         ex = self.exchange()
         lr = float(opt["state"]["learningRate"])
-        st = self.__dict__.setdefault("_opt_state", {})
         L.check(lib.vbnn_sgd_step(h, _p(self.weight3), _p(self.gradWeight3), self.weight3.numel(), lr))
         L.check(lib.vbnn_sgd_step(h, _p(self.bias3), _p(self.gradBias3), self.bias3.numel(), lr))
         n = len(self.vb)
@@ -1465,25 +990,15 @@ class FusedMLP:
             L.check(lib.vbnn_sgd_step(h, _p(v.bias), _p(v.gradBias), v.O, lr))
             r0, nr = partition.layer_row_shard(v.O, W, R)
             mine[k].copy_(v.stats)                           # in: the WHOLE layer's pre-update statistics (var_hat of the KL terms)
-            cfgs = []
-            for key, cfg in (("mean", opt["meanState"]), ("var", opt["varState"])):
-                s = st.setdefault((v.layer_id, key), {"t": 0})
-                if "m" not in s:
-                    s["m"] = torch.zeros(nr, v.I, dtype=torch.float32, device=self.device)
-                    s["v"] = torch.zeros(nr, v.I, dtype=torch.float32, device=self.device)
-                s["t"] += 1
-                cfgs.append((s, L.AdamCfg(lr=float(cfg["learningRate"]), beta1=float(cfg.get("beta1", 0.9)),
-                                          beta2=float(cfg.get("beta2", 0.999)), eps=float(cfg.get("epsilon", 1e-8)),
-                                          lambda_=float(cfg.get("lambda", 1.0)), t=s["t"])))
-            (sm, cm), (sv, cv) = cfgs
+            sm, cm = self._adam_slot(v, "mean", v.means[r0:r0 + nr], opt["meanState"])
+            sv, cv = self._adam_slot(v, "var", v.lvars[r0:r0 + nr], opt["varState"])
             descs[k] = L.UpdateDesc(means=_p(v.means[r0:r0 + nr]), lvars=_p(v.lvars[r0:r0 + nr]), O=nr, I=v.I,
                                     mu_s=_p(v.mu_s.t[r0:r0 + nr]), var_s=_p(v.var_s.t[r0:r0 + nr]), ld_w=v.mu_s.ld,
                                     muT_s=None, varT_s=None, ld_wT=0, stats=_p(mine[k]), grad_mu=_p(v.gradWeight[r0:r0 + nr]),
                                     grad_lv=_p(v.gradSum[r0:r0 + nr]), m_mu=_p(sm["m"]), v_mu=_p(sm["v"]), m_lv=_p(sv["m"]),
                                     v_lv=_p(sv["v"]), mu=cm, lv=cv, bias=None, grad_bias=None, lr_bias=lr, B=self.B,
                                     log14=None, kl_add=1.0)
-        w3 = L.PackDesc(src=_p(self.weight3), rows=self.n_classes, cols=self.sizes[-1], ld_src=self.sizes[-1],
-                        dst=self.w3_s.ptr, ld_dst=self.w3_s.ld, dstT=self.w3T_s.ptr, ld_dstT=self.w3T_s.ld)
+        w3 = self._w3_pack_desc()
         L.check(lib.vbnn_update(h, self.code, n, descs, C.byref(w3)))
         # what the next forward reads, from every rank: the shadows (in place: rank r's rows are its contribution), the parts
         for v in self.vb:
@@ -1494,7 +1009,7 @@ class FusedMLP:
         ptrs = (C.c_void_p * n)(*[v.stats.data_ptr() for v in self.vb])
         L.check(lib.vbnn_stats_combine(h, n, W, _p(self._stat_parts), ptrs))
         for v in self.vb:
-            if v.muT_s is not None and getattr(v, "use_muT", True):       # transposed shadows: rebuilt locally from the gathered ones
+            if v.muT_s is not None and v.use_muT:       # transposed shadows: rebuilt locally from the gathered ones
                 L.check(lib.vbnn_transpose_packed(h, self.code, v.mu_s.ptr, v.mu_s.ld, v.O, v.I, v.muT_s.ptr, v.muT_s.ld))
                 L.check(lib.vbnn_transpose_packed(h, self.code, v.var_s.ptr, v.var_s.ld, v.O, v.I, v.varT_s.ptr, v.varT_s.ld))
         self._params_stale = W > 1
@@ -1526,7 +1041,7 @@ class FusedMLP:
             self._exchange.check()
 
     def _early(self, v, lrt=True):
-        return v.msg_early is not None and lrt and self.fuse_kl and getattr(v, "early_ok", True)
+        return v.msg_early is not None and lrt and self.fuse_kl and v.early_ok
 
     def buckets(self):
         """The all-reduce messages of one step, in issue order (last VB layer + final Linear first)."""
@@ -1577,6 +1092,16 @@ class FusedMLP:
             return (x @ R / math.sqrt(x.shape[1])).contiguous()
         return ((torch.arange(N, device=x.device, dtype=torch.int64) + row0) * 2654435761 % self.n_classes).to(torch.int32)
 
+    def _adam_slot(self, v, key, like, cfg):
+        """Adam for layer v's means (key "mean") or lvars ("var"): the state dict -- m, v zeroed on first use, shaped like `like`
+        (the whole parameter, or the sharded update's row slice of it), t advanced by this step -- and the step's vbnn_adam_cfg."""
+        s = self._opt_state.setdefault((v.layer_id, key), {"t": 0})
+        if "m" not in s:
+            s["m"], s["v"] = torch.zeros_like(like), torch.zeros_like(like)
+        s["t"] += 1
+        return s, L.AdamCfg(lr=float(cfg["learningRate"]), beta1=float(cfg.get("beta1", 0.9)), beta2=float(cfg.get("beta2", 0.999)),
+                            eps=float(cfg.get("epsilon", 1e-8)), lambda_=float(cfg.get("lambda", 1.0)), t=s["t"])
+
     # ---- mlp:update + VBLinear:update (mlp.lua:117-142, VBLinear.lua:124-166) on the device: the dW epilogue
     # already produced the TOTAL gradients (likelihood / S + KL), so the update is ONE sweep per layer (vbnn_update):
     # SGD on the bias, Adam on means and lvars, and -- from the new parameters, in the same pass -- the GEMM shadows
@@ -1596,8 +1121,7 @@ class FusedMLP:
         lib, h = L.lib(), self.ctx.h
         self._pver += 1
         lr = float(opt["state"]["learningRate"])
-        st = self.__dict__.setdefault("_opt_state", {})
-        if log and getattr(self, "update_log", None) is None:
+        if log and self.update_log is None:
             self.update_log = torch.zeros(len(self.vb), 14, dtype=torch.float64, device=self.device)
         L.check(lib.vbnn_sgd_step(h, _p(self.weight3), _p(self.gradWeight3), self.weight3.numel(), lr))
         L.check(lib.vbnn_sgd_step(h, _p(self.bias3), _p(self.gradBias3), self.bias3.numel(), lr))
@@ -1607,29 +1131,16 @@ class FusedMLP:
             for v in self.vb:
                 L.check(lib.vbnn_sgd_step(h, _p(v.bias), _p(v.gradBias), v.O, lr))
                 for key, x, g, cfg in (("mean", v.means, v.gradWeight, opt["meanState"]), ("var", v.lvars, v.gradSum, opt["varState"])):
-                    s = st.setdefault((v.layer_id, key), {"t": 0})
-                    if "m" not in s:
-                        s["m"], s["v"] = torch.zeros_like(x), torch.zeros_like(x)
-                    s["t"] += 1
+                    s, c = self._adam_slot(v, key, x, cfg)
                     L.check(lib.vbnn_adam_step(h, _p(x), _p(g), None, _p(s["m"]), _p(s["v"]), x.numel(),
-                                               float(cfg["learningRate"]), float(cfg.get("beta1", 0.9)),
-                                               float(cfg.get("beta2", 0.999)), float(cfg.get("epsilon", 1e-8)),
-                                               float(cfg.get("lambda", 1.0)), s["t"], None))
+                                               c.lr, c.beta1, c.beta2, c.eps, c.lambda_, c.t, None))
             self.prepare()
             return
         descs = (L.UpdateDesc * len(self.vb))()
         for k, v in enumerate(self.vb):
-            cfgs = []
-            for key, x, cfg in (("mean", v.means, opt["meanState"]), ("var", v.lvars, opt["varState"])):
-                s = st.setdefault((v.layer_id, key), {"t": 0})
-                if "m" not in s:
-                    s["m"], s["v"] = torch.zeros_like(x), torch.zeros_like(x)
-                s["t"] += 1
-                cfgs.append((s, L.AdamCfg(lr=float(cfg["learningRate"]), beta1=float(cfg.get("beta1", 0.9)),
-                                          beta2=float(cfg.get("beta2", 0.999)), eps=float(cfg.get("epsilon", 1e-8)),
-                                          lambda_=float(cfg.get("lambda", 1.0)), t=s["t"])))
-            (sm, cm), (sv, cv) = cfgs
-            use_t = v.muT_s is not None and getattr(v, "use_muT", True)
+            sm, cm = self._adam_slot(v, "mean", v.means, opt["meanState"])
+            sv, cv = self._adam_slot(v, "var", v.lvars, opt["varState"])
+            use_t = v.muT_s is not None and v.use_muT
             descs[k] = L.UpdateDesc(means=_p(v.means), lvars=_p(v.lvars), O=v.O, I=v.I, mu_s=v.mu_s.ptr, var_s=v.var_s.ptr,
                                     ld_w=v.mu_s.ld, muT_s=v.muT_s.ptr if use_t else None, varT_s=v.varT_s.ptr if use_t else None,
                                     ld_wT=v.muT_s.ld if v.muT_s else 0, stats=_p(v.stats), grad_mu=_p(v.gradWeight),
@@ -1637,8 +1148,7 @@ class FusedMLP:
                                     mu=cm, lv=cv, bias=_p(v.bias), grad_bias=_p(v.gradBias), lr_bias=lr, B=self.B,
                                     log14=C.c_void_p(self.update_log[k].data_ptr()) if log else None,
                                     kl_add=1.0 if self.kl_in_update else 0.0)
-        w3 = L.PackDesc(src=_p(self.weight3), rows=self.n_classes, cols=self.sizes[-1], ld_src=self.sizes[-1],
-                        dst=self.w3_s.ptr, ld_dst=self.w3_s.ld, dstT=self.w3T_s.ptr, ld_dstT=self.w3T_s.ld)
+        w3 = self._w3_pack_desc()
         if self._held is not None:                            # a held pruning mask: the frozen weights keep every bit
             L.check(lib.vbnn_update_masked(h, self.code, len(self.vb), descs, self._held_ptrs(), C.byref(w3)))
         else:
@@ -1668,384 +1178,3 @@ class FusedMLP:
                                              _p(self._lc), v.O * v.I))
             lc += float(self._lc[0].item())
         return lc
-
-    # ---- fine-tuning a pruned network: a pruning mask HELD through training. The GEMMs of a step read the operand shadows only,
-    # so the whole feature is the parameter sweep: while a mask is held prepare() / update() / calc_lc() go through
-    # vbnn_prepare_masked / vbnn_update_masked / vbnn_calc_lc_masked -- +0 in a pruned weight's shadow entries, its fp32 parameters
-    # and Adam moments frozen bit for bit, the prior statistics those of the kept weights. run / test / predict are unchanged.
-    def _held_ptrs(self):
-        return (C.c_void_p * len(self.vb))(*[m.data_ptr() for m in self._held])
-
-    def _refuse_held(self, what):
-        if self._held is not None:
-            raise RuntimeError(f"{what}: a pruning mask is held, and {what} keys on the fp32 parameters, which still hold the frozen "
-                               "weights' values -- release_pruned() first")
-
-    @property
-    def held(self):
-        """Per VB layer the number of weights the held mask freezes, or None when nothing is held."""
-        return None if self._held is None else list(self._held_counts)
-
-    def held_mask(self, li):
-        """The held mask of VB layer li as an O x I bool tensor (True = pruned and frozen)."""
-        if self._held is None:
-            raise RuntimeError("held_mask: no pruning mask is held")
-        return self._held[li].bool()
-
-    @_ordered
-    def hold_pruned(self, result):
-        """Train the network `result` leaves: from now on the weights it prunes are out of the network AND frozen. `result`: a
-        PruneResult or SparsePruneResult of this engine at the current parameter version. Its byte masks (the vbnn_prune_pack
-        route of PruneResult.mask) are ORed into whatever is already held -- the held set only grows, which is what an iterative
-        schedule needs -- the shadows and statistics are rewritten by the masked prepare (a parameter-version change: `result`
-        and any other snapshot are void afterwards), and the per-layer held counts are returned (synchronises once).
-        prune() stays legal under a held mask and reads the raw fp32 parameters, frozen values included: prune(q) followed by
-        hold_pruned gives gradual pruning, but a frozen weight may rank above the new threshold, so the held fraction can exceed
-        the requested one -- the returned counts are the true ones.
-        Refused: weight-noise mode (sample() packs drawn weights and would need a masked draw), the sharded update, an engine
-        with fuse_kl = False (its parameters are stepped by the module-level update, which knows no mask: the frozen weights would
-        move), and a mask that leaves a layer without a kept weight.
-        The mask tensors are allocated by the FIRST hold and updated in place by later ones, so their device addresses are stable
-        while a mask is held; a step captured by capture_step whose issue() contained prepare() or update() replays the calls it
-        recorded -- masked with those addresses if it was captured under a held mask, unmasked if not. Capture such a step again
-        after the first hold_pruned and after release_pruned. prune_units / compact / compress are refused while a mask is held; compressing
-        a held network by its mask is the follow-up. The data-parallel all-reduce mode works as it stands: the update is
-        rank-local and identical on every rank (hold the same result on every rank)."""
-        if not isinstance(result, PruneResult) or result.engine is not self:
-            raise ValueError("hold_pruned: a PruneResult of this engine")
-        if self.mode == "wn":
-            raise RuntimeError("hold_pruned: weight-noise mode packs drawn weights in sample(), which knows no mask -- LRT only")
-        if self.sharded:
-            raise RuntimeError("hold_pruned: not with the sharded update (every rank sweeps a slice of the rows)")
-        if not self.fuse_kl:
-            raise RuntimeError("hold_pruned: needs opt.fuse_kl = True (FusedMLP.update is the only update that carries the mask)")
-        if result.version != self._pver:
-            raise RuntimeError("hold_pruned: the parameters changed since this result was taken (prune() again)")
-        masks = []
-        for li in range(len(self.vb)):
-            m = result.mask(li).to(torch.uint8)
-            masks.append(m if self._held is None else torch.bitwise_or(m, self._held[li]))
-        counts = torch.stack([m.sum(dtype=torch.int64) for m in masks]).cpu().tolist()
-        for li, (v, n) in enumerate(zip(self.vb, counts)):
-            if n >= v.O * v.I:
-                raise RuntimeError(f"hold_pruned: VB layer {li} would be left without a kept weight")
-        if self._held is None:
-            self._held = [m.contiguous() for m in masks]
-        else:                                                 # in place: the addresses a captured update holds stay valid
-            for old, m in zip(self._held, masks):
-                old.copy_(m)
-        self._held_counts = [int(n) for n in counts]
-        self.prepare()
-        return self.held
-
-    @_ordered
-    def release_pruned(self):
-        """Drops the held mask and runs the ordinary prepare(): the frozen weights are back, with the values (and Adam moments)
-        they had when they were held."""
-        self._held = self._held_counts = None
-        self.prepare()
-
-    # ---- structured pruning (csrc/units.hip): whole hidden units by the group form of mainviz.lua:20-21, and the compact engine
-    # that is left -- a smaller DENSE network for the ordinary kernels. Nothing of this engine changes: prune_units reads the
-    # fp32 parameters, compact writes a new FusedMLP.
-    def _unit_descs(self, keys, keep, n_keep, lis):
-        descs = (L.UnitDesc * len(lis))()
-        for j, li in enumerate(lis):
-            v = self.vb[li]
-            descs[j] = L.UnitDesc(means=_p(v.means), lvars=_p(v.lvars), O=v.O, I=v.I, key=_p(keys[li]),
-                                  keep=_p(keep[li]) if keep is not None else None,
-                                  n_keep=C.c_void_p(n_keep.data_ptr() + 4 * li) if n_keep is not None else None)
-        return descs
-
-    @_ordered
-    def unit_snr(self, li):
-        """||means[o, :]|| / ||sigma[o, :]|| of VB layer li's output units as an O-element fp32 tensor: the unit pruning key, bit
-        for bit (|mu| / sigma of mainviz.lua:20 when the layer has one input)."""
-        self._need_gathered_parameters("unit_snr")
-        keys = {li: torch.empty(self.vb[li].O, dtype=torch.float32, device=self.device)}
-        L.check(L.lib().vbnn_unit_snr(self.ctx.h, 1, self._unit_descs(keys, None, None, [li])))
-        return keys[li]
-
-    @_ordered
-    def prune_units(self, fraction=None, threshold=None, scope="global", multiple=1):
-        """Prune whole hidden units by signal-to-noise ratio: every output unit of a VB layer with ||mu_o|| / ||sigma_o|| < tau.
-        Exactly one of threshold (tau itself) and fraction in [0, 1] (tau = the exact k-th smallest unit key, k = floor(fraction
-        n_units), so at most k units go -- fewer when keys tie at tau; fraction = 1: tau = +inf). scope = "global": one tau over
-        the units of all VB layers; "layer": the fraction applies to each layer. multiple: every layer's kept count is rounded
-        UP to a multiple of it (capped at the layer's width) by taking back the best of the pruned units -- 256 gives widths the
-        tiled GEMM kernels take; a layer never loses its last unit. Returns a UnitPruneResult (synchronises once, to read tau and
-        the kept counts); nothing changes in this engine -- compact(result) builds the smaller one."""
-        if (fraction is None) == (threshold is None):
-            raise ValueError("prune_units: exactly one of fraction and threshold")
-        if scope not in ("global", "layer"):
-            raise ValueError(f"prune_units: scope = {scope!r} ('global' or 'layer')")
-        if fraction is not None and not 0.0 <= float(fraction) <= 1.0:
-            raise ValueError(f"prune_units: fraction = {fraction} (0 .. 1)")
-        if int(multiple) != multiple or int(multiple) < 1:
-            raise ValueError(f"prune_units: multiple = {multiple} (an integer >= 1)")
-        self._refuse_held("prune_units")
-        self._need_gathered_parameters("prune_units")
-        if not self._shadows_ready:            # (prepare() counts as a parameter change: do it before the snapshot is versioned)
-            self.prepare()
-        lib, ctx, dev, nl = L.lib(), self.ctx.h, self.device, len(self.vb)
-        keys = [torch.empty(v.O, dtype=torch.float32, device=dev) for v in self.vb]
-        keep = [torch.zeros(v.O, dtype=torch.int32, device=dev) for v in self.vb]
-        words = torch.zeros(2 * nl, dtype=torch.int32, device=dev)               # [tau per layer | kept count per layer]: ONE read-back
-        tau, n_keep = words[:nl].view(torch.float32), words[nl:]
-        tau_host = float(threshold) if threshold is not None else float("inf")
-        select = fraction is not None and float(fraction) < 1.0                   # else the threshold is a host value
-        every = list(range(nl))
-        L.check(lib.vbnn_unit_snr(ctx, nl, self._unit_descs(keys, keep, n_keep, every)))
-        for g in ([every] if scope == "global" else [[li] for li in every]):
-            if select:                         # the threshold stays on the device, behind the select
-                n_g = sum(self.vb[li].O for li in g)
-                k = min(int(math.floor(float(fraction) * n_g)), n_g - 1)
-                L.check(lib.vbnn_unit_select(ctx, len(g), self._unit_descs(keys, keep, n_keep, g), k, C.c_void_p(tau.data_ptr() + 4 * g[0])))
-        L.check(lib.vbnn_unit_index(ctx, nl, self._unit_descs(keys, keep, n_keep, every), _p(tau) if select else None, tau_host,
-                                    int(multiple)))
-        host = words.cpu()
-        counts = host[nl:].tolist()
-        return UnitPruneResult(self, scope, multiple, host[:nl].view(torch.float32).tolist() if select else [tau_host] * nl,
-                               [keep[li][:counts[li]] for li in every], self.sizes, self.n_classes, self._pver)
-
-    @_ordered
-    def compact(self, result, **opt_overrides):
-        """The network `result` (a UnitPruneResult of this engine) leaves, as a new, ordinary FusedMLP on the same device: hidden =
-        result.hidden, one process; means / lvars / bias of every VB layer and the final weight gathered on the device (a
-        layer's rows by its own kept list, its columns by the previous layer's; the first layer keeps every input), the final
-        bias copied, prepare()d, with this engine's seed and draw counter and a fresh optimiser state. The removed units'
-        constant activations are dropped, not folded into the next bias. The noise of the compact engine is addressed by the
-        compacted unit index: its sampled predictions are the pruned network's in distribution, not draw for draw.
-        opt_overrides: options of the new engine that differ from this one's."""
-        if not isinstance(result, UnitPruneResult) or result.engine is not self:
-            raise ValueError("compact: a UnitPruneResult of this engine")
-        self._refuse_held("compact")
-        if result.version != self._pver:
-            raise RuntimeError("compact: the parameters changed since this result was taken (prune_units() again)")
-        self._need_gathered_parameters("compact")
-        opt = dict(self.opt)
-        for name in ("exchange_mode", "exchange", "cu_budget"):                   # one process, this engine's stream
-            opt.pop(name, None)
-        opt.update(opt_overrides)
-        opt["hidden"] = list(result.hidden)
-        new = FusedMLP(opt, device=self.device, stream=self.ctx.torch_stream)
-        lib = L.lib()
-        with new._on_stream():
-            cols = None
-            for v, w, rows in zip(self.vb, new.vb, result.keep):
-                a = L.UnitGatherArgs(means=_p(v.means), lvars=_p(v.lvars), bias=_p(v.bias), O=v.O, I=v.I, rows=_p(rows), n_rows=w.O,
-                                     cols=_p(cols), n_cols=w.I, dst_means=_p(w.means), dst_lvars=_p(w.lvars), dst_bias=_p(w.bias))
-                L.check(lib.vbnn_unit_gather(new.ctx.h, C.byref(a)))
-                cols = rows
-            a = L.UnitGatherArgs(means=_p(self.weight3), lvars=None, bias=None, O=self.n_classes, I=self.sizes[-1], rows=None,
-                                 n_rows=self.n_classes, cols=_p(cols), n_cols=new.sizes[-1], dst_means=_p(new.weight3),
-                                 dst_lvars=None, dst_bias=None)
-            L.check(lib.vbnn_unit_gather(new.ctx.h, C.byref(a)))
-            a = L.UnitGatherArgs(means=_p(self.bias3), lvars=None, bias=None, O=1, I=self.n_classes, rows=None, n_rows=1, cols=None,
-                                 n_cols=self.n_classes, dst_means=_p(new.bias3), dst_lvars=None, dst_bias=None)     # (a plain copy)
-            L.check(lib.vbnn_unit_gather(new.ctx.h, C.byref(a)))
-            new.draw = self.draw
-            if new._draw_dev is not None:      # the new engine's device counter starts at zero: advance it to the mirror
-                L.check(lib.vbnn_sample(new.ctx.h, _p(new._draw_dev), self.draw))
-        new.prepare()
-        return new
-
-    def prune_units_curve(self, inputs, targets, fractions, S=None, map=False, scope="global", multiple=1):
-        """What unit pruning costs: for every fraction q a prune_units(fraction=q, scope=scope, multiple=multiple), the compact
-        engine and its predict(inputs, S, targets, map). One dict per fraction: fraction, tau (per layer), hidden, n_weights,
-        nll, accuracy, mean_draw_nll, mean_draw_accuracy, mutual_info (mean over rows). Every compact engine starts from THIS
-        engine's draw counter, which does not move: the points see the same draws (addressed by their own unit indices)."""
-        rows = []
-        for q in fractions:
-            res = self.prune_units(fraction=q, scope=scope, multiple=multiple)
-            p = self.compact(res).predict(inputs, S=S, targets=targets, map=map)
-            rows.append(dict(fraction=float(q), tau=res.tau, hidden=res.hidden, n_weights=res.n_weights, nll=p.nll,
-                             accuracy=p.accuracy, mean_draw_nll=p.mean_draw_nll, mean_draw_accuracy=p.mean_draw_accuracy,
-                             mutual_info=float(p.mutual_info.mean().item())))
-        return rows
-
-    # ---- signal-to-noise pruning (mainviz.lua:20-27) and the pruned view of predict(). Nothing of the training step is
-    # touched: the pruned operands are shadows of their own (PruneResult), read by predict() alone while the view is set.
-    def _prune_descs(self, mu_p, var_p, stats, lis, masks=None):
-        descs = (L.PruneDesc * len(lis))()
-        for j, li in enumerate(lis):
-            v = self.vb[li]
-            descs[j] = L.PruneDesc(means=_p(v.means), lvars=_p(v.lvars), O=v.O, I=v.I, mu_p=mu_p[li].ptr, var_p=var_p[li].ptr,
-                                   ld_w=mu_p[li].ld, stats=C.c_void_p(stats[li].data_ptr()),
-                                   mask=_p(masks[li]) if masks is not None else None)
-        return descs
-
-    @_ordered
-    def snr(self, li):
-        """|means / sqrt(exp(lvars))| of VB layer li (mainviz.lua:20) as an O x I fp32 tensor: the pruning key, bit for bit."""
-        self._need_gathered_parameters("snr")
-        v = self.vb[li]
-        out = torch.empty_like(v.means)
-        L.check(L.lib().vbnn_snr(self.ctx.h, _p(v.means), _p(v.lvars), v.O * v.I, _p(out)))
-        return out
-
-    @_ordered
-    def prune(self, fraction=None, threshold=None, scope="global"):
-        """Prune by signal-to-noise ratio: every weight with |mu| / sigma < tau (mainviz.lua:20-21). Exactly one of
-        threshold (tau itself; the reference uses 0.005) and fraction in [0, 1] (tau = the exact k-th smallest key,
-        k = floor(fraction W), so at most k weights go -- fewer when keys tie at tau; fraction = 1: tau = +inf, everything).
-        scope = "global": one tau over all VB layers; "layer": the fraction applies to each layer (one tau per layer).
-        Returns a PruneResult (synchronises to read tau and the counts); nothing changes for predict() until use_pruned.
-        Under a held mask (hold_pruned) the keys are still those of the raw fp32 parameters, frozen weights included."""
-        if (fraction is None) == (threshold is None):
-            raise ValueError("prune: exactly one of fraction and threshold")
-        if scope not in ("global", "layer"):
-            raise ValueError(f"prune: scope = {scope!r} ('global' or 'layer')")
-        if fraction is not None and not 0.0 <= float(fraction) <= 1.0:
-            raise ValueError(f"prune: fraction = {fraction} (0 .. 1)")
-        self._need_gathered_parameters("prune")
-        if not self._shadows_ready:            # (predict under the view reads the packed final weight)
-            self.prepare()
-        lib, ctx, dev, nl = L.lib(), self.ctx.h, self.device, len(self.vb)
-        mu_p = [_Packed(v.O, v.I, self.tdt, dev) for v in self.vb]
-        var_p = [_Packed(v.O, v.I, self.tdt, dev) for v in self.vb]
-        stats = torch.zeros(nl, 4, dtype=torch.float64, device=dev)
-        tau = torch.full((nl,), float(threshold) if threshold is not None else float("inf"), dtype=torch.float32, device=dev)
-        groups = [list(range(nl))] if scope == "global" else [[li] for li in range(nl)]
-        nbytes = C.c_size_t()
-        L.check(lib.vbnn_prune_workspace_bytes(nl, self._prune_descs(mu_p, var_p, stats, list(range(nl))), C.byref(nbytes)))
-        if self._prune_ws is None or self._prune_ws.numel() < nbytes.value:
-            self._prune_ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        for g in groups:
-            descs = self._prune_descs(mu_p, var_p, stats, g)
-            Wg = sum(self.vb[li].O * self.vb[li].I for li in g)
-            k = int(math.floor(float(fraction) * Wg)) if fraction is not None else Wg
-            tau_g = C.c_void_p(tau.data_ptr() + 4 * g[0]) if k < Wg else None       # on the device, behind the select
-            if tau_g is not None:
-                L.check(lib.vbnn_prune_select(ctx, len(g), descs, k, tau_g, _p(self._prune_ws), self._prune_ws.numel()))
-                if len(g) > 1:
-                    tau[g[0] + 1:g[-1] + 1] = tau[g[0]]
-            L.check(lib.vbnn_prune_pack(ctx, self.code, len(g), descs, tau_g,
-                                        float(threshold) if threshold is not None else float("inf")))
-        return PruneResult(self, scope, tau.cpu().tolist(), stats.cpu().tolist(), mu_p, var_p, self._pver)
-
-    @_ordered
-    def _prune_mask(self, res, li):
-        if res.engine is not self or res.version != self._pver:
-            raise RuntimeError("PruneResult.mask: the parameters changed since this result was taken")
-        self._need_gathered_parameters("mask")
-        v = self.vb[li]
-        masks = {li: torch.zeros(v.O, v.I, dtype=torch.uint8, device=self.device)}
-        stats = {li: torch.zeros(4, dtype=torch.float64, device=self.device)}
-        descs = self._prune_descs(res.mu_p, res.var_p, stats, [li], masks)          # the same sweep: the shadows get the same bits
-        L.check(L.lib().vbnn_prune_pack(self.ctx.h, self.code, 1, descs, None, res.tau[li]))
-        return masks[li].bool()
-
-    def use_pruned(self, result):
-        """predict() reads the pruned operands of `result` (a PruneResult of this engine) from now on; None: the unpruned
-        shadows again. Nothing else looks at the view: run / test / update / prepare and their operands are untouched
-        (hold_pruned is what trains a pruned network)."""
-        if result is not None and (not isinstance(result, PruneResult) or result.engine is not self):
-            raise ValueError("use_pruned: a PruneResult of this engine, or None")
-        self._pruned = result
-
-    @contextlib.contextmanager
-    def pruned(self, result):
-        """with eng.pruned(result): ... -- use_pruned(result) for the block, the previous view afterwards."""
-        prev = self._pruned
-        self.use_pruned(result)
-        try:
-            yield result
-        finally:
-            self._pruned = prev
-
-    def prune_curve(self, inputs, targets, fractions, S=None, map=False, scope="global"):
-        """What pruning costs: for every fraction q a prune(fraction=q, scope=scope) and a predict(inputs, S, targets, map)
-        under that view. One dict per fraction: fraction, tau (per layer), n_pruned, nll, accuracy, mean_draw_nll,
-        mean_draw_accuracy, mutual_info (mean over rows). The keys are re-formed by every select and pack sweep (nothing per
-        weight is kept between the points). Each point consumes S draws as a predict() call of its own would (none with
-        map=True), so the points see different noise; the engine's view is afterwards what it was before."""
-        rows = []
-        for q in fractions:
-            res = self.prune(fraction=q, scope=scope)
-            with self.pruned(res):
-                p = self.predict(inputs, S=S, targets=targets, map=map)
-            rows.append(dict(fraction=float(q), tau=res.tau, n_pruned=res.n_pruned, nll=p.nll, accuracy=p.accuracy,
-                             mean_draw_nll=p.mean_draw_nll, mean_draw_accuracy=p.mean_draw_accuracy,
-                             mutual_info=float(p.mutual_info.mean().item())))
-        return rows
-
-    def prune_curve_sparse(self, inputs, targets, fractions, S=None, map=False, scope="global"):
-        """prune_curve with every point evaluated through the compressed form (prune(...).compress() as the view)."""
-        rows = []
-        for q in fractions:
-            res = self.prune(fraction=q, scope=scope).compress()
-            with self.pruned(res):
-                p = self.predict(inputs, S=S, targets=targets, map=map)
-            rows.append(dict(fraction=float(q), tau=res.tau, n_pruned=res.n_pruned, nnz=sum(res.nnz), nbytes=res.nbytes,
-                             dense_nbytes=res.dense_nbytes, nll=p.nll, accuracy=p.accuracy, mean_draw_nll=p.mean_draw_nll,
-                             mean_draw_accuracy=p.mean_draw_accuracy, mutual_info=float(p.mutual_info.mean().item())))
-        return rows
-
-    # ---- the compressed pruned view (csrc/sparse.hip). compress: a PruneResult's kept weights as CSR, built on the device at
-    # the result's own tau (the entry count is known from its statistics: no extra synchronisation before the allocation).
-    # _predict_forward_sparse: predict's forward under such a view -- K-major activations from layer to layer (xT from the
-    # input packer, hT from every layer but the last, which writes the row-major h the head reads), squares formed in registers.
-    @_ordered
-    def _compress(self, res):
-        if not isinstance(res, PruneResult) or res.engine is not self:
-            raise ValueError("compress: a PruneResult of this engine")
-        self._refuse_held("compress")
-        if res.version != self._pver:
-            raise RuntimeError("compress: the parameters changed since this result was taken (prune() again)")
-        if isinstance(res, SparsePruneResult):
-            return res
-        self._need_gathered_parameters("compress")
-        lib, ctx, dev, nl = L.lib(), self.ctx.h, self.device, len(self.vb)
-        nnz = [int(st[3]) - int(st[0]) for st in res.stats]                       # W - pruned, as vbnn_prune_pack counted them
-        idx = [2 if v.I <= 65536 else 4 for v in self.vb]
-        row_ptr = [torch.zeros(v.O + 1, dtype=torch.int32, device=dev) for v in self.vb]
-        cols = [torch.zeros(max(n, 1), dtype=torch.int16 if ib == 2 else torch.int32, device=dev) for n, ib in zip(nnz, idx)]
-        mu_v = [torch.zeros(max(n, 1), dtype=self.tdt, device=dev) for n in nnz]
-        var_v = [torch.zeros(max(n, 1), dtype=self.tdt, device=dev) for n in nnz]
-        nnz_dev = torch.zeros(nl, dtype=torch.int32, device=dev)
-        for li, v in enumerate(self.vb):
-            pd = (L.PruneDesc * 1)(L.PruneDesc(means=_p(v.means), lvars=_p(v.lvars), O=v.O, I=v.I))
-            sd = (L.SparseDesc * 1)(L.SparseDesc(row_ptr=_p(row_ptr[li]), cols=_p(cols[li]), mu_v=_p(mu_v[li]), var_v=_p(var_v[li]),
-                                                 O=v.O, I=v.I, nnz_cap=nnz[li], nnz_dev=C.c_void_p(nnz_dev.data_ptr() + 4 * li),
-                                                 idx_bytes=idx[li]))
-            L.check(lib.vbnn_prune_compress(ctx, self.code, 1, pd, sd, None, res.tau[li]))
-        got = [n & 0xffffffff for n in nnz_dev.cpu().tolist()]
-        if got != nnz:
-            raise RuntimeError(f"compress: the device kept {got} weights per layer, the pruning's statistics say {nnz}")
-        esz = torch.empty(0, dtype=self.tdt).element_size()
-        dense = sum(2 * v.O * L.pad_ld(v.I) * esz for v in self.vb)
-        return SparsePruneResult(res, row_ptr, cols, mu_v, var_v, nnz, idx, dense)
-
-    def _sparse_buffers(self, rows):
-        """K-major operands of the sparse forward: T[0] the packed input's transpose, T[li + 1] layer li's hT (ping-pong per
-        hidden width, as _predict_buffers). Kept across calls while the row count holds."""
-        if getattr(self, "_sparse_key", None) != rows:
-            slots = {}
-            T = [_Packed(self.sizes[0], rows, self.tdt, self.device)]
-            for li, v in enumerate(self.vb[:-1]):
-                if (v.O, li % 2) not in slots:
-                    slots[(v.O, li % 2)] = _Packed(v.O, rows, self.tdt, self.device)
-                T.append(slots[(v.O, li % 2)])
-            self._sparse_bufs, self._sparse_key = T, rows
-        return self._sparse_bufs
-
-    def _predict_forward_sparse(self, bufs, x, N, rpd, draw, row0, lrt, pack=True):
-        """_predict_forward under a compressed view: vbnn_pack_input (with the transposed copy) + vbnn_forward_sparse per layer."""
-        lib, ctx, code = L.lib(), self.ctx.h, self.code
-        pv, nl = self._pruned, len(self.vb)
-        T = self._sparse_buffers(bufs[0].x.t.shape[0])
-        if pack:                               # (the packer always writes the row-major copy too; no sparse layer reads it)
-            b0 = bufs[0]
-            L.check(lib.vbnn_pack_input(ctx, code, _p(x), x.stride(0), N, self.sizes[0], b0.x.ptr, None, b0.x.ld, T[0].ptr, None,
-                                        T[0].ld, rpd))
-        for li, v in enumerate(self.vb):
-            last = li == nl - 1
-            out = bufs[li + 1]
-            a = L.SparseFwdArgs(row_ptr=_p(pv.row_ptr[li]), cols=_p(pv.cols[li]), mu_v=_p(pv.mu_v[li]),
-                                var_v=_p(pv.var_v[li]) if lrt else None, idx_bytes=pv.idx_bytes[li], xT=T[li].ptr, x2T=None,
-                                ld_xT=T[li].ld, N=N, I=v.I, O=v.O, bias=_p(v.bias), seed=self.seed, layer=v.layer_id, draw=draw,
-                                row0=row0, y=None, ld_y=0, relu=1, h=out.x.ptr if last else None, h2=None,
-                                ld_h=out.x.ld if last else 0, hT=None if last else T[li + 1].ptr, h2T=None,
-                                ld_hT=0 if last else T[li + 1].ld, rows_per_draw=rpd)
-            L.check(lib.vbnn_forward_sparse(ctx, code, C.byref(a)))

@@ -13,6 +13,7 @@ into libvbnn_hip.so through include/vbnn_hip.h on raw device pointers. Differenc
 Lua surface, all forced by the host language: class targets are 0-based; `opt` is a dict.
 """
 import ctypes as C
+import functools
 import math
 
 import torch
@@ -20,6 +21,20 @@ import torch
 from . import _lib as L
 
 _DT = {"f32": (L.F32, torch.float32), "bf16": (L.BF16, torch.bfloat16)}
+
+
+class _VB:
+    pass
+
+
+def _ordered(fn):
+    """Engine entry points that launch or allocate: the body runs with the engine's stream as torch's current stream, that
+    stream ordered behind whatever the caller queued on ITS current stream before the call (FusedMLP._on_stream)."""
+    @functools.wraps(fn)
+    def wrapped(self, *args, **kwargs):
+        with self._on_stream():
+            return fn(self, *args, **kwargs)
+    return wrapped
 
 
 def _p(t):
