@@ -782,6 +782,62 @@ typedef struct vbnn_gauss_moments_args {
 } vbnn_gauss_moments_args;
 int vbnn_predict_gauss_moments(vbnn_ctx* ctx, const vbnn_gauss_moments_args* a);
 
+/* The class-probability posterior predictive for ANY class count (additive, ABI 6): what vbnn_head_predict states above for
+ * C <= 16, from the final Linear's f32 logits y_s (R x C per draw, as vbnn_forward writes them) instead of from h, with the
+ * top-K classes of the averaged prediction. The third member of the moments family: all arithmetic is fp32, operation by
+ * operation as written here (compiled without floating-point contraction; the division is correctly rounded).
+ * Per row and draw, in draw order:
+ *   mx = max_c y[c], arg_s = its first index;   lse = mx + logf(sum_c expf(y[c] - mx));   o[c] = y[c] - lse
+ *   per class the online logsumexp L[c]: draw 0 sets L = o, every later draw L = max(L, o) + log1p(exp(-|L - o|)) -- never a
+ *     sum of probabilities, which underflow. Here log1p(u), u = expf(-|L - o|) in [0, 1], is evaluated as
+ *     w = 1 + u;  log1p(u) = (logf(w) * u) / (w - 1)  (u itself where w = 1): w - 1 is exact and the correctly rounded quotient
+ *     restores what rounding 1 + u lost -- within 3 ulp of log1p, at a fraction of the library log1pf's instructions;
+ *   per row the running sums  sum_s H_s with H_s = -sum_c expf(o[c]) * o[c]  and, with a target t (clamped to [0, C - 1]),
+ *     sum_s -o[t]  and  sum_s [arg_s = t]  (draw 0 starts each).
+ * Finish per row:  log_p[c] = L[c] - logf(float(S));  p[c] = expf(log_p[c]);  entropy = -sum_c p[c] * log_p[c];
+ *   expected_entropy = (sum_s H_s) / float(S);  mutual_info = entropy - expected_entropy (S = 1 gives exactly 0);
+ *   top-K: K rounds of "the first maximum of log_p among the classes not yet taken" (ties go to the lower index) give
+ *   topk_idx (R x K) and topk_prob = expf of that log_p (bitwise probs at topk_idx);  pred = argmax log_p (first maximum),
+ *   which is topk_idx[:, 0] when K >= 1.
+ * Every row sum (sum_c expf, H_s, entropy) is formed in an order that depends on C alone, by the family's rule: a row is
+ * worked by T = 64 threads (C <= 256, four rows per workgroup) or T = 256 (above); thread i adds, in ascending order, the
+ * columns 4 q .. 4 q + 3 of its quads q = i, i + T, ...; the threads of a wave are added by the xor butterfly 32, 16, .. 1; the
+ * four waves in wave order. Maximum and arg-max reductions take the lower index among equal maxima. The same assignment holds
+ * on the 16-byte and on the scalar access path (chosen per launch from the leading dimensions and the base addresses; a row's
+ * last, partial quad always goes element by element), in both forms, for every R and row position. Pad columns are never read.
+ * Logits are finite or NaN. A NaN logit makes every float output of its row NaN (topk_prob included) and the float totals
+ * ([0] and [2]) NaN, and leaves every other row bit for bit alone; pred and topk_idx of such a row are unspecified but inside
+ * [0, C - 1]. Infinite logits (-inf as a mask included) are NOT supported in this version: the outputs of such a row are
+ * unspecified.
+ * VBNN_MOMENTS_STACKED: y holds all S draws (draw s = rows [s R, (s+1) R)); one call walks them with L in registers
+ * (C <= VBNN_CLASS_MOMENTS_STACKED_MAX_C; draw / state ignored). VBNN_MOMENTS_ACCUMULATE: y holds ONE draw, number `draw`; the
+ * running values live in `state` between the S calls, any C. Both forms run one device function per draw: given the same y per
+ * draw, every output and total is bitwise equal between them. */
+#define VBNN_CLASS_MOMENTS_STACKED_MAX_C 4096   /* largest C the STACKED form takes */
+#define VBNN_CLASS_MOMENTS_MAX_K 8              /* largest K */
+typedef struct vbnn_class_moments_args {
+    const float* y; int64_t ld_y;       /* f32 logits: S R x C (STACKED; draw s = rows [s R, (s+1) R)) or R x C (ACCUMULATE); ld_y >= C */
+    const int32_t* target;              /* R class indices, or NULL: no totals */
+    int64_t R, C, S;                    /* minibatch rows, classes (>= 1, any), draws of the WHOLE prediction (>= 1) */
+    int32_t form;                       /* VBNN_MOMENTS_STACKED or VBNN_MOMENTS_ACCUMULATE */
+    int32_t draw;                       /* ACCUMULATE: 0-based index of this draw; 0 starts the state (nothing is read from it), S - 1 finishes */
+    int64_t K;                          /* top-K classes: 0 .. min(VBNN_CLASS_MOMENTS_MAX_K, C) */
+    float* state; int64_t ld_state;     /* ACCUMULATE: R x ld_state floats, ld_state >= C + 3, row r = { L[0 .. C-1], sum H, sum -o[t], hits }
+                                         * (a multiple of 4 on a 16-byte base takes the 16-byte path) */
+    /* outputs of the finish, each optional (NULL to skip -- probs and log_probs too: R x C of stores) */
+    float* probs; float* log_probs; int64_t ld_out;   /* R x C each */
+    float* entropy;                     /* R: H[p] (total predictive uncertainty) */
+    float* expected_entropy;            /* R: 1/S sum_s H(p_s) (the aleatoric part) */
+    float* mutual_info;                 /* R: entropy - expected_entropy (the epistemic part) */
+    int32_t* pred;                      /* R: argmax p */
+    int32_t* topk_idx; float* topk_prob;   /* R x K each (need K >= 1) */
+    /* with target: 5 doubles WRITTEN by the finish, { sum_r -log_p[t_r], sum_r [pred = t_r], sum_{r,s} -o_s[t_r],
+     * sum_{r,s} [arg_s = t_r], sum_r [t_r in top-K] (0 when K = 0) }, each summed over rows in double in a fixed order (workgroup
+     * partials, one finish block; no float atomics). NULL to skip. */
+    double* totals;
+} vbnn_class_moments_args;
+int vbnn_predict_class_moments(vbnn_ctx* ctx, const vbnn_class_moments_args* a);
+
 /* ---- signal-to-noise pruning (additive, ABI 6): mainviz.lua:20-27 on the device, and the pruned operand shadows that let
  * vbnn_forward / vbnn_head_predict evaluate the pruned network ---------------------------------------------------------------
  * The key of a weight is snr = |means / sqrt(exp(lvars))| in fp32, operation for operation as mainviz.lua:20 forms

@@ -290,6 +290,23 @@ typedef struct vbnn_gauss_moments_args {
     double* totals;
 } vbnn_gauss_moments_args;
 int vbnn_predict_gauss_moments(vbnn_ctx* ctx, const vbnn_gauss_moments_args* a);
+typedef struct vbnn_class_moments_args {
+    const float* y; int64_t ld_y;
+    const int32_t* target;
+    int64_t R, C, S;
+    int32_t form;
+    int32_t draw;
+    int64_t K;
+    float* state; int64_t ld_state;
+    float* probs; float* log_probs; int64_t ld_out;
+    float* entropy;
+    float* expected_entropy;
+    float* mutual_info;
+    int32_t* pred;
+    int32_t* topk_idx; float* topk_prob;
+    double* totals;
+} vbnn_class_moments_args;
+int vbnn_predict_class_moments(vbnn_ctx* ctx, const vbnn_class_moments_args* a);
 typedef struct vbnn_prune_desc {
     const float* means; const float* lvars; int64_t O, I;
     void* mu_p; void* var_p; int64_t ld_w;

@@ -118,6 +118,17 @@ class GaussMomentsArgs(C.Structure):  # vbnn_gauss_moments_args
 GAUSS_MOMENTS_STACKED_MAX_D = 8192    # VBNN_GAUSS_MOMENTS_STACKED_MAX_D
 
 
+class ClassMomentsArgs(C.Structure):  # vbnn_class_moments_args
+    _fields_ = [("y", _vp), ("ld_y", _i64), ("target", _vp), ("R", _i64), ("C", _i64), ("S", _i64),
+                ("form", C.c_int32), ("draw", C.c_int32), ("K", _i64), ("state", _vp), ("ld_state", _i64),
+                ("probs", _vp), ("log_probs", _vp), ("ld_out", _i64), ("entropy", _vp), ("expected_entropy", _vp),
+                ("mutual_info", _vp), ("pred", _vp), ("topk_idx", _vp), ("topk_prob", _vp), ("totals", _vp)]
+
+
+CLASS_MOMENTS_STACKED_MAX_C = 4096    # VBNN_CLASS_MOMENTS_STACKED_MAX_C
+CLASS_MOMENTS_MAX_K = 8               # VBNN_CLASS_MOMENTS_MAX_K
+
+
 class PruneDesc(C.Structure):         # vbnn_prune_desc
     _fields_ = [("means", _vp), ("lvars", _vp), ("O", _i64), ("I", _i64), ("mu_p", _vp), ("var_p", _vp), ("ld_w", _i64),
                 ("stats", _vp), ("mask", _vp)]
@@ -234,6 +245,7 @@ _SIGS = {
     "vbnn_gauss_nll_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _f, _f, _vp, _i64, _i, _vp], _i),
     "vbnn_gauss_nll_backward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _f, _f, _vp, _i64], _i),
     "vbnn_predict_gauss_moments": ([_vp, C.POINTER(GaussMomentsArgs)], _i),
+    "vbnn_predict_class_moments": ([_vp, C.POINTER(ClassMomentsArgs)], _i),
     "vbnn_snr": ([_vp, _vp, _vp, _i64, _vp], _i),
     "vbnn_prune_workspace_bytes": ([_i, _vp, C.POINTER(C.c_size_t)], _i),
     "vbnn_prune_select": ([_vp, _i, _vp, _i64, _vp, _vp, C.c_size_t], _i),

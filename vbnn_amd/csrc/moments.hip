@@ -1,7 +1,7 @@
 // moments.hip -- vbnn_predict_moments: the regression posterior predictive (include/vbnn_hip.h): Welford mean / M2 over the S
 // draws of the final Linear's f32 outputs, per-row squared errors and the online logsumexp of the mixture's log density.
 // vbnn_predict_gauss_moments (second half of the file): the same for the heteroscedastic Gaussian head, whose rows carry a
-// log noise variance beside every mean; it shares the access, row-sum, logsumexp and partial-sum functions below.
+// log noise variance beside every mean; it shares the logsumexp below and the access, row-sum and partial-sum functions of moments_common.h.
 // A streaming kernel: no MFMA, no LDS in the column loop; LDS only carries the four waves' row partials. Compiled WITHOUT
 // floating-point contraction (Makefile): every line below is the fp32 operation it spells.
 //
@@ -9,55 +9,18 @@
 // the quads q = i, i + TR, ... (columns 4 q .. 4 q + 3) on the 16-byte AND on the scalar path, so a row sum's order depends on
 // D alone. STACKED keeps mean / M2 / target of a thread's quads in registers across the draws (NQ quads: D <= 4 . 256 . NQ) and
 // loads draw s + 1 while draw s is reduced; ACCUMULATE streams the state through NQ quads per thread at a time.
-#include "common.h"
+#include "moments_common.h"
 #include <math.h>
 #include <algorithm>
 
 constexpr int MOM_NQ = 4;
 static_assert(VBNN_MOMENTS_STACKED_MAX_D == 4 * 256 * MOM_NQ, "the STACKED form's register tile");
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct MomArgs {
     const float* y; int64_t ld_y; const float* t; int64_t ld_t; int64_t R, D; int S, draw; float noise_var;
     float* state; float* mean; float* var; int64_t ld_out; float* row_var; float* row_sq_err; float* row_log_lik; double* part;
     int y_vec, t_vec, o_vec, s_vec;            // 16-byte access allowed (s_vec: the state's rows alternate 16 / 8-byte alignment)
 };
-
-// four consecutive floats; mode 2: one 16-byte access, 1: two 8-byte, 0: element by element (`valid` of them). The streams a
-// launch reads or writes once take the nontemporal hint (NT) on their vector accesses; 4-byte stores stay plain, which the L2
-// combines (the update sweep's finding).
-template <bool NT>
-__device__ __forceinline__ void mom_load4(const float* p, float (&v)[4], int valid, int mode) {
-    v[0] = v[1] = v[2] = v[3] = 0.f;
-    if (valid == 0) return;
-    if (mode == 2) {
-        const f32x4 t = NT ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)) : *reinterpret_cast<const f32x4*>(p);
-        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-    } else if (mode == 1) {
-        const f32x2* p2 = reinterpret_cast<const f32x2*>(p);
-        const f32x2 a = NT ? __builtin_nontemporal_load(p2) : p2[0];
-        const f32x2 b = NT ? __builtin_nontemporal_load(p2 + 1) : p2[1];
-        v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (j < valid) v[j] = NT ? __builtin_nontemporal_load(p + j) : p[j];
-    }
-}
-template <bool NT>
-__device__ __forceinline__ void mom_store4(float* p, const float (&v)[4], int valid, int mode) {
-    if (valid == 0) return;
-    if (mode == 2) {
-        const f32x4 t = {v[0], v[1], v[2], v[3]};
-        if (NT) __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(p)); else *reinterpret_cast<f32x4*>(p) = t;
-    } else if (mode == 1) {
-        f32x2* p2 = reinterpret_cast<f32x2*>(p);
-        const f32x2 a = {v[0], v[1]}, b = {v[2], v[3]};
-        if (NT) { __builtin_nontemporal_store(a, p2); __builtin_nontemporal_store(b, p2 + 1); } else { p2[0] = a; p2[1] = b; }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (j < valid) p[j] = v[j];
-    }
-}
 
 // ---- THE per-draw update, one quad: both forms call this and nothing else on a draw's elements
 __device__ __forceinline__ void mom_draw_quad(const float (&y)[4], const float (&t)[4], bool has_t, int valid, float n,
@@ -102,44 +65,6 @@ __device__ __forceinline__ void mom_finish_row(const MomArgs& a, int64_t r, floa
         if (a.row_log_lik) a.row_log_lik[r] = ll;
     }
     tot[0] += (double)sq; tot[1] += (double)sumE; tot[2] += (double)ll; tot[3] += (double)vs;
-}
-
-// sum over the row's threads: lane-strided partials in, the xor butterfly inside a wave, the waves in wave order through LDS.
-// Every thread of the row returns the same bits. WPR == 4: block-uniform call (two barriers).
-template <int WPR, int N>
-__device__ __forceinline__ void mom_row_sum(float (&v)[N], float (*red)[4], int wave) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] += __shfl_xor(v[k], off, 64);
-    if (WPR == 1) return;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < N; ++k) red[k][wave] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-    __syncthreads();
-}
-
-// the workgroup's partial of the NT totals (four; the Gaussian head's five): [NT][gridDim.x] doubles, which k_moments_finish
-// adds in workgroup order
-template <int WPR, int NT>
-__device__ __forceinline__ void mom_store_partials(double* part, const double (&tot)[NT], double (*dred)[4], int wave, int tr) {
-    if (!part) return;                                     // launch-uniform
-    if (WPR == 1) {
-        if (tr == 0)
-#pragma unroll
-            for (int k = 0; k < NT; ++k) dred[k][wave] = tot[k];
-        __syncthreads();
-        if (threadIdx.x < NT) {
-            const int k = threadIdx.x;
-            part[(int64_t)k * gridDim.x + blockIdx.x] = ((dred[k][0] + dred[k][1]) + dred[k][2]) + dred[k][3];
-        }
-    } else if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < NT; ++k) part[(int64_t)k * gridDim.x + blockIdx.x] = tot[k];
-    }
 }
 
 template <int WPR>

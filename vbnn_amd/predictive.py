@@ -1,4 +1,4 @@
-"""The posterior predictives of the fused engine (FusedMLP.predict / predict_regression): forward-only passes on buffers of
+"""The posterior predictives of the fused engine (FusedMLP.predict / predict_classes / predict_regression): forward-only passes on buffers of
 their own, dense or under a pruned view (pruning.py). A mixin of vbnn_amd/engine.py:FusedMLP."""
 import ctypes as C
 import math
@@ -21,12 +21,17 @@ class PredictResult:
     1/S sum_s softmax(f_s(x)) and its log), entropy (H[p]), expected_entropy (1/S sum_s H(p_s)), mutual_info (their difference:
     the epistemic part), pred (int32, argmax p). With targets also Python floats: nll (mean -log p[t]) and accuracy (percent)
     of the averaged prediction, and mean_draw_nll / mean_draw_accuracy -- the mean over draws of each draw's NLL and accuracy,
-    the two numbers test() returns. None without targets."""
+    the two numbers test() returns. None without targets.
+    FusedMLP.predict_classes (any class count) returns the same fields with the same meanings (probs / log_probs None with
+    keep_probs=False) and, with topk = K > 0, topk_idx (R x K int32: the K most probable classes, most probable first, ties to
+    the lower index) and topk_prob (R x K: their probabilities), with targets topk_accuracy (percent of rows whose target is
+    among them); with keep_draws, draws (S x R x C: every draw's logits). totals: the library's sums."""
 
     def __init__(self, probs, log_probs, entropy, expected_entropy, mutual_info, pred):
         self.probs, self.log_probs, self.entropy = probs, log_probs, entropy
         self.expected_entropy, self.mutual_info, self.pred = expected_entropy, mutual_info, pred
         self.nll = self.accuracy = self.mean_draw_nll = self.mean_draw_accuracy = None
+        self.totals = self.topk_idx = self.topk_prob = self.topk_accuracy = self.draws = None
         self.S, self.stacked, self.chunks = None, None, None
 
 
@@ -251,7 +256,7 @@ class _Predictive:
         RegressionPredictResult of this rank's rows (no collective, as test()).
         criterion = "gauss": D = n_classes / 2, the network supplies the noise (noise_var must be None), the result carries the
         aleatoric noise_var beside the epistemic var, and keep_draws returns the S x R x 2 D outputs (means, log variances)."""
-        lib, ctx, code = L.lib(), self.ctx.h, self.code
+        lib, ctx = L.lib(), self.ctx.h
         if self.criterion not in ("mse", "gauss"):
             raise ValueError("predict_regression: the regression predictive needs the MSE criterion or the Gaussian one "
                              "(criterion = 'nll': use predict)")
@@ -272,8 +277,7 @@ class _Predictive:
             assert targets.dtype == torch.float32 and targets.is_cuda and tuple(targets.shape) == (R, D)
             targets = targets.contiguous()
         p = self._predictive_plan("predict_regression", inputs, S, map, row0)
-        x, R, S, map, row0, lrt = p.x, p.R, p.S, p.map, p.row0, p.lrt
-        stacked, Rc, n_chunks, op_rows, bufs, wts, d0 = p.stacked, p.Rc, p.n_chunks, p.op_rows, p.bufs, p.wts, p.d0
+        R, S, map, stacked, Rc, n_chunks = p.R, p.S, p.map, p.stacked, p.Rc, p.n_chunks
         f32 = dict(dtype=torch.float32, device=self.device)
         has_t = targets is not None
         res = RegressionPredictResult(torch.empty(R, D, **f32), torch.empty(R, D, **f32), torch.empty(R, **f32),
@@ -282,16 +286,9 @@ class _Predictive:
                                       torch.empty(S, R, Wd, **f32) if keep_draws else None)
         if gauss:
             res.noise_var, res.row_noise_var = torch.empty(R, D, **f32), torch.empty(R, **f32)
-        direct = keep_draws and (not stacked or n_chunks == 1)      # the final Linear writes into res.draws itself
-        ybuf = None
-        if not direct:                                               # the y buffer: kept with the predict buffers
-            ybuf = bufs.y_reg
-            if ybuf is None or tuple(ybuf.shape) != (op_rows, Wd):
-                ybuf = bufs.y_reg = torch.empty(op_rows, Wd, **f32)
         one_call = stacked and D <= (L.GAUSS_MOMENTS_STACKED_MAX_D if gauss else L.MOMENTS_STACKED_MAX_D)   # else: ACCUMULATE per draw
         state = None if one_call else torch.empty(Rc, (3 if gauss else 2) * D + 2, **f32)
         totals = torch.zeros(n_chunks, 5 if gauss else 4, dtype=torch.float64, device=self.device) if has_t else None
-        nl, H = len(self.vb), self.sizes[-1]
         form = L.MOMENTS_STACKED if one_call else L.MOMENTS_ACCUMULATE
         if gauss:
             a = L.GaussMomentsArgs(ld_y=Wd, ld_t=D, D=D, S=S, form=form, s_min=self.logvar_clamp[0], s_max=self.logvar_clamp[1],
@@ -304,46 +301,16 @@ class _Predictive:
         def off(t, row):
             return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
 
-        def final_linear(N, y_ptr):
-            fa = L.FwdArgs(w=self.w3_s.ptr, w2=None, x=bufs[nl].x.ptr, x2=None, ld_w=self.w3_s.ld, ld_x=bufs[nl].x.ld,
-                           N=N, I=H, O=Wd, bias=_p(self.bias3), y=y_ptr, ld_y=Wd)
-            L.check(lib.vbnn_forward(ctx, code, C.byref(fa)))
-
-        for k in range(n_chunks):
-            c0 = k * Rc
-            rows = min(Rc, R - c0)
-            xc = x[c0:c0 + rows]
+        def point(c0, rows):                   # the chunk's targets and outputs
             a.R = rows
             a.target = off(targets, c0 * D)
-            a.totals = C.c_void_p(totals[k].data_ptr()) if has_t else None
+            a.totals = C.c_void_p(totals[c0 // Rc].data_ptr()) if has_t else None
             a.mean, a.var = off(res.mean, c0 * D), off(res.var, c0 * D)
             a.row_var, a.row_sq_err, a.row_log_lik = off(res.row_var, c0), off(res.row_sq_err, c0), off(res.row_log_lik, c0)
             if gauss:
                 a.noise_var, a.row_noise_var = off(res.noise_var, c0 * D), off(res.row_noise_var, c0)
-            if stacked:                        # every draw in one forward: draw s = rows [s rows, (s+1) rows) of y
-                if wts is not None:
-                    self._predict_wn_sample(wts, None if map else d0)
-                self._predict_forward(bufs, wts, xc, S * rows, rows if S > 1 else 0, d0, row0 + c0, lrt)
-                y = res.draws if direct else ybuf
-                final_linear(S * rows, _p(y))
-                if one_call:
-                    a.y = _p(y)
-                    L.check(moments(ctx, C.byref(a)))
-                else:
-                    for s in range(S):
-                        a.y, a.draw = off(y, s * rows * Wd), s
-                        L.check(moments(ctx, C.byref(a)))
-                if keep_draws and not direct:
-                    res.draws[:, c0:c0 + rows].copy_(ybuf[:S * rows].view(S, rows, Wd))
-                continue
-            for s in range(S):                 # one draw per forward, the running moments in `state` between the launches
-                if wts is not None:
-                    self._predict_wn_sample(wts, d0 + s)
-                self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
-                yp = off(res.draws, (s * R + c0) * Wd) if direct else _p(ybuf)
-                final_linear(rows, yp)
-                a.y, a.draw = yp, s
-                L.check(moments(ctx, C.byref(a)))
+
+        self._moments_loop(p, Wd, res.draws, keep_draws, one_call, a, lambda: L.check(moments(ctx, C.byref(a))), point)
         self._consume_draws(S, map)
         if has_t:
             tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
@@ -357,6 +324,122 @@ class _Predictive:
             res.mean_var = tot[3] / (R * D)
         res.S, res.stacked, res.chunks = S, stacked, n_chunks
         return res
+
+    # ---- the class-probability predictive for any class count (vbnn_predict_class_moments): predict()'s contract, buffers and
+    # result, by predict_regression's route -- the final Linear as _generic_head runs it (f32 logits), then the moments of the
+    # family over the S draws' log-softmaxes -- with the top-K classes. Nothing of the training step is written.
+    @_ordered
+    def predict_classes(self, inputs, S=None, targets=None, map=False, row0=None, topk=0, keep_probs=True, keep_draws=False):
+        """predict() for any n_classes >= 2: p(y | x, D) ~ 1/S sum_s softmax(f_s(x)) over draws self.draw + 1 .. self.draw + S,
+        which `self.draw` advances by; S, targets, map and row0 as predict(). topk = K (0 .. 8, at most n_classes): the K most
+        probable classes per row and their probabilities, with targets the top-K accuracy. keep_probs=False: the R x C
+        matrices are not stored (probs / log_probs None) -- the per-row uncertainties, pred and the top K only. keep_draws: the
+        S x R x C logits are returned too. Returns a PredictResult of this rank's rows (no collective, as test())."""
+        lib, ctx = L.lib(), self.ctx.h
+        Cn, K = self.n_classes, int(topk)
+        if self.criterion != "nll":
+            raise ValueError(f"predict_classes: a class-probability predictive needs the NLL criterion (criterion = "
+                             f"'{self.criterion}' has none: use predict_regression)")
+        if not 0 <= K <= min(L.CLASS_MOMENTS_MAX_K, Cn):
+            raise ValueError(f"predict_classes: topk = {K} (0 .. {L.CLASS_MOMENTS_MAX_K}, and at most n_classes = {Cn})")
+        if targets is not None:                # (before the plan, as predict)
+            assert targets.dtype == torch.int32 and targets.is_cuda and targets.numel() == inputs.shape[0]
+            targets = targets.contiguous()
+        p = self._predictive_plan("predict_classes", inputs, S, map, row0)
+        R, S, map, stacked, Rc, n_chunks = p.R, p.S, p.map, p.stacked, p.Rc, p.n_chunks
+        f32 = dict(dtype=torch.float32, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        has_t = targets is not None
+        res = PredictResult(torch.empty(R, Cn, **f32) if keep_probs else None, torch.empty(R, Cn, **f32) if keep_probs else None,
+                            torch.empty(R, **f32), torch.empty(R, **f32), torch.empty(R, **f32), torch.empty(R, **i32))
+        if K:
+            res.topk_idx, res.topk_prob = torch.empty(R, K, **i32), torch.empty(R, K, **f32)
+        if keep_draws:
+            res.draws = torch.empty(S, R, Cn, **f32)
+        one_call = stacked and Cn <= L.CLASS_MOMENTS_STACKED_MAX_C       # else: ACCUMULATE per draw
+        ld_state = (Cn + 3 + 3) // 4 * 4                                 # a multiple of 4: every row of the state on the 16-byte path
+        state = None if one_call else torch.empty(Rc, ld_state, **f32)
+        totals = torch.zeros(n_chunks, 5, dtype=torch.float64, device=self.device) if has_t else None
+        a = L.ClassMomentsArgs(ld_y=Cn, C=Cn, S=S, form=L.MOMENTS_STACKED if one_call else L.MOMENTS_ACCUMULATE, K=K,
+                               state=_p(state), ld_state=ld_state, ld_out=Cn)
+
+        def off(t, row):
+            return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
+
+        def point(c0, rows):                   # the chunk's targets and outputs
+            a.R = rows
+            a.target = off(targets, c0)
+            a.totals = C.c_void_p(totals[c0 // Rc].data_ptr()) if has_t else None
+            a.probs, a.log_probs = off(res.probs, c0 * Cn), off(res.log_probs, c0 * Cn)
+            a.entropy, a.expected_entropy, a.mutual_info = off(res.entropy, c0), off(res.expected_entropy, c0), off(res.mutual_info, c0)
+            a.pred, a.topk_idx, a.topk_prob = off(res.pred, c0), off(res.topk_idx, c0 * K), off(res.topk_prob, c0 * K)
+
+        self._moments_loop(p, Cn, res.draws, keep_draws, one_call, a,
+                           lambda: L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a))), point)
+        self._consume_draws(S, map)
+        if has_t:
+            tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
+            res.totals = tot
+            res.nll, res.accuracy = tot[0] / R, 100.0 * tot[1] / R
+            res.mean_draw_nll, res.mean_draw_accuracy = tot[2] / (R * S), 100.0 * tot[3] / (R * S)
+            res.topk_accuracy = 100.0 * tot[4] / R if K else None
+        res.S, res.stacked, res.chunks = S, stacked, n_chunks
+        return res
+
+    def _moments_loop(self, p, Wd, draws, keep_draws, one_call, a, call, point):
+        """The chunk loop predict_regression and predict_classes share: per chunk the forward (every draw stacked, or one draw
+        at a time), the final Linear's f32 outputs (Wd wide) into the y buffer kept with the predict buffers -- or straight
+        into `draws` (S x R x Wd) where keep_draws allows -- and the moments of the family over them: `call()` launches the
+        entry point on `a` (its y / draw set here) after `point(c0, rows)` has aimed it at the chunk; one STACKED call
+        (one_call), or a call per draw on the running state."""
+        lib, ctx, code = L.lib(), self.ctx.h, self.code
+        x, R, S, map, row0, lrt = p.x, p.R, p.S, p.map, p.row0, p.lrt
+        stacked, Rc, n_chunks, op_rows, bufs, wts, d0 = p.stacked, p.Rc, p.n_chunks, p.op_rows, p.bufs, p.wts, p.d0
+        nl, H = len(self.vb), self.sizes[-1]
+        direct = keep_draws and (not stacked or n_chunks == 1)      # the final Linear writes into draws itself
+        ybuf = None
+        if not direct:                                               # the y buffer: kept with the predict buffers
+            ybuf = bufs.y_reg
+            if ybuf is None or tuple(ybuf.shape) != (op_rows, Wd):
+                ybuf = bufs.y_reg = torch.empty(op_rows, Wd, dtype=torch.float32, device=self.device)
+
+        def off(t, row):
+            return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
+
+        def final_linear(N, y_ptr):
+            fa = L.FwdArgs(w=self.w3_s.ptr, w2=None, x=bufs[nl].x.ptr, x2=None, ld_w=self.w3_s.ld, ld_x=bufs[nl].x.ld,
+                           N=N, I=H, O=Wd, bias=_p(self.bias3), y=y_ptr, ld_y=Wd)
+            L.check(lib.vbnn_forward(ctx, code, C.byref(fa)))
+
+        for k in range(n_chunks):
+            c0 = k * Rc
+            rows = min(Rc, R - c0)
+            xc = x[c0:c0 + rows]
+            point(c0, rows)
+            if stacked:                        # every draw in one forward: draw s = rows [s rows, (s+1) rows) of y
+                if wts is not None:
+                    self._predict_wn_sample(wts, None if map else d0)
+                self._predict_forward(bufs, wts, xc, S * rows, rows if S > 1 else 0, d0, row0 + c0, lrt)
+                y = draws if direct else ybuf
+                final_linear(S * rows, _p(y))
+                if one_call:
+                    a.y = _p(y)
+                    call()
+                else:
+                    for s in range(S):
+                        a.y, a.draw = off(y, s * rows * Wd), s
+                        call()
+                if keep_draws and not direct:
+                    draws[:, c0:c0 + rows].copy_(ybuf[:S * rows].view(S, rows, Wd))
+                continue
+            for s in range(S):                 # one draw per forward, the running moments in `state` between the launches
+                if wts is not None:
+                    self._predict_wn_sample(wts, d0 + s)
+                self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
+                yp = off(draws, (s * R + c0) * Wd) if direct else _p(ybuf)
+                final_linear(rows, yp)
+                a.y, a.draw = yp, s
+                call()
 
     # ---- predict's forward under a compressed pruned view (csrc/sparse.hip; pruning.py: _compress): K-major activations from layer to
     # layer (xT from the input packer, hT from every layer but the last, which writes the row-major h the head reads), squares in registers.

@@ -136,7 +136,10 @@ class Main:
                 if "dev_noise_var" in pred:
                     pred["dev_noise_var"] += r.mean_noise_var
             elif opt.get("predictive"):    # the S-draw model average on the same minibatch (its own draws, after test()'s)
-                r = net.predict(x, targets=t)
+                if getattr(net, "n_classes", 0) > 16:      # predict's head holds a row's classes in one 16-wide tile
+                    r = net.predict_classes(x, targets=t, keep_probs=False)
+                else:
+                    r = net.predict(x, targets=t)
                 pred["devacc_pred"] += r.accuracy
                 pred["devnll_pred"] += r.nll
                 pred["dev_mi"] += float(r.mutual_info.double().mean())
