@@ -838,6 +838,56 @@ typedef struct vbnn_class_moments_args {
 } vbnn_class_moments_args;
 int vbnn_predict_class_moments(vbnn_ctx* ctx, const vbnn_class_moments_args* a);
 
+/* Regression predictive quantiles (additive, ABI 6): the fourth member of the moments family. Per element (r, d) the
+ * predictive is the equal-weight mixture of S components, one per draw of the final Linear's f32 outputs; this call gives its
+ * quantiles at Q probabilities and, with targets, the probability integral transform (PIT) F(t) and the calibration counts
+ * #{t <= q_j}. Draw s of row r starts at y + s draw_stride + r ld_y (draw_stride >= R ld_y): a stacked chunk buffer
+ * (draw_stride = R ld_y) and a row range of an S x R_total x W draws tensor (draw_stride = R_total W) are both read in place.
+ * Draws and targets are finite or NaN. One launch, any D >= 1 and R >= 1 (R < 2^31, every row or plane pitch times its count below 2^60), 1 <= S <= VBNN_QUANTILES_MAX_S, 1 <= Q <=
+ * VBNN_QUANTILES_MAX_Q; p strictly ascending, each in [0.001, 0.999]. The file is compiled without floating-point contraction.
+ * VBNN_QUANT_EMPIRICAL (a row is D wide; the draws are the distribution): fp32, operation by operation. With a_0 <= .. <=
+ * a_{S-1} the element's draws in ascending order (the sign of a zero among equal zeros is unspecified):
+ *   pos = p * float(S - 1);  k = min(int(pos), S - 2);  frac = pos - float(k);  q = min(a_k + frac * (a_{k+1} - a_k), a_{k+1})
+ *   (S = 1: q = a_0) -- numpy's method "linear"; the final min is part of the contract: where the rounding of the product and
+ *   the sum would lift q above a_{k+1} it returns a_{k+1}, which keeps q_j ascending;
+ *   pit = float(#{s : y_s <= t}) / float(S) (correctly rounded).
+ * VBNN_QUANT_FIXED_NOISE (a row is D wide; component s is N(y_s, noise_var), noise_var > 0) and VBNN_QUANT_GAUSS (a row is
+ * 2 D wide, m at column 0 and s at column D; component s is N(m_s, exp(s_c)), s_c = min(max(s, s_min), s_max), the rule of
+ * vbnn_predict_gauss_moments): q is the root of F(q) = 1/S sum_s Phi((q - mu_s) / sigma_s) = p. These two kinds are defined by
+ * accuracy, not by operation order: the kernel evaluates F in fp32 (a running sum over s of erfcf terms) and returns the
+ * upper of two ADJACENT floats lo < q with F32(lo) < p <= F32(q), found by a safeguarded Newton iteration inside a bracket
+ * followed by bisection on the floats' ordered bit patterns -- at most 24 + 33 evaluations of F per quantile, a bound that
+ * does not depend on the data, and an element's result depends on its own draws alone. So, with eps_F the error allowed to
+ * the fp32 evaluation of F:  F(q - 2 ulp) - eps_F <= p <= F(q + 2 ulp) + eps_F  for the exact F -- the exact root of an F
+ * perturbed by at most eps_F lies within 2 fp32 ulps of q -- and pit = F(t) within eps_F. (tests/test_quantiles_ref.py
+ * measures eps_F; it grows like sqrt(S) 2^-25.) Components are expected to keep sigma_s >= 32 ulp(|mu_s|).
+ * Every kind: q_0 <= q_1 <= .. per element. A NaN in any draw of an element (for GAUSS: in m or in s) makes that element's q
+ * and pit NaN and no other element's; a NaN target gives a NaN pit; neither counts anywhere. Pad columns and the gaps between
+ * draws are never read; for GAUSS the m and s halves never read each other's columns. The draws take 16-byte loads where D,
+ * ld_y, draw_stride are multiples of 4 and the half's base address is 16-byte aligned, 4-byte loads otherwise (chosen per
+ * launch); outputs and targets go element by element, consecutive threads to consecutive columns. */
+enum { VBNN_QUANT_EMPIRICAL = 0, VBNN_QUANT_FIXED_NOISE = 1, VBNN_QUANT_GAUSS = 2 };
+#define VBNN_QUANTILES_MAX_S 128   /* most draws */
+#define VBNN_QUANTILES_MAX_Q 8     /* most probabilities */
+typedef struct vbnn_quantiles_args {
+    const float* y; int64_t ld_y;       /* f32 outputs of the final Linear, all S draws; ld_y >= D (GAUSS: >= 2 D) */
+    int64_t draw_stride;                /* floats between draw s and draw s + 1 of the same row (>= R ld_y) */
+    const float* target; int64_t ld_t;  /* R x D regression targets, or NULL */
+    int64_t R, D, S;                    /* rows, outputs per row, draws */
+    int32_t kind;                       /* VBNN_QUANT_* */
+    int32_t Q;                          /* probabilities in p */
+    float p[8];                         /* VBNN_QUANTILES_MAX_Q entries; the first Q are read */
+    float noise_var;                    /* FIXED_NOISE: tau^2 > 0 */
+    float s_min, s_max;                 /* GAUSS: the clamp of s (s_min <= s_max) */
+    /* outputs, each optional (NULL to skip) */
+    float* q; int64_t ld_q; int64_t plane_stride;   /* Q planes of R x D: q_j of (r, d) at q + j plane_stride + r ld_q + d */
+    float* pit; int64_t ld_pit;         /* R x D (needs target) */
+    int32_t* row_le;                    /* R x Q, WRITTEN: entry (r, j) = #{d : t <= q_j} (needs target) */
+    uint64_t* count_le;                 /* Q: the call ADDS #{(r, d) : t <= q_j} with integer atomics -- the caller zeroes it; the
+                                         * result does not depend on the order, and a chunked call needs no host sum (needs target) */
+} vbnn_quantiles_args;
+int vbnn_predict_quantiles(vbnn_ctx* ctx, const vbnn_quantiles_args* a);
+
 /* ---- signal-to-noise pruning (additive, ABI 6): mainviz.lua:20-27 on the device, and the pruned operand shadows that let
  * vbnn_forward / vbnn_head_predict evaluate the pruned network ---------------------------------------------------------------
  * The key of a weight is snr = |means / sqrt(exp(lvars))| in fp32, operation for operation as mainviz.lua:20 forms

@@ -307,6 +307,23 @@ typedef struct vbnn_class_moments_args {
     double* totals;
 } vbnn_class_moments_args;
 int vbnn_predict_class_moments(vbnn_ctx* ctx, const vbnn_class_moments_args* a);
+enum { VBNN_QUANT_EMPIRICAL = 0, VBNN_QUANT_FIXED_NOISE = 1, VBNN_QUANT_GAUSS = 2 };
+typedef struct vbnn_quantiles_args {
+    const float* y; int64_t ld_y;
+    int64_t draw_stride;
+    const float* target; int64_t ld_t;
+    int64_t R, D, S;
+    int32_t kind;
+    int32_t Q;
+    float p[8];
+    float noise_var;
+    float s_min, s_max;
+    float* q; int64_t ld_q; int64_t plane_stride;
+    float* pit; int64_t ld_pit;
+    int32_t* row_le;
+    uint64_t* count_le;
+} vbnn_quantiles_args;
+int vbnn_predict_quantiles(vbnn_ctx* ctx, const vbnn_quantiles_args* a);
 typedef struct vbnn_prune_desc {
     const float* means; const float* lvars; int64_t O, I;
     void* mu_p; void* var_p; int64_t ld_w;

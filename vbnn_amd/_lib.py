@@ -129,6 +129,18 @@ CLASS_MOMENTS_STACKED_MAX_C = 4096    # VBNN_CLASS_MOMENTS_STACKED_MAX_C
 CLASS_MOMENTS_MAX_K = 8               # VBNN_CLASS_MOMENTS_MAX_K
 
 
+class QuantilesArgs(C.Structure):     # vbnn_quantiles_args
+    _fields_ = [("y", _vp), ("ld_y", _i64), ("draw_stride", _i64), ("target", _vp), ("ld_t", _i64), ("R", _i64), ("D", _i64),
+                ("S", _i64), ("kind", C.c_int32), ("Q", C.c_int32), ("p", _f * 8), ("noise_var", _f), ("s_min", _f), ("s_max", _f),
+                ("q", _vp), ("ld_q", _i64), ("plane_stride", _i64), ("pit", _vp), ("ld_pit", _i64), ("row_le", _vp),
+                ("count_le", _vp)]
+
+
+QUANT_EMPIRICAL, QUANT_FIXED_NOISE, QUANT_GAUSS = 0, 1, 2
+QUANTILES_MAX_S = 128                 # VBNN_QUANTILES_MAX_S
+QUANTILES_MAX_Q = 8                   # VBNN_QUANTILES_MAX_Q
+
+
 class PruneDesc(C.Structure):         # vbnn_prune_desc
     _fields_ = [("means", _vp), ("lvars", _vp), ("O", _i64), ("I", _i64), ("mu_p", _vp), ("var_p", _vp), ("ld_w", _i64),
                 ("stats", _vp), ("mask", _vp)]
@@ -246,6 +258,7 @@ _SIGS = {
     "vbnn_gauss_nll_backward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _f, _f, _vp, _i64], _i),
     "vbnn_predict_gauss_moments": ([_vp, C.POINTER(GaussMomentsArgs)], _i),
     "vbnn_predict_class_moments": ([_vp, C.POINTER(ClassMomentsArgs)], _i),
+    "vbnn_predict_quantiles": ([_vp, C.POINTER(QuantilesArgs)], _i),
     "vbnn_snr": ([_vp, _vp, _vp, _i64, _vp], _i),
     "vbnn_prune_workspace_bytes": ([_i, _vp, C.POINTER(C.c_size_t)], _i),
     "vbnn_prune_select": ([_vp, _i, _vp, _i64, _vp, _vp, C.c_size_t], _i),

@@ -20,7 +20,7 @@ import torch
 from . import _lib as L
 from . import partition
 from .nn import Context, _DT, _Packed, _VB, _ordered, _p, fill_normal
-from .predictive import PredictResult, RegressionPredictResult, _Predictive       # noqa: F401  (the result classes: re-exported)
+from .predictive import PredictResult, QuantilePredictResult, RegressionPredictResult, _Predictive       # noqa: F401  (the result classes: re-exported)
 from .pruning import PruneResult, SparsePruneResult, UnitPruneResult, _Pruning      # noqa: F401
 
 

@@ -1,5 +1,5 @@
-"""The posterior predictives of the fused engine (FusedMLP.predict / predict_classes / predict_regression): forward-only passes on buffers of
-their own, dense or under a pruned view (pruning.py). A mixin of vbnn_amd/engine.py:FusedMLP."""
+"""The posterior predictives of the fused engine (FusedMLP.predict / predict_classes / predict_regression / predict_quantiles):
+forward-only passes on buffers of their own, dense or under a pruned view (pruning.py). A mixin of vbnn_amd/engine.py:FusedMLP."""
 import ctypes as C
 import math
 import types
@@ -57,8 +57,39 @@ class RegressionPredictResult:
         self.S, self.stacked, self.chunks = None, None, None
 
 
+class QuantilePredictResult:
+    """FusedMLP.predict_quantiles' outputs for R minibatch rows of D outputs. probs: the Q probabilities (Python floats, as fp32
+    holds them); quantiles (Q x R x D device tensor: per output the p_j-quantile of the S-component predictive mixture, ascending
+    in j); moments: the RegressionPredictResult of the same draws, bit for bit predict_regression's; kind: "empirical" (mse
+    without noise_var: the draws are the distribution -- epistemic-only intervals), "fixed_noise" (mse with noise_var) or
+    "gauss"; draws (S x R x W) with keep_draws. With targets: pit (R x D: the mixture's CDF at the target -- uniform on [0, 1] for
+    a calibrated predictive), row_le (R x Q int32: per row the number of outputs with t <= q_j), count_le (Q integers, their
+    totals) and calibration (Q Python floats, count_le / (R D): calibrated means calibration[j] ~ probs[j]). None without."""
+
+    def __init__(self, probs, quantiles, moments, kind):
+        self.probs, self.quantiles, self.moments, self.kind = probs, quantiles, moments, kind
+        self.pit = self.row_le = self.count_le = self.calibration = self.draws = None
+        self.S = moments.S
+
+    def _index(self, p):
+        p32 = float(torch.tensor(p, dtype=torch.float32))
+        for j, pj in enumerate(self.probs):
+            if pj == p32:
+                return j
+        raise ValueError(f"interval: the probability {p:g} is not among probs = {self.probs}")
+
+    def interval(self, level):
+        """The central interval of mass `level`: (lo, hi, coverage, mean_width) -- the (1 - level) / 2 and (1 + level) / 2
+        quantiles (R x D device tensors; both probabilities must be among probs), and with targets the fraction of targets in
+        (lo, hi] (calibration_hi - calibration_lo; calibrated means ~ level), else None; mean_width: the mean of hi - lo."""
+        lo, hi = self._index((1.0 - level) / 2), self._index((1.0 + level) / 2)
+        cov = self.calibration[hi] - self.calibration[lo] if self.calibration is not None else None
+        ql, qh = self.quantiles[lo], self.quantiles[hi]
+        return ql, qh, cov, float((qh - ql).double().mean())
+
+
 class _Predictive:
-    def _predictive_plan(self, what, inputs, S, map, row0):
+    def _predictive_plan(self, what, inputs, S, map, row0, max_S=None):
         """What predict and predict_regression (`what`, for the messages) share ahead of their chunk loops: resolves S / map,
         checks the inputs, prepares a fresh engine, checks the pruned view and decides the pass -- x (R rows), S, map, row0, lrt,
         stacked, Rc minibatch rows per chunk (n_chunks of them, op_rows operand rows each), the buffers, WN's weights, d0."""
@@ -66,6 +97,8 @@ class _Predictive:
         S = 1 if map else int(self.opt["testSamples"] if S is None else S)
         if S < 1:
             raise ValueError(f"{what}: S = {S} draws (at least one)")
+        if max_S is not None and S > max_S:
+            raise ValueError(f"{what}: S = {S} draws (at most {max_S})")
         x = inputs.reshape(inputs.shape[0], -1)
         R = x.shape[0]
         assert x.shape[1] == self.sizes[0] and x.dtype == torch.float32 and x.is_cuda and R > 0
@@ -256,27 +289,31 @@ class _Predictive:
         RegressionPredictResult of this rank's rows (no collective, as test()).
         criterion = "gauss": D = n_classes / 2, the network supplies the noise (noise_var must be None), the result carries the
         aleatoric noise_var beside the epistemic var, and keep_draws returns the S x R x 2 D outputs (means, log variances)."""
+        return self._regression_predict("predict_regression", inputs, S, targets, noise_var, map, row0, keep_draws)
+
+    def _regression_predict(self, what, inputs, S, targets, noise_var, map, row0, keep_draws, max_S=None):
+        """predict_regression's body, which predict_quantiles (`what`, for the messages) runs too."""
         lib, ctx = L.lib(), self.ctx.h
         if self.criterion not in ("mse", "gauss"):
-            raise ValueError("predict_regression: the regression predictive needs the MSE criterion or the Gaussian one "
+            raise ValueError(f"{what}: the regression predictive needs the MSE criterion or the Gaussian one "
                              "(criterion = 'nll': use predict)")
         gauss = self.criterion == "gauss"
         Wd = self.n_classes                                          # the final Linear's width: D, or { m[D], s[D] }
         D = Wd // 2 if gauss else Wd
         if gauss and noise_var is not None:
-            raise ValueError("predict_regression: criterion = 'gauss' predicts its own noise variance (noise_var must be None)")
+            raise ValueError(f"{what}: criterion = 'gauss' predicts its own noise variance (noise_var must be None)")
         if noise_var is not None:
             noise_var = float(noise_var)
             if not (noise_var > 0.0 and math.isfinite(noise_var)):
-                raise ValueError(f"predict_regression: noise_var = {noise_var} (a finite variance above zero, or None)")
+                raise ValueError(f"{what}: noise_var = {noise_var} (a finite variance above zero, or None)")
         if targets is not None:                # (before the plan, as predict)
             R = inputs.shape[0]
             if gauss and tuple(targets.shape) != (R, D):
-                raise ValueError(f"predict_regression: targets of shape {tuple(targets.shape)} (criterion = 'gauss' takes R x D = "
+                raise ValueError(f"{what}: targets of shape {tuple(targets.shape)} (criterion = 'gauss' takes R x D = "
                                  f"{R} x {D}: one target per mean)")
             assert targets.dtype == torch.float32 and targets.is_cuda and tuple(targets.shape) == (R, D)
             targets = targets.contiguous()
-        p = self._predictive_plan("predict_regression", inputs, S, map, row0)
+        p = self._predictive_plan(what, inputs, S, map, row0, max_S)
         R, S, map, stacked, Rc, n_chunks = p.R, p.S, p.map, p.stacked, p.Rc, p.n_chunks
         f32 = dict(dtype=torch.float32, device=self.device)
         has_t = targets is not None
@@ -323,6 +360,57 @@ class _Predictive:
             res.log_lik = tot[2] / R if (gauss or noise_var is not None) else None
             res.mean_var = tot[3] / (R * D)
         res.S, res.stacked, res.chunks = S, stacked, n_chunks
+        return res
+
+    # ---- the regression predictive's quantiles (vbnn_predict_quantiles): predict_regression's pass with the draws kept, then ONE
+    # launch over all rows of them -- per output the quantiles of the S-component mixture, and with targets the probability
+    # integral transform and the calibration counts.
+    @_ordered
+    def predict_quantiles(self, inputs, probs, S=None, targets=None, noise_var=None, map=False, row0=None, keep_draws=False):
+        """The quantiles of p(y | x, D) ~ 1/S sum_s N(f_s(x), noise) per output at the probabilities `probs` (1 .. 8 of them,
+        strictly ascending, each in [0.001, 0.999]) over draws self.draw + 1 .. self.draw + S (S <= 128), which `self.draw`
+        advances by. Everything else is predict_regression's contract -- criteria "mse" and "gauss" only, S / targets / noise_var /
+        map / row0 as there, chunking by opt.predict_rows, pruned views -- and its pass: `.moments` of the result is bit for bit
+        what predict_regression gives from the same counter. The mixture follows the engine: "gauss" -> N(m_s, exp(s_s)); "mse"
+        with noise_var -> N(f_s, noise_var); "mse" without -> the draws themselves (epistemic-only intervals). With targets the
+        result carries pit, row_le, calibration and interval(level)'s coverage. keep_draws: the draws are returned too.
+        Memory: the S x R x W fp32 draws (S R W 4 bytes, W the final Linear's width) are always held for the one quantile launch,
+        returned or not; opt.predict_rows bounds the forward's buffers, NOT this. Returns a QuantilePredictResult."""
+        lib, ctx = L.lib(), self.ctx.h
+        probs = [float(v) for v in probs]
+        Q = len(probs)
+        p32 = torch.tensor(probs, dtype=torch.float32).tolist()          # as fp32 holds them: what the kernel compares
+        if not 1 <= Q <= L.QUANTILES_MAX_Q:
+            raise ValueError(f"predict_quantiles: {Q} probabilities (1 .. {L.QUANTILES_MAX_Q})")
+        if not all(0.001 <= v <= 0.999 for v in probs) or any(b <= a for a, b in zip(p32, p32[1:])):
+            raise ValueError(f"predict_quantiles: probs = {probs} (strictly ascending, each in [0.001, 0.999])")
+        mom = self._regression_predict("predict_quantiles", inputs, S, targets, noise_var, map, row0, True, max_S=L.QUANTILES_MAX_S)
+        draws = mom.draws
+        if not keep_draws:
+            mom.draws = None
+        Sn, R, Wd = draws.shape
+        gauss = self.criterion == "gauss"
+        D = Wd // 2 if gauss else Wd
+        kind = "gauss" if gauss else ("fixed_noise" if noise_var is not None else "empirical")
+        res = QuantilePredictResult(p32, torch.empty(Q, R, D, dtype=torch.float32, device=self.device), mom, kind)
+        res.draws = draws if keep_draws else None
+        a = L.QuantilesArgs(y=_p(draws), ld_y=Wd, draw_stride=R * Wd, R=R, D=D, S=Sn, Q=Q,
+                            kind={"gauss": L.QUANT_GAUSS, "fixed_noise": L.QUANT_FIXED_NOISE, "empirical": L.QUANT_EMPIRICAL}[kind],
+                            noise_var=float(noise_var or 0.0), s_min=self.logvar_clamp[0] if gauss else 0.0,
+                            s_max=self.logvar_clamp[1] if gauss else 0.0, q=_p(res.quantiles), ld_q=D, plane_stride=R * D)
+        for j, v in enumerate(p32):
+            a.p[j] = v
+        count = None
+        if targets is not None:
+            targets = targets.contiguous()     # (the helper's own copy is local to it; a no-op on a contiguous tensor)
+            res.pit = torch.empty(R, D, dtype=torch.float32, device=self.device)
+            res.row_le = torch.empty(R, Q, dtype=torch.int32, device=self.device)
+            count = torch.zeros(Q, dtype=torch.int64, device=self.device)
+            a.target, a.ld_t, a.pit, a.ld_pit, a.row_le, a.count_le = _p(targets), D, _p(res.pit), D, _p(res.row_le), _p(count)
+        L.check(lib.vbnn_predict_quantiles(ctx, C.byref(a)))
+        if count is not None:
+            res.count_le = count.cpu().tolist()                          # (synchronises)
+            res.calibration = [c / (R * D) for c in res.count_le]
         return res
 
     # ---- the class-probability predictive for any class count (vbnn_predict_class_moments): predict()'s contract, buffers and

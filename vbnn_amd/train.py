@@ -122,6 +122,11 @@ class Main:
                 pred.update(devll_pred=0.0, dev_noise_var=0.0)
             elif tau2 is not None:
                 pred["devll_pred"] = 0.0
+        # opt.quantile_probs (off by default): `dev_cal@<p>`, the fraction of the test targets at or below the predictive's
+        # p-quantile (calibrated: p) -- FusedMLP.predict_quantiles, whose moments are predict_regression's of the same draws
+        qprobs = [float(v) for v in (opt.get("quantile_probs") or [])] if (regression and opt.get("predictive")) else []
+        for pj in qprobs:
+            pred[f"dev_cal@{pj:g}"] = 0.0
         for t0 in starts:
             inputs, targets = dataset.create_minibatch(t0, bs, n, opt.get("geometry"))
             x, t = self._to_device(inputs, targets)
@@ -129,7 +134,13 @@ class Main:
             accuracy += acc
             error += err
             if opt.get("predictive") and regression:
-                r = net.predict_regression(x, targets=t, noise_var=tau2)
+                if qprobs:                                 # opt.quantile_probs: the same draws give the calibration too
+                    qr = net.predict_quantiles(x, qprobs, targets=t, noise_var=tau2)
+                    r = qr.moments
+                    for pj, cj in zip(qprobs, qr.calibration):
+                        pred[f"dev_cal@{pj:g}"] += cj
+                else:
+                    r = net.predict_regression(x, targets=t, noise_var=tau2)
                 pred["dev_epi_var"] += r.mean_var
                 if "devll_pred" in pred:
                     pred["devll_pred"] += r.log_lik
@@ -211,7 +222,7 @@ class Main:
                     if k in rec:
                         self.log.add(k, rec[k])
                 for k in rec:
-                    if k in ("pruned count", "pruned var mean", "held fraction") or k.startswith("devacc_pruned@"):
+                    if k in ("pruned count", "pruned var mean", "held fraction") or k.startswith(("devacc_pruned@", "dev_cal@")):
                         self.log.add(k, rec[k])
                 self.log.flush()
                 self.save()                                                                # main.lua:181
