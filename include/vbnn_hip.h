@@ -1020,6 +1020,23 @@ typedef struct vbnn_unit_gather_args {
 } vbnn_unit_gather_args;
 int vbnn_unit_gather(vbnn_ctx* ctx, const vbnn_unit_gather_args* a);
 
+/* ---- a device digest of a buffer (additive, ABI 6): what a checkpoint records per tensor before the download and checks again
+ * after the upload, and what the replicas of a data-parallel run compare in 8 bytes per tensor -------------------------------
+ * Over the buffer's 32-bit words w_0 .. w_{n_words - 1} (little-endian, as they lie in memory; the bits of a float, NaN
+ * payloads and the sign of a zero included):
+ *   out[0] += sum_i mix(((index0 + i + 1) << 32) | w_i)   mod 2^64
+ * with mix the splitmix64 finaliser on a uint64 z, every operation mod 2^64:
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31)
+ * Position-dependent (two unequal words swapped change it) and order-independent (a sum of integers): any grid and any order of
+ * the atomics give the same bits, and the digests of the pieces of a buffer, each taken with index0 = the piece's first word,
+ * add up to the digest of the whole. The call ADDS into out (a device word, 8-byte aligned): the caller zeroes it, and several
+ * calls may accumulate into one word. It detects damage; it is NOT cryptographic -- anyone can construct a collision.
+ * VBNN_ERR_INVALID, with out untouched: index0 + n_words > 2^32 - 1, buf not 4-byte aligned, out NULL. n_words = 0 is legal and
+ * adds nothing (buf is then not read and may be NULL). One read-only streaming launch: 16-byte loads on the 16-byte aligned
+ * body, 4-byte loads for a head and a tail of up to three words each, one 64-bit integer atomic per workgroup; no floating-point
+ * arithmetic. 4 B read per word, nothing written. */
+int vbnn_digest(vbnn_ctx* ctx, const void* buf, uint64_t n_words, uint64_t index0, uint64_t* out);
+
 /* The same criterion as separate modules, for the module-level call order of mlp.lua:77-80:
  * nn.LogSoftMax:updateOutput is vbnn_logsoftmax_nll with g_logits = loss = correct = NULL. */
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,

@@ -377,6 +377,7 @@ typedef struct vbnn_unit_gather_args {
     float* dst_means; float* dst_lvars; float* dst_bias;
 } vbnn_unit_gather_args;
 int vbnn_unit_gather(vbnn_ctx* ctx, const vbnn_unit_gather_args* a);
+int vbnn_digest(vbnn_ctx* ctx, const void* buf, uint64_t n_words, uint64_t index0, uint64_t* out);
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,
                      float inv_n, double* loss_sum_dev, int32_t* correct_dev);
 int vbnn_nll_backward(vbnn_ctx* ctx, const int32_t* target, int64_t N, int64_t C, float inv_n, float* g);

@@ -269,6 +269,7 @@ _SIGS = {
     "vbnn_unit_select": ([_vp, _i, _vp, _i64, _vp], _i),
     "vbnn_unit_index": ([_vp, _i, _vp, _vp, _f, _i64], _i),
     "vbnn_unit_gather": ([_vp, C.POINTER(UnitGatherArgs)], _i),
+    "vbnn_digest": ([_vp, _vp, _u64, _u64, _vp], _i),
     "vbnn_nll_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _f, _vp, _vp], _i),
     "vbnn_nll_backward": ([_vp, _vp, _i64, _i64, _f, _vp], _i),
     "vbnn_logsoftmax_backward": ([_vp, _vp, _vp, _vp, _i64, _i64], _i),

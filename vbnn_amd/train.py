@@ -18,6 +18,10 @@ are ORed, and prune() ranks the frozen weights by the values they were frozen wi
 one; the series `held fraction` logs the true one, and `lc` is then the kept weights' sum. The reference only counts what
 would go (mainviz.lua:20-27).
 
+opt.checkpoint = True (off by default): save() also writes `<network_name>/model` -- the engine's complete state (FusedMLP.save) plus
+trainer = {epoch, indices, rng}; opt.network_to_load = <dir> loads `<dir>/model` into the engine and restores the trainer, and the run
+continues bit for bit as the uninterrupted one would have (checkpoint.py says why).
+
 Differences from main.lua, all deliberate: the loop ends after `epochs` (the reference loops forever, :164); a last
 short minibatch is skipped rather than padded with uninitialised rows (data.lua:9-20); targets are 0-based.
 """
@@ -26,6 +30,7 @@ import os
 import numpy as np
 import torch
 
+from . import checkpoint as ckpt
 from . import utils as u
 from .engine import FusedMLP
 from .logger import Logger
@@ -61,6 +66,23 @@ class Main:
         self.indices = None
         self.epoch = 0                                                                    # epochs run so far (opt.prune_schedule counts them)
         self.log = Logger(opt["network_name"], append=bool(opt.get("network_to_load"))) if opt.get("log") else None
+        if opt.get("network_to_load"):                                                    # main.lua:146-148
+            self._resume(os.path.join(str(opt["network_to_load"]), "model"))
+
+    def _resume(self, path):
+        """opt.network_to_load = <dir>: <dir>/model (a FusedMLP.save file, written by a run with opt.checkpoint) goes into this Main's engine;
+        its `trainer` table, when it has one, restores the epoch counter (opt.prune_schedule continues at the right epoch), the minibatch
+        start indices and the shuffling RandomState. A file without one resumes the engine only."""
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"opt.network_to_load: {path} does not exist (a run saves it with opt.checkpoint = True)")
+        table = ckpt.read_checkpoint(path)
+        self.net.load_state_dict(table["engine"])
+        tr = table.get("trainer")
+        if tr:
+            self.epoch = int(tr["epoch"])
+            idx = np.asarray(tr["indices"]).astype(np.int64).reshape(-1).tolist()
+            self.indices = idx if idx else None
+            ckpt.rng_from_table(tr["rng"], self.rng)
 
     def _to_device(self, inputs, targets):
         x = torch.from_numpy(np.ascontiguousarray(inputs, dtype=np.float32)).to(self.device)
@@ -198,6 +220,13 @@ class Main:
         u.safe_save(means, os.path.join(d, "parameters"), "means")
         u.safe_save(vars_, os.path.join(d, "parameters"), "vars")
         u.safe_save({k: (list(v) if isinstance(v, tuple) else v) for k, v in self.opt.items()}, d, "opt")
+        if self.opt.get("checkpoint"):
+            # main.lua:181's `model`, as data: the engine's whole state and the trainer's, one file (checkpoint.py). The replicas of a
+            # data-parallel run are compared first (a collective: every rank is here); rank 0 alone writes
+            net.check_replicas()
+            if getattr(net, "rank", 0) == 0:
+                net.save(os.path.join(d, "model"), trainer={"epoch": self.epoch, "indices": self.indices,
+                                                            "rng": ckpt.rng_state_table(self.rng)})
 
     def run(self, trainSet, testSet, epochs=1):                                           # main.lua:138-184
         history = []
