@@ -89,12 +89,12 @@ def test_gauss_kernels_use_no_private_memory():
     (4 and 8 quads per thread); VBNN_GAUSS_MOMENTS_STACKED_MAX_D is the wider one's reach."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_regs
-    ks = [k for k in kernel_regs.kernels() if "k_gauss_" in k["name"] or "k_moments_finish" in k["name"]]
+    ks = [k for k in kernel_regs.kernels() if "k_gauss_" in k["name"] or "GaussFamily" in k["name"] or "k_moments_finish" in k["name"]]
     names = " ".join(k["name"] for k in ks)
-    for want in ("k_gauss_nll", "k_gauss_moments_stacked", "k_gauss_moments_accumulate", "k_moments_finishILi5E"):
+    for want in ("k_gauss_nll", "k_moments_stackedI11GaussFamily", "k_moments_accumulateI11GaussFamily", "k_moments_finishILi5E"):
         assert want in names, (want, names)
-    assert len([k for k in ks if "k_gauss_moments_stacked" in k["name"]]) == 3          # a wave per row / a workgroup per row, two tiles
-    assert len([k for k in ks if "k_gauss_moments_accumulate" in k["name"]]) == 2
+    assert len([k for k in ks if "k_moments_stackedI11GaussFamily" in k["name"]]) == 3  # a wave per row / a workgroup per row, two tiles
+    assert len([k for k in ks if "k_moments_accumulateI11GaussFamily" in k["name"]]) == 2
     for k in ks:
         assert int(k["scratch"]) == 0 and int(k["spill"]) == 0, k
         assert int(k["lds"]) <= 8192, k

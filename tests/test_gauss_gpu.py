@@ -262,6 +262,7 @@ MOM_CASES = {
     "37x70x3": (37, 70, 3, {}, False, 1.0),
     "64x257x30": (64, 257, 30, {}, False, 12.0),
     "5xCAPx4": (5, "cap", 4, {}, False, 1.0),
+    "3x4101x2-wide-tile-partial-quad": (3, 4101, 2, {}, False, 1.0),
     "2xCAP+4x3-above-the-cap": (2, "cap+4", 3, {}, False, 4.0),
     "9x8x7-nan-pads": (9, 8, 7, dict(ld_y=24, ld_t=16), False, 4.0),
     "9x8x7-y-off-by-one-float": (9, 8, 7, dict(y_offset=1), False, 1.0),

@@ -94,6 +94,7 @@ CASES = {
     "3x5x2": (3, 5, 2, 0.5, {}, False),
     "37x70x3": (37, 70, 3, 1.0, {}, False),
     "64x257x30": (64, 257, 30, 0.01, {}, False),
+    "3x1029x3-partial-quad-in-the-second-slot": (3, 1029, 3, 0.5, {}, False),
     "5x4096x4": (5, 4096, 4, 0.25, {}, False),
     "2x4100x3-above-the-cap": (2, 4100, 3, 0.25, {}, False),
     "9x8x7-nan-pads": (9, 8, 7, 0.5, dict(ld_y=24, ld_t=16), False),

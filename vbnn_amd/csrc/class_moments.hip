@@ -12,7 +12,6 @@
 #include "moments_common.h"
 #include <math.h>
 #include <limits.h>
-#include <algorithm>
 
 constexpr int CLS_NQ = 4;
 static_assert(VBNN_CLASS_MOMENTS_STACKED_MAX_C == 4 * 256 * CLS_NQ, "the register tile of a row");
@@ -227,17 +226,6 @@ __device__ __forceinline__ void cls_finish(const ClsArgs& a, int64_t r, int t, i
     cls_finish_row<WPR>(a, r, t, tr, f, scan, sh, wave, tot);
 }
 
-template <int NQ, int TR>
-__device__ __forceinline__ void cls_tile(int tr, int64_t C, int (&valid)[NQ], int (&col)[NQ]) {
-    const int nq = (int)((C + 3) >> 2);
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) {
-        const int q = tr + k * TR;
-        col[k] = 4 * q;
-        valid[k] = q < nq ? min(4, (int)C - 4 * q) : 0;
-    }
-}
-
 template <int WPR, int NQ>
 __global__ __launch_bounds__(256) void k_class_stacked(const ClsArgs a) {
     constexpr int TR = 64 * WPR, RPB = 4 / WPR;
@@ -246,7 +234,7 @@ __global__ __launch_bounds__(256) void k_class_stacked(const ClsArgs a) {
     const int tr = WPR == 1 ? lane : (int)threadIdx.x;
     double tot[CLS_NT] = {0.0, 0.0, 0.0, 0.0, 0.0};
     int valid[NQ], col[NQ];
-    cls_tile<NQ, TR>(tr, a.C, valid, col);
+    mom_tile<NQ, TR>(tr, a.C, valid, col);
     for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < a.R; r0 += (int64_t)gridDim.x * RPB) {
         const int64_t r = r0 + (WPR == 1 ? wave : 0);
         if (r >= a.R) continue;                            // WPR == 1 only: a whole wave, and that path has no barrier in the loop
@@ -286,7 +274,7 @@ __global__ __launch_bounds__(256) void k_class_accumulate(const ClsArgs a) {
     const bool first = a.draw == 0, fin = a.draw == a.S - 1;
     double tot[CLS_NT] = {0.0, 0.0, 0.0, 0.0, 0.0};
     int valid[NQ], col[NQ];
-    cls_tile<NQ, TR>(tr, a.C, valid, col);
+    mom_tile<NQ, TR>(tr, a.C, valid, col);
     for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < a.R; r0 += (int64_t)gridDim.x * RPB) {
         const int64_t r = r0 + (WPR == 1 ? wave : 0);
         if (r >= a.R) continue;                            // WPR == 1 only (see k_class_stacked)
@@ -384,26 +372,6 @@ __global__ __launch_bounds__(256) void k_class_accumulate_wide(const ClsArgs a) 
     if (fin) mom_store_partials<4, CLS_NT>(a.part, tot, sh.dred, wave, tr);
 }
 
-// the five totals: the workgroups' partials in workgroup order
-__global__ __launch_bounds__(256) void k_class_moments_finish(const double* __restrict__ part, int nb, double* __restrict__ totals) {
-    __shared__ double sh[CLS_NT][4];
-    double v[CLS_NT];
-#pragma unroll
-    for (int k = 0; k < CLS_NT; ++k) v[k] = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 256)
-#pragma unroll
-        for (int k = 0; k < CLS_NT; ++k) v[k] += part[(int64_t)k * nb + b];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < CLS_NT; ++k) v[k] += __shfl_xor(v[k], off, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < CLS_NT; ++k) sh[k][threadIdx.x >> 6] = v[k];
-    __syncthreads();
-    if (threadIdx.x < CLS_NT) totals[threadIdx.x] = ((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + sh[threadIdx.x][2]) + sh[threadIdx.x][3];
-}
-
 template <int WPR, int NQ>
 static void cls_launch(bool stacked, int nb, hipStream_t stream, const ClsArgs& m) {
     if (stacked) hipLaunchKernelGGL((k_class_stacked<WPR, NQ>), dim3(nb), dim3(256), 0, stream, m);
@@ -429,31 +397,25 @@ extern "C" int vbnn_predict_class_moments(vbnn_ctx* ctx, const vbnn_class_moment
         VBNN_REQUIRE(a->ld_state >= a->C + 3, "ld_state: a row of the state holds C + 3 floats");
         VBNN_REQUIRE(a->draw >= 0 && a->draw < a->S, "draw outside [0, S)");
     }
-    const bool fin = stacked || a->draw == a->S - 1;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
     ClsArgs m;
     m.y = a->y; m.ld_y = a->ld_y; m.t = a->target; m.R = a->R; m.C = a->C; m.S = (int)a->S; m.draw = stacked ? 0 : a->draw;
     m.K = (int)a->K; m.state = stacked ? nullptr : a->state; m.ld_state = stacked ? 0 : a->ld_state;
     m.probs = a->probs; m.log_probs = a->log_probs; m.ld_out = a->ld_out; m.entropy = a->entropy;
     m.expected_entropy = a->expected_entropy; m.mutual_info = a->mutual_info; m.pred = a->pred; m.topk_idx = a->topk_idx;
     m.topk_prob = a->topk_prob;
-    m.y_vec = (a->ld_y & 3) == 0 && al16(a->y);
-    m.o_vec = (a->ld_out & 3) == 0 && al16(a->probs) && al16(a->log_probs);
-    m.s_vec = !stacked && (a->ld_state & 3) == 0 && al16(a->state);
-    const bool wave_rows = a->C <= 256;                    // one wave per row, four rows per workgroup; above: a workgroup per row
-    vbnn_cu_scope scope(ctx);
-    const int64_t groups = wave_rows ? (a->R + 3) / 4 : a->R;
-    const int nb = (int)std::min<int64_t>(groups, (int64_t)vbnn_cu_count() * 8);   // ~8 workgroups per CU, grid-stride above
-    const bool totals = fin && a->totals;
-    VBNN_REQUIRE(!totals || (size_t)nb * CLS_NT <= ctx->scratch_doubles, "reduction scratch");
-    m.part = totals ? ctx->scratch : nullptr;
+    m.y_vec = (a->ld_y & 3) == 0 && mom_al16(a->y);
+    m.o_vec = (a->ld_out & 3) == 0 && mom_al16(a->probs) && mom_al16(a->log_probs);
+    m.s_vec = !stacked && (a->ld_state & 3) == 0 && mom_al16(a->state);
+    const MomPlan<CLS_NT> plan(ctx, a->C, a->R, (stacked || a->draw == a->S - 1) && a->totals);
+    VBNN_REQUIRE(plan.fits, "reduction scratch");
+    m.part = plan.part;
     // the register tile follows C; thread i owns quads i, i + T, ... under every tile, so the bits do not depend on it
-    if (wave_rows) cls_launch<1, 1>(stacked, nb, ctx->stream, m);
-    else if (a->C <= 4 * 256 * 1) cls_launch<4, 1>(stacked, nb, ctx->stream, m);
-    else if (a->C <= 4 * 256 * 2) cls_launch<4, 2>(stacked, nb, ctx->stream, m);
-    else if (a->C <= 4 * 256 * CLS_NQ) cls_launch<4, CLS_NQ>(stacked, nb, ctx->stream, m);
-    else hipLaunchKernelGGL(k_class_accumulate_wide, dim3(nb), dim3(256), 0, ctx->stream, m);
-    if (totals) hipLaunchKernelGGL(k_class_moments_finish, dim3(1), dim3(256), 0, ctx->stream, ctx->scratch, nb, a->totals);
+    if (plan.wave_rows) cls_launch<1, 1>(stacked, plan.nb, ctx->stream, m);
+    else if (a->C <= 4 * 256 * 1) cls_launch<4, 1>(stacked, plan.nb, ctx->stream, m);
+    else if (a->C <= 4 * 256 * 2) cls_launch<4, 2>(stacked, plan.nb, ctx->stream, m);
+    else if (a->C <= 4 * 256 * CLS_NQ) cls_launch<4, CLS_NQ>(stacked, plan.nb, ctx->stream, m);
+    else hipLaunchKernelGGL(k_class_accumulate_wide, dim3(plan.nb), dim3(256), 0, ctx->stream, m);
+    plan.finish(ctx->stream, a->totals);
     return vbnn_check_launch("k_class_moments");
     VBNN_API_END
 }

@@ -1,7 +1,9 @@
 // moments_common.h -- what the kernels of the moments family (moments.hip, class_moments.hip) share: the quad access paths,
-// the row sum whose order depends on the row width alone, and the workgroup partials of the double totals.
+// a thread's tile of a row, the row sum whose order depends on the row width alone, the workgroup partials of the double
+// totals with the kernel that adds them, and the host's launch plan.
 #pragma once
 #include "common.h"
+#include <algorithm>
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -41,6 +43,19 @@ __device__ __forceinline__ void mom_store4(float* p, const float (&v)[4], int va
     }
 }
 
+// a thread's NQ quads of a row of `width` columns, the first of them quad q0: quads q0, q0 + TR, ... (columns col[k] ..
+// col[k] + valid[k] - 1; valid 0 past the row's end). Thread i of the row passes q0 = i, plus the chunk's first quad.
+template <int NQ, int TR, typename I>
+__device__ __forceinline__ void mom_tile(I q0, int64_t width, int (&valid)[NQ], I (&col)[NQ]) {
+    const I nq = (I)((width + 3) >> 2);
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+        const I q = q0 + (I)k * TR;
+        col[k] = 4 * q;
+        valid[k] = q < nq ? (int)min((I)4, (I)width - 4 * q) : 0;
+    }
+}
+
 // sum over the row's threads: lane-strided partials in, the xor butterfly inside a wave, the waves in wave order through LDS.
 // Every thread of the row returns the same bits. WPR == 4: block-uniform call (two barriers).
 template <int WPR, int N>
@@ -59,8 +74,8 @@ __device__ __forceinline__ void mom_row_sum(float (&v)[N], float (*red)[4], int 
     __syncthreads();
 }
 
-// the workgroup's partial of the NT totals (four; the Gaussian head's five): [NT][gridDim.x] doubles, which k_moments_finish
-// adds in workgroup order
+// the workgroup's partial of the NT totals (four; the Gaussian head's and the classes' five): [NT][gridDim.x] doubles, which
+// k_moments_finish adds in workgroup order
 template <int WPR, int NT>
 __device__ __forceinline__ void mom_store_partials(double* part, const double (&tot)[NT], double (*dred)[4], int wave, int tr) {
     if (!part) return;                                     // launch-uniform
@@ -78,3 +93,45 @@ __device__ __forceinline__ void mom_store_partials(double* part, const double (&
         for (int k = 0; k < NT; ++k) part[(int64_t)k * gridDim.x + blockIdx.x] = tot[k];
     }
 }
+
+template <int NT>
+__global__ __launch_bounds__(256) void k_moments_finish(const double* __restrict__ part, int nb, double* __restrict__ totals) {
+    __shared__ double sh[NT][4];
+    double v[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) v[k] = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 256)
+#pragma unroll
+        for (int k = 0; k < NT; ++k) v[k] += part[(int64_t)k * nb + b];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < NT; ++k) v[k] += __shfl_xor(v[k], off, 64);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < NT; ++k) sh[k][threadIdx.x >> 6] = v[k];
+    __syncthreads();
+    if (threadIdx.x < NT) totals[threadIdx.x] = ((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + sh[threadIdx.x][2]) + sh[threadIdx.x][3];
+}
+
+// ---- host side
+static inline bool mom_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// the launch plan of a family's kernels over R rows of `width` columns; `totals`: this launch finishes and the caller wants the
+// NT totals. The caller requires `fits` ("reduction scratch"), launches nb workgroups of 256 with `part`, then calls finish().
+template <int NT>
+struct MomPlan {
+    vbnn_cu_scope scope;
+    bool wave_rows;                                        // one wave per row, four rows per workgroup; else a workgroup per row
+    int nb;                                                // ~8 workgroups per CU, grid-stride above
+    bool fits;
+    double* part;                                          // the workgroups' partials, null without totals
+    MomPlan(const vbnn_ctx* ctx, int64_t width, int64_t R, bool totals) : scope(ctx), wave_rows(width <= 256) {
+        nb = (int)std::min<int64_t>(wave_rows ? (R + 3) / 4 : R, (int64_t)vbnn_cu_count() * 8);
+        fits = !totals || (size_t)nb * NT <= ctx->scratch_doubles;
+        part = totals ? ctx->scratch : nullptr;
+    }
+    void finish(hipStream_t stream, double* totals) const {
+        if (part) hipLaunchKernelGGL(k_moments_finish<NT>, dim3(1), dim3(256), 0, stream, part, nb, totals);
+    }
+};

@@ -11,6 +11,16 @@ from .nn import _Packed, _VB, _ordered, _p
 from .pruning import SparsePruneResult
 
 
+def _off(t, row):
+    """The address of element `row` of t (4-byte elements), None without t."""
+    return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
+
+
+def _chunk_sums(totals):
+    """The chunks' totals (chunks x NT doubles on the device) added in chunk order; synchronises."""
+    return [sum(col) for col in zip(*totals.cpu().tolist())]
+
+
 class _PredictBuffers(list):
     """predict's operands per layer input (+ .r, the sequential bf16 forwards' throwaway noise factor; .y_reg: predict_regression's y)."""
     r = y_reg = None
@@ -189,7 +199,7 @@ class _Predictive:
                 L.check(lib.vbnn_head_predict(ctx, code, C.byref(a)))
         self._consume_draws(S, map)
         if totals is not None:
-            tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
+            tot = _chunk_sums(totals)
             res.totals = tot
             res.nll, res.accuracy = tot[0] / R, 100.0 * tot[1] / R
             res.mean_draw_nll, res.mean_draw_accuracy = tot[2] / (R * S), 100.0 * tot[3] / (R * S)
@@ -335,22 +345,19 @@ class _Predictive:
             a = L.MomentsArgs(ld_y=D, ld_t=D, D=D, S=S, form=form, noise_var=noise_var or 0.0, state=_p(state), ld_out=D)
             moments = lib.vbnn_predict_moments
 
-        def off(t, row):
-            return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
-
         def point(c0, rows):                   # the chunk's targets and outputs
             a.R = rows
-            a.target = off(targets, c0 * D)
+            a.target = _off(targets, c0 * D)
             a.totals = C.c_void_p(totals[c0 // Rc].data_ptr()) if has_t else None
-            a.mean, a.var = off(res.mean, c0 * D), off(res.var, c0 * D)
-            a.row_var, a.row_sq_err, a.row_log_lik = off(res.row_var, c0), off(res.row_sq_err, c0), off(res.row_log_lik, c0)
+            a.mean, a.var = _off(res.mean, c0 * D), _off(res.var, c0 * D)
+            a.row_var, a.row_sq_err, a.row_log_lik = _off(res.row_var, c0), _off(res.row_sq_err, c0), _off(res.row_log_lik, c0)
             if gauss:
-                a.noise_var, a.row_noise_var = off(res.noise_var, c0 * D), off(res.row_noise_var, c0)
+                a.noise_var, a.row_noise_var = _off(res.noise_var, c0 * D), _off(res.row_noise_var, c0)
 
         self._moments_loop(p, Wd, res.draws, keep_draws, one_call, a, lambda: L.check(moments(ctx, C.byref(a))), point)
         self._consume_draws(S, map)
         if has_t:
-            tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
+            tot = _chunk_sums(totals)
             res.totals = tot
             res.mse = tot[0] / (R * D)
             if gauss:
@@ -451,22 +458,19 @@ class _Predictive:
         a = L.ClassMomentsArgs(ld_y=Cn, C=Cn, S=S, form=L.MOMENTS_STACKED if one_call else L.MOMENTS_ACCUMULATE, K=K,
                                state=_p(state), ld_state=ld_state, ld_out=Cn)
 
-        def off(t, row):
-            return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
-
         def point(c0, rows):                   # the chunk's targets and outputs
             a.R = rows
-            a.target = off(targets, c0)
+            a.target = _off(targets, c0)
             a.totals = C.c_void_p(totals[c0 // Rc].data_ptr()) if has_t else None
-            a.probs, a.log_probs = off(res.probs, c0 * Cn), off(res.log_probs, c0 * Cn)
-            a.entropy, a.expected_entropy, a.mutual_info = off(res.entropy, c0), off(res.expected_entropy, c0), off(res.mutual_info, c0)
-            a.pred, a.topk_idx, a.topk_prob = off(res.pred, c0), off(res.topk_idx, c0 * K), off(res.topk_prob, c0 * K)
+            a.probs, a.log_probs = _off(res.probs, c0 * Cn), _off(res.log_probs, c0 * Cn)
+            a.entropy, a.expected_entropy, a.mutual_info = _off(res.entropy, c0), _off(res.expected_entropy, c0), _off(res.mutual_info, c0)
+            a.pred, a.topk_idx, a.topk_prob = _off(res.pred, c0), _off(res.topk_idx, c0 * K), _off(res.topk_prob, c0 * K)
 
         self._moments_loop(p, Cn, res.draws, keep_draws, one_call, a,
                            lambda: L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a))), point)
         self._consume_draws(S, map)
         if has_t:
-            tot = [sum(col) for col in zip(*totals.cpu().tolist())]     # chunk order (synchronises)
+            tot = _chunk_sums(totals)
             res.totals = tot
             res.nll, res.accuracy = tot[0] / R, 100.0 * tot[1] / R
             res.mean_draw_nll, res.mean_draw_accuracy = tot[2] / (R * S), 100.0 * tot[3] / (R * S)
@@ -491,9 +495,6 @@ class _Predictive:
             if ybuf is None or tuple(ybuf.shape) != (op_rows, Wd):
                 ybuf = bufs.y_reg = torch.empty(op_rows, Wd, dtype=torch.float32, device=self.device)
 
-        def off(t, row):
-            return C.c_void_p(t.data_ptr() + 4 * row) if t is not None else None
-
         def final_linear(N, y_ptr):
             fa = L.FwdArgs(w=self.w3_s.ptr, w2=None, x=bufs[nl].x.ptr, x2=None, ld_w=self.w3_s.ld, ld_x=bufs[nl].x.ld,
                            N=N, I=H, O=Wd, bias=_p(self.bias3), y=y_ptr, ld_y=Wd)
@@ -515,7 +516,7 @@ class _Predictive:
                     call()
                 else:
                     for s in range(S):
-                        a.y, a.draw = off(y, s * rows * Wd), s
+                        a.y, a.draw = _off(y, s * rows * Wd), s
                         call()
                 if keep_draws and not direct:
                     draws[:, c0:c0 + rows].copy_(ybuf[:S * rows].view(S, rows, Wd))
@@ -524,7 +525,7 @@ class _Predictive:
                 if wts is not None:
                     self._predict_wn_sample(wts, d0 + s)
                 self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
-                yp = off(draws, (s * R + c0) * Wd) if direct else _p(ybuf)
+                yp = _off(draws, (s * R + c0) * Wd) if direct else _p(ybuf)
                 final_linear(rows, yp)
                 a.y, a.draw = yp, s
                 call()
