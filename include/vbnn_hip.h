@@ -888,6 +888,59 @@ typedef struct vbnn_quantiles_args {
 } vbnn_quantiles_args;
 int vbnn_predict_quantiles(vbnn_ctx* ctx, const vbnn_quantiles_args* a);
 
+/* ---- the sampling-free predictive by moment propagation (additive, ABI 6; vbnn_amd/csrc/propagate.hip; not in the reference) --
+ * A factorised-Gaussian posterior needs no draws to predict: one pass carries (mean a, second moment q, variance c) of every
+ * activation through the network. A hidden layer is three SINGLE products of vbnn_forward (w2 = NULL, y out, no ReLU):
+ *   m = a mu^T + b,   v1 = q (sigma^2)^T,   v2 = c (mu^2)^T      (the first layer's input is deterministic: a = x, q = x . x, no v2)
+ * -- Var[sum_i w_i h_i] = sum_i (sigma_i^2 E[h_i^2] + mu_i^2 Var[h_i]) for independent w and h, unit correlations dropped -- then
+ * vbnn_relu_moments; the final Linear gives the output mean a w3^T + b3 and the output variance c (w3^2)^T. The three calls
+ * below are the pieces that are not a GEMM. All three calls' arithmetic is fp32, operation by operation as written here
+ * (compiled without floating-point contraction; sqrt and the division are correctly rounded; expf / erfcf are the library
+ * functions). Non-finite inputs and negative variances are out of contract: the outputs of such an element are unspecified
+ * (no other element is affected).
+ *
+ * vbnn_relu_moments: per element of an N x O block, the moments of h = max(0, y), y ~ N(m, v), with v = v1 (v2 == NULL) or
+ * v = v1 + v2:
+ *   v > 0:   s = sqrtf(v);  al = m / s;  phi = 0.3989423f * expf(-0.5f * (al * al));  Phi = 0.5f * erfcf(-(al * 0.70710677f))
+ *            a = max(m * Phi + s * phi, 0);   q = max((m * m + v) * Phi + (m * s) * phi, 0);   c = max(q - a * a, 0)
+ *   else:    a = max(m, 0);  q = a * a;  c = 0        (zero inputs, pruned-away units, pad rows: no division, no NaN)
+ * i.e. a = s (al Phi + phi), q = s^2 ((al^2 + 1) Phi + al phi) in the form that needs no al^2 (a huge |al| does not overflow);
+ * Phi goes through erfcf on BOTH sides, so the lower tail keeps its relative accuracy; q - a * a is formed in fp32 before any
+ * rounding to the operand type. a, q, c are PACKED operands (dtype, N x ld_out, each optional): pads are never written.
+ * A streaming kernel, no LDS: a thread works 16 bytes of every output (4 fp32 / 8 bf16 columns) with 16-byte loads and stores
+ * where the base addresses and leading dimensions allow (chosen per launch; a row's last partial group and everything else go
+ * element by element, 4-byte loads). Bitwise reproducible (no reduction). m, v1, v2 are 4-byte aligned, a, q, c aligned to their
+ * element; an output that overlaps an input or another output is VBNN_ERR_INVALID. */
+typedef struct vbnn_relu_moments_args {
+    const float* m; int64_t ld_m;           /* pre-activation mean, N x O fp32 */
+    const float* v1; const float* v2; int64_t ld_v;   /* variance parts, N x O fp32 each (one ld); v2 may be NULL */
+    int64_t N, O;
+    void* a; void* q; void* c; int64_t ld_out;        /* E[h], E[h^2], Var[h]: packed (dtype), N x ld_out, ld_out >= O; NULL to skip */
+} vbnn_relu_moments_args;
+int vbnn_relu_moments(vbnn_ctx* ctx, int dtype, const vbnn_relu_moments_args* a);
+
+/* dst[r][c] = T(float(src[r][c]) * float(src[r][c])) for r < rows, c < cols over a packed operand (dtype -> dtype; bf16: the
+ * fp32 product rounded to nearest-even): the mu^2 operand from the mu shadow and the final Linear's w3^2 from its packed weight,
+ * AS THEY ARE -- a dense pruned view's +0 entries, a held mask's, a compact network's shapes need nothing else. Pads are neither
+ * read nor written. 16-byte accesses where both bases and both leading dimensions allow. */
+int vbnn_square_shadow(vbnn_ctx* ctx, int dtype, const void* src, int64_t ld_src, int64_t rows, int64_t cols,
+                       void* dst, int64_t ld_dst);
+
+/* S draws of R x C Gaussian logits: y[s][r][c] = m[r][c] + sqrtf(v[r][c]) * z, z = lane c & 3 of
+ * vbnn_normal4(seed, VBNN_STREAM_ZETA, layer, draw + s, row0 + r, c >> 2) -- the contract's bit-exact form (what
+ * vbnn_fill_normal gives for the same address), one multiply and one add in fp32. `layer` is the FINAL Linear's layer id (the
+ * number of VB layers): every other ZETA draw of the library belongs to a VB layer's forward (ids below it), and the final
+ * Linear draws from EPS / ZETA nowhere else, so no existing path reads this stream. Draw s of row r starts at
+ * y + s draw_stride + r ld_y: with ld_y = C, draw_stride = R C exactly the S R x C layout vbnn_predict_class_moments takes. */
+typedef struct vbnn_logit_draws_args {
+    const float* m; int64_t ld_m;           /* logit means, R x C fp32 */
+    const float* v; int64_t ld_v;           /* logit variances, R x C fp32 (>= 0) */
+    int64_t R, C, S;
+    uint64_t seed; uint32_t layer; uint32_t draw; int64_t row0;
+    float* y; int64_t ld_y; int64_t draw_stride;      /* ld_y >= C, draw_stride >= R ld_y */
+} vbnn_logit_draws_args;
+int vbnn_logit_draws(vbnn_ctx* ctx, const vbnn_logit_draws_args* a);
+
 /* ---- signal-to-noise pruning (additive, ABI 6): mainviz.lua:20-27 on the device, and the pruned operand shadows that let
  * vbnn_forward / vbnn_head_predict evaluate the pruned network ---------------------------------------------------------------
  * The key of a weight is snr = |means / sqrt(exp(lvars))| in fp32, operation for operation as mainviz.lua:20 forms

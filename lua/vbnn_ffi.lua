@@ -324,6 +324,23 @@ typedef struct vbnn_quantiles_args {
     uint64_t* count_le;
 } vbnn_quantiles_args;
 int vbnn_predict_quantiles(vbnn_ctx* ctx, const vbnn_quantiles_args* a);
+typedef struct vbnn_relu_moments_args {
+    const float* m; int64_t ld_m;
+    const float* v1; const float* v2; int64_t ld_v;
+    int64_t N, O;
+    void* a; void* q; void* c; int64_t ld_out;
+} vbnn_relu_moments_args;
+int vbnn_relu_moments(vbnn_ctx* ctx, int dtype, const vbnn_relu_moments_args* a);
+int vbnn_square_shadow(vbnn_ctx* ctx, int dtype, const void* src, int64_t ld_src, int64_t rows, int64_t cols,
+                       void* dst, int64_t ld_dst);
+typedef struct vbnn_logit_draws_args {
+    const float* m; int64_t ld_m;
+    const float* v; int64_t ld_v;
+    int64_t R, C, S;
+    uint64_t seed; uint32_t layer; uint32_t draw; int64_t row0;
+    float* y; int64_t ld_y; int64_t draw_stride;
+} vbnn_logit_draws_args;
+int vbnn_logit_draws(vbnn_ctx* ctx, const vbnn_logit_draws_args* a);
 typedef struct vbnn_prune_desc {
     const float* means; const float* lvars; int64_t O, I;
     void* mu_p; void* var_p; int64_t ld_w;

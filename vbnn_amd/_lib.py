@@ -141,6 +141,16 @@ QUANTILES_MAX_S = 128                 # VBNN_QUANTILES_MAX_S
 QUANTILES_MAX_Q = 8                   # VBNN_QUANTILES_MAX_Q
 
 
+class ReluMomentsArgs(C.Structure):   # vbnn_relu_moments_args
+    _fields_ = [("m", _vp), ("ld_m", _i64), ("v1", _vp), ("v2", _vp), ("ld_v", _i64), ("N", _i64), ("O", _i64),
+                ("a", _vp), ("q", _vp), ("c", _vp), ("ld_out", _i64)]
+
+
+class LogitDrawsArgs(C.Structure):    # vbnn_logit_draws_args
+    _fields_ = [("m", _vp), ("ld_m", _i64), ("v", _vp), ("ld_v", _i64), ("R", _i64), ("C", _i64), ("S", _i64),
+                ("seed", _u64), ("layer", _u32), ("draw", _u32), ("row0", _i64), ("y", _vp), ("ld_y", _i64), ("draw_stride", _i64)]
+
+
 class PruneDesc(C.Structure):         # vbnn_prune_desc
     _fields_ = [("means", _vp), ("lvars", _vp), ("O", _i64), ("I", _i64), ("mu_p", _vp), ("var_p", _vp), ("ld_w", _i64),
                 ("stats", _vp), ("mask", _vp)]
@@ -259,6 +269,9 @@ _SIGS = {
     "vbnn_predict_gauss_moments": ([_vp, C.POINTER(GaussMomentsArgs)], _i),
     "vbnn_predict_class_moments": ([_vp, C.POINTER(ClassMomentsArgs)], _i),
     "vbnn_predict_quantiles": ([_vp, C.POINTER(QuantilesArgs)], _i),
+    "vbnn_relu_moments": ([_vp, _i, C.POINTER(ReluMomentsArgs)], _i),
+    "vbnn_square_shadow": ([_vp, _i, _vp, _i64, _i64, _i64, _vp, _i64], _i),
+    "vbnn_logit_draws": ([_vp, C.POINTER(LogitDrawsArgs)], _i),
     "vbnn_snr": ([_vp, _vp, _vp, _i64, _vp], _i),
     "vbnn_prune_workspace_bytes": ([_i, _vp, C.POINTER(C.c_size_t)], _i),
     "vbnn_prune_select": ([_vp, _i, _vp, _i64, _vp, _vp, C.c_size_t], _i),

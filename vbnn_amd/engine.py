@@ -55,6 +55,7 @@ class _StepGraph:
             L.check(L.lib().vbnn_graph_launch(self.h))
         self.eng.draw += self.draws                      # the host's mirror of the device counter
         self.eng._first = False
+        self.eng._ana_ops_stale = True                   # a replayed update() moves the shadows without a new parameter version
 
     def close(self):
         if self.h:
@@ -288,6 +289,8 @@ class FusedMLP(_Predictive, _Pruning, _Checkpoint):
         self._held_counts = None
         self._opt_state, self.update_log = {}, None           # Adam's moments and step counts (_adam_slot); update(log=True)'s series
         self._pred_bufs = self._pred_key = self._pred_wts = self._sparse_bufs = self._sparse_key = None     # predictive.py, on first use
+        self._ana_ops = self._ana_bufs = None                 # predict_analytic's squared operands (per parameter version) and buffers
+        self._ana_ops_stale = False                           # set by a graph replay (_StepGraph.launch): the squares are rebuilt
         self.init_parameters()
 
     # mlp.lua:47-55 (He rule for every weight, bias zero) + the bench's non-degenerate means

@@ -1,5 +1,6 @@
-"""The posterior predictives of the fused engine (FusedMLP.predict / predict_classes / predict_regression / predict_quantiles):
-forward-only passes on buffers of their own, dense or under a pruned view (pruning.py). A mixin of vbnn_amd/engine.py:FusedMLP."""
+"""The posterior predictives of the fused engine (FusedMLP.predict / predict_classes / predict_regression / predict_quantiles, and
+the sampling-free predict_analytic): forward-only passes on buffers of their own, dense or under a pruned view (pruning.py). A
+mixin of vbnn_amd/engine.py:FusedMLP."""
 import ctypes as C
 import math
 import types
@@ -35,13 +36,16 @@ class PredictResult:
     FusedMLP.predict_classes (any class count) returns the same fields with the same meanings (probs / log_probs None with
     keep_probs=False) and, with topk = K > 0, topk_idx (R x K int32: the K most probable classes, most probable first, ties to
     the lower index) and topk_prob (R x K: their probabilities), with targets topk_accuracy (percent of rows whose target is
-    among them); with keep_draws, draws (S x R x C: every draw's logits). totals: the library's sums."""
+    among them); with keep_draws, draws (S x R x C: every draw's logits). totals: the library's sums.
+    FusedMLP.predict_analytic (criterion "nll") returns the same fields from S draws of the propagated logit distribution, with
+    logit_mean / logit_var (R x C: the propagated moments they were drawn from) and, with keep_probs, draws (the sampled logits)."""
 
     def __init__(self, probs, log_probs, entropy, expected_entropy, mutual_info, pred):
         self.probs, self.log_probs, self.entropy = probs, log_probs, entropy
         self.expected_entropy, self.mutual_info, self.pred = expected_entropy, mutual_info, pred
         self.nll = self.accuracy = self.mean_draw_nll = self.mean_draw_accuracy = None
         self.totals = self.topk_idx = self.topk_prob = self.topk_accuracy = self.draws = None
+        self.logit_mean = self.logit_var = None                # predict_analytic: the propagated logit moments (R x C)
         self.S, self.stacked, self.chunks = None, None, None
 
 
@@ -57,7 +61,11 @@ class RegressionPredictResult:
     aleatoric part -- the total predictive variance is var + noise_var), row_noise_var (R: its mean over the outputs), and with
     targets mean_noise_var and mean_draw_nll (the mean over draws of each draw's Gaussian criterion: test()'s number); totals
     then has five sums, mean_draw_mse is None, draws is S x R x 2 D and row_log_lik / log_lik are those of the mixture of
-    N(m_s, diag exp(s_s))."""
+    N(m_s, diag exp(s_s)).
+    FusedMLP.predict_analytic (criterion "mse") returns the same fields without draws: S = 0 and draws None; mean and var are the
+    PROPAGATED output mean and epistemic variance (no Monte-Carlo noise); row_log_lik / log_lik are those of ONE Gaussian
+    N(mean, var + noise_var) per output; mean_draw_mse is its expectation under that Gaussian, mse + mean_var; totals =
+    [sum row_sq_err, sum (row_sq_err + D row_var), sum row_log_lik (0 without noise_var), sum var]."""
 
     def __init__(self, mean, var, row_var, row_sq_err, row_log_lik, draws):
         self.mean, self.var, self.row_var = mean, var, row_var
@@ -442,6 +450,22 @@ class _Predictive:
             targets = targets.contiguous()
         p = self._predictive_plan("predict_classes", inputs, S, map, row0)
         R, S, map, stacked, Rc, n_chunks = p.R, p.S, p.map, p.stacked, p.Rc, p.n_chunks
+        one_call = stacked and Cn <= L.CLASS_MOMENTS_STACKED_MAX_C       # else: ACCUMULATE per draw
+        res, a, totals, point, _state = self._class_moments_plan(R, S, Rc, n_chunks, one_call, targets, K, keep_probs)
+        if keep_draws:
+            res.draws = torch.empty(S, R, Cn, dtype=torch.float32, device=self.device)
+        self._moments_loop(p, Cn, res.draws, keep_draws, one_call, a,
+                           lambda: L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a))), point)
+        self._consume_draws(S, map)
+        self._class_moments_finish(res, totals, R, S, K)
+        res.S, res.stacked, res.chunks = S, stacked, n_chunks
+        return res
+
+    def _class_moments_plan(self, R, S, Rc, n_chunks, one_call, targets, K, keep_probs):
+        """What predict_classes and predict_analytic set up for vbnn_predict_class_moments over R rows in n_chunks chunks of Rc:
+        the PredictResult with its output tensors, the argument block, the chunks' totals, point(c0, rows), which aims the
+        block at a chunk (y / draw are the caller's), and the ACCUMULATE form's state."""
+        Cn = self.n_classes
         f32 = dict(dtype=torch.float32, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
         has_t = targets is not None
@@ -449,9 +473,6 @@ class _Predictive:
                             torch.empty(R, **f32), torch.empty(R, **f32), torch.empty(R, **f32), torch.empty(R, **i32))
         if K:
             res.topk_idx, res.topk_prob = torch.empty(R, K, **i32), torch.empty(R, K, **f32)
-        if keep_draws:
-            res.draws = torch.empty(S, R, Cn, **f32)
-        one_call = stacked and Cn <= L.CLASS_MOMENTS_STACKED_MAX_C       # else: ACCUMULATE per draw
         ld_state = (Cn + 3 + 3) // 4 * 4                                 # a multiple of 4: every row of the state on the 16-byte path
         state = None if one_call else torch.empty(Rc, ld_state, **f32)
         totals = torch.zeros(n_chunks, 5, dtype=torch.float64, device=self.device) if has_t else None
@@ -466,17 +487,18 @@ class _Predictive:
             a.entropy, a.expected_entropy, a.mutual_info = _off(res.entropy, c0), _off(res.expected_entropy, c0), _off(res.mutual_info, c0)
             a.pred, a.topk_idx, a.topk_prob = _off(res.pred, c0), _off(res.topk_idx, c0 * K), _off(res.topk_prob, c0 * K)
 
-        self._moments_loop(p, Cn, res.draws, keep_draws, one_call, a,
-                           lambda: L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a))), point)
-        self._consume_draws(S, map)
-        if has_t:
-            tot = _chunk_sums(totals)
-            res.totals = tot
-            res.nll, res.accuracy = tot[0] / R, 100.0 * tot[1] / R
-            res.mean_draw_nll, res.mean_draw_accuracy = tot[2] / (R * S), 100.0 * tot[3] / (R * S)
-            res.topk_accuracy = 100.0 * tot[4] / R if K else None
-        res.S, res.stacked, res.chunks = S, stacked, n_chunks
-        return res
+        return res, a, totals, point, state          # (state: the caller keeps it alive across its launches)
+
+    @staticmethod
+    def _class_moments_finish(res, totals, R, S, K):
+        """The Python floats of a class predictive from the chunks' totals (synchronises); nothing without targets."""
+        if totals is None:
+            return
+        tot = _chunk_sums(totals)
+        res.totals = tot
+        res.nll, res.accuracy = tot[0] / R, 100.0 * tot[1] / R
+        res.mean_draw_nll, res.mean_draw_accuracy = tot[2] / (R * S), 100.0 * tot[3] / (R * S)
+        res.topk_accuracy = 100.0 * tot[4] / R if K else None
 
     def _moments_loop(self, p, Wd, draws, keep_draws, one_call, a, call, point):
         """The chunk loop predict_regression and predict_classes share: per chunk the forward (every draw stacked, or one draw
@@ -564,3 +586,214 @@ class _Predictive:
                                 ld_h=out.x.ld if last else 0, hT=None if last else T[li + 1].ptr, h2T=None,
                                 ld_hT=0 if last else T[li + 1].ld, rows_per_draw=rpd)
             L.check(lib.vbnn_forward_sparse(ctx, code, C.byref(a)))
+
+    # ---- the sampling-free predictive (csrc/propagate.hip): ONE pass that carries the mean, the second moment
+    # and the variance of every activation through the network -- per hidden layer three single GEMMs of vbnn_forward (a mu^T + b,
+    # q (sigma^2)^T, c (mu^2)^T) and vbnn_relu_moments, then the final Linear's a w3^T + b3 and c (w3^2)^T -- on buffers of its own.
+    # Exact for one VB layer; with more, unit correlations are dropped and pre-activations taken as Gaussian.
+    @_ordered
+    def predict_analytic(self, inputs, targets=None, noise_var=None, S=None, row0=None, topk=0, keep_probs=True):
+        """The posterior predictive WITHOUT Monte-Carlo forwards: the network runs once, on moments.
+        criterion = "mse": a RegressionPredictResult with predict_regression's fields -- mean (the propagated output mean), var
+        (the propagated epistemic variance), row_var; with targets (R x D) row_sq_err, mse, mean_var and mean_draw_mse (its
+        expectation under the propagated Gaussian, mse + mean_var); with noise_var (tau^2 > 0) row_log_lik / log_lik of
+        N(mean, var + tau^2) per output -- ONE Gaussian, not predict_regression's mixture over draws. draws is None, S = 0, no
+        draw is consumed and two calls agree bit for bit. The row sums and the log-likelihood are torch operations on the R x D
+        outputs (no kernel of the library: they are a few R x D elementwise passes beside the network's GEMMs).
+        criterion = "nll" (any class count): the logit mean and variance are sampled S times (default opt.testSamples; draws
+        self.draw + 1 .. self.draw + S of the final Linear's own noise stream, rows addressed from row0 as predict) by
+        vbnn_logit_draws and finished by vbnn_predict_class_moments: a PredictResult with predict_classes' fields (topk,
+        keep_probs), plus logit_mean / logit_var (R x C) and, with keep_probs, draws (the S x R x C sampled logits; without, they
+        stay in a per-chunk buffer). `self.draw` advances by S (host and device counter). Only R x C logits are sampled; the logits are taken as independent Gaussians.
+        criterion = "gauss" is refused (the clamp on the log variance makes its moments a separate piece of work). Both modes;
+        dense pruned views, held masks and compact networks work through the operand shadows; compressed views are refused.
+        Chunked by opt.predict_rows. Returns this rank's rows (no collective)."""
+        lib, ctx, code = L.lib(), self.ctx.h, self.code
+        what = "predict_analytic"
+        if self.criterion == "gauss":
+            raise ValueError(f"{what}: criterion = 'gauss' is not supported -- the clamp on the log variance makes the moments of "
+                             "exp(s) a separate piece of work (the follow-up); use predict_regression")
+        if isinstance(self._pruned, SparsePruneResult):
+            raise ValueError(f"{what}: a compressed pruned view is not supported (use the dense PruneResult it was compressed "
+                             "from, or predict / predict_regression)")
+        nll = self.criterion == "nll"
+        Wd, K = self.n_classes, int(topk)
+        if inputs.dim() < 2 or inputs.shape[0] < 1 or inputs.numel() != inputs.shape[0] * self.sizes[0]:
+            raise ValueError(f"{what}: inputs of shape {tuple(inputs.shape)} (R x {self.sizes[0]}, R >= 1)")
+        x = inputs.reshape(inputs.shape[0], -1)
+        if x.dtype != torch.float32 or not x.is_cuda:
+            raise ValueError(f"{what}: inputs are fp32 device tensors")
+        R = x.shape[0]
+        if nll:
+            if noise_var is not None:
+                raise ValueError(f"{what}: noise_var belongs to the regression predictive (criterion = 'nll')")
+            if not 0 <= K <= min(L.CLASS_MOMENTS_MAX_K, Wd):
+                raise ValueError(f"{what}: topk = {K} (0 .. {L.CLASS_MOMENTS_MAX_K}, and at most n_classes = {Wd})")
+            S = int(self.opt["testSamples"] if S is None else S)
+            if S < 1:
+                raise ValueError(f"{what}: S = {S} draws (at least one)")
+            if targets is not None:
+                if targets.dtype != torch.int32 or not targets.is_cuda or targets.numel() != R:
+                    raise ValueError(f"{what}: targets of shape {tuple(targets.shape)} (R = {R} int32 class indices on the device)")
+                targets = targets.contiguous()
+        else:
+            if K:
+                raise ValueError(f"{what}: topk belongs to the class predictive (criterion = 'mse')")
+            if S is not None or row0 is not None:
+                raise ValueError(f"{what}: S and row0 address the class predictive's logit draws (criterion = 'mse' draws nothing)")
+            if noise_var is not None:
+                noise_var = float(noise_var)
+                if not (noise_var > 0.0 and math.isfinite(noise_var)):
+                    raise ValueError(f"{what}: noise_var = {noise_var} (a finite variance above zero, or None)")
+            if targets is not None:
+                if targets.dtype != torch.float32 or not targets.is_cuda or tuple(targets.shape) != (R, Wd):
+                    raise ValueError(f"{what}: targets of shape {tuple(targets.shape)} (R x D = {R} x {Wd} fp32 on the device)")
+                targets = targets.contiguous()
+        row0 = self.rank * R if row0 is None else int(row0)
+        if not self._shadows_ready:
+            self.prepare()
+        if self._pruned is not None and self._pruned.version != self._pver:
+            raise RuntimeError(f"{what}: the pruned view was taken from older parameters (update / prepare / init_parameters "
+                               "ran since): prune() again, or use_pruned(None)")
+        ops = self._analytic_operands()
+        Rc = max(1, min(R, int(self.opt.get("predict_rows", 32768))))
+        n_chunks = (R + Rc - 1) // Rc
+        B = self._analytic_buffers(Rc)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        nl, H = len(self.vb), self.sizes[-1]
+
+        def gemm(w, xin, N, I, O, bias, y, ld_y):                # one single product of vbnn_forward: y = x w^T (+ b), fp32 out
+            fa = L.FwdArgs(w=w.ptr, w2=None, x=xin.ptr, x2=None, ld_w=w.ld, ld_x=xin.ld, N=N, I=I, O=O, bias=bias, y=y, ld_y=ld_y)
+            L.check(lib.vbnn_forward(ctx, code, C.byref(fa)))
+
+        def propagate(xc, rows, mean_ptr, var_ptr):              # the chunk's output mean and variance (rows x Wd fp32 each)
+            b0 = B.act[0]
+            L.check(lib.vbnn_pack_input(ctx, code, _p(xc), xc.stride(0), rows, self.sizes[0], b0.a.ptr, b0.q.ptr, b0.a.ld,
+                                        None, None, 0, 0))
+            for li, v in enumerate(self.vb):
+                xin, out, ld = B.act[li], B.act[li + 1], L.pad_ld(v.O)
+                mu, var, mu2 = ops.mu[li], ops.var[li], ops.mu2[li]
+                gemm(mu, xin.a, rows, v.I, v.O, _p(v.bias), _p(B.m), ld)
+                gemm(var, xin.q, rows, v.I, v.O, None, _p(B.v1), ld)
+                if li > 0:                                       # (the first layer's input is deterministic: c = 0)
+                    gemm(mu2, xin.c, rows, v.I, v.O, None, _p(B.v2), ld)
+                ra = L.ReluMomentsArgs(m=_p(B.m), ld_m=ld, v1=_p(B.v1), v2=_p(B.v2) if li > 0 else None, ld_v=ld, N=rows, O=v.O,
+                                       a=out.a.ptr, q=out.q.ptr if li < nl - 1 else None, c=out.c.ptr, ld_out=out.a.ld)
+                L.check(lib.vbnn_relu_moments(ctx, code, C.byref(ra)))
+            gemm(self.w3_s, B.act[nl].a, rows, H, Wd, _p(self.bias3), mean_ptr, Wd)
+            gemm(ops.w3sq, B.act[nl].c, rows, H, Wd, None, var_ptr, Wd)
+
+        if not nll:
+            res = RegressionPredictResult(torch.empty(R, Wd, **f32), torch.empty(R, Wd, **f32), None, None, None, None)
+            for k in range(n_chunks):
+                c0 = k * Rc
+                rows = min(Rc, R - c0)
+                propagate(x[c0:c0 + rows], rows, _off(res.mean, c0 * Wd), _off(res.var, c0 * Wd))
+            res.row_var = res.var.mean(dim=1)
+            if targets is not None:
+                d2 = (targets - res.mean) ** 2
+                res.row_sq_err = d2.sum(dim=1)
+                if noise_var is not None:
+                    tv = res.var + noise_var
+                    res.row_log_lik = (-0.5 * (torch.log(6.2831855 * tv) + d2 / tv)).sum(dim=1)
+                sq, vs = float(res.row_sq_err.double().sum()), float(res.var.double().sum())
+                ll = float(res.row_log_lik.double().sum()) if noise_var is not None else 0.0
+                res.totals = [sq, sq + vs, ll, vs]
+                res.mse, res.mean_var = sq / (R * Wd), vs / (R * Wd)
+                res.mean_draw_mse = (sq + vs) / (R * Wd)
+                res.log_lik = ll / R if noise_var is not None else None
+            res.S, res.stacked, res.chunks = 0, None, n_chunks
+            return res
+
+        # keep_probs: the draws are returned, written straight into the S x R x C result (one chunk: one STACKED call; more: a call
+        # per draw, each read in place). Otherwise they live in the chunk's own S x rows x C buffer, kept with the other buffers.
+        stacked = (n_chunks == 1 or not keep_probs) and Wd <= L.CLASS_MOMENTS_STACKED_MAX_C
+        res, a, totals, point, _state = self._class_moments_plan(R, S, Rc, n_chunks, stacked, targets, K, keep_probs)
+        res.logit_mean, res.logit_var = torch.empty(R, Wd, **f32), torch.empty(R, Wd, **f32)
+        if keep_probs:
+            res.draws = torch.empty(S, R, Wd, **f32)
+        elif B.y is None or B.y.numel() != S * Rc * Wd:
+            B.y = torch.empty(S * Rc * Wd, **f32)
+        d0 = self.draw + 1
+        for k in range(n_chunks):
+            c0 = k * Rc
+            rows = min(Rc, R - c0)
+            mp, vp = _off(res.logit_mean, c0 * Wd), _off(res.logit_var, c0 * Wd)
+            propagate(x[c0:c0 + rows], rows, mp, vp)
+            y0, stride = (_off(res.draws, c0 * Wd), R * Wd) if keep_probs else (_p(B.y), rows * Wd)
+            da = L.LogitDrawsArgs(m=mp, ld_m=Wd, v=vp, ld_v=Wd, R=rows, C=Wd, S=S, seed=self.seed, layer=nl, draw=d0,
+                                  row0=row0 + c0, y=y0, ld_y=Wd, draw_stride=stride)
+            L.check(lib.vbnn_logit_draws(ctx, C.byref(da)))
+            point(c0, rows)
+            if stacked:
+                a.y = y0
+                L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a)))
+            else:
+                for s in range(S):
+                    a.y, a.draw = C.c_void_p(y0.value + 4 * s * stride), s
+                    L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a)))
+        self._consume_draws(S, False)
+        self._class_moments_finish(res, totals, R, S, K)
+        res.S, res.stacked, res.chunks = S, False, n_chunks
+        return res
+
+    def _analytic_operands(self):
+        """predict_analytic's weight-side operands: mu and sigma^2 as the predictive reads them -- the pruned view's shadows, the
+        operand shadows (LRT: a held mask's +0 entries included), or packed here from means / lvars (WN, whose prepare packs
+        none) -- and mu^2 and w3^2 squared from them AS THEY ARE (vbnn_square_shadow). Rebuilt when the parameter version or the
+        pruned view changes, and after a graph replay (a captured update() changes the shadows without a new version); kept otherwise."""
+        key = (self._pver, self._pruned)
+        st = getattr(self, "_ana_ops", None)
+        if st is not None and st.key[0] == key[0] and st.key[1] is key[1] and not self._ana_ops_stale:
+            return st
+        self._ana_ops_stale = False
+        lib, ctx, code, dev = L.lib(), self.ctx.h, self.code, self.device
+        st = st or types.SimpleNamespace(mu2=[_Packed(v.O, v.I, self.tdt, dev) for v in self.vb], own=None,
+                                         w3sq=_Packed(self.n_classes, self.sizes[-1], self.tdt, dev))
+        pv = self._pruned
+        if pv is not None:
+            st.mu, st.var = list(pv.mu_p), list(pv.var_p)
+        elif self.mode == "lrt":
+            st.mu, st.var = [v.mu_s for v in self.vb], [v.var_s for v in self.vb]
+        else:                                  # weight noise: the shadows of means and exp(lvars), packed on demand
+            if st.own is None:
+                st.own = [(_Packed(v.O, v.I, self.tdt, dev), _Packed(v.O, v.I, self.tdt, dev)) for v in self.vb]
+            for v, (m_s, v_s) in zip(self.vb, st.own):
+                L.check(lib.vbnn_pack(ctx, code, L.PACK_COPY, _p(v.means), None, v.I, v.O, v.I, m_s.ptr, m_s.ld, None, 0))
+                L.check(lib.vbnn_pack(ctx, code, L.PACK_EXP, _p(v.lvars), None, v.I, v.O, v.I, v_s.ptr, v_s.ld, None, 0))
+            st.mu, st.var = [o[0] for o in st.own], [o[1] for o in st.own]
+        for v, mu, mu2 in zip(self.vb, st.mu, st.mu2):
+            L.check(lib.vbnn_square_shadow(ctx, code, mu.ptr, mu.ld, v.O, v.I, mu2.ptr, mu2.ld))
+        L.check(lib.vbnn_square_shadow(ctx, code, self.w3_s.ptr, self.w3_s.ld, self.n_classes, self.sizes[-1], st.w3sq.ptr, st.w3sq.ld))
+        st.key = key
+        self._ana_ops = st
+        return st
+
+    def _analytic_buffers(self, rows):
+        """predict_analytic's own buffers for `rows` operand rows: act[li] = layer li's input moments (a, q, c packed; act[0] the
+        packed input and its square), one ping-pong pair per hidden width as _predict_buffers; m, v1, v2: the three products'
+        fp32 outputs (rows x the widest padded layer). Kept across calls while the row count holds."""
+        st = getattr(self, "_ana_bufs", None)
+        if st is not None and st.rows == rows:
+            return st
+        dev, tdt, nl = self.device, self.tdt, len(self.vb)
+        slots = {}
+
+        def slot(cols, parity, q, c):
+            b = slots.get((cols, parity))
+            if b is None:
+                b = slots[(cols, parity)] = types.SimpleNamespace(a=_Packed(rows, cols, tdt, dev), q=None, c=None)
+            if q and b.q is None:
+                b.q = _Packed(rows, cols, tdt, dev)
+            if c and b.c is None:
+                b.c = _Packed(rows, cols, tdt, dev)
+            return b
+        act = [slot(self.sizes[0], "in", True, False)]
+        for li, v in enumerate(self.vb):
+            act.append(slot(v.O, li % 2, li < nl - 1, True))
+        wide = rows * max(L.pad_ld(v.O) for v in self.vb)
+        f32 = dict(dtype=torch.float32, device=dev)
+        st = types.SimpleNamespace(rows=rows, act=act, m=torch.zeros(wide, **f32), v1=torch.zeros(wide, **f32), v2=torch.zeros(wide, **f32),
+                                   y=None)                  # (y: the class predictive's S x rows x C logit draws, on first use)
+        self._ana_bufs = st
+        return st

@@ -147,6 +147,11 @@ class Main:
         # opt.quantile_probs (off by default): `dev_cal@<p>`, the fraction of the test targets at or below the predictive's
         # p-quantile (calibrated: p) -- FusedMLP.predict_quantiles, whose moments are predict_regression's of the same draws
         qprobs = [float(v) for v in (opt.get("quantile_probs") or [])] if (regression and opt.get("predictive")) else []
+        # opt.predictive = "analytic": the same series from FusedMLP.predict_analytic -- one moment-propagation pass instead of
+        # opt.testSamples forwards ("mse" and "nll"; it has no quantiles)
+        analytic = opt.get("predictive") == "analytic"
+        if analytic and qprobs:
+            raise ValueError("opt.quantile_probs needs the sampled predictive (opt.predictive = True): predict_analytic has no quantiles")
         for pj in qprobs:
             pred[f"dev_cal@{pj:g}"] = 0.0
         for t0 in starts:
@@ -156,7 +161,9 @@ class Main:
             accuracy += acc
             error += err
             if opt.get("predictive") and regression:
-                if qprobs:                                 # opt.quantile_probs: the same draws give the calibration too
+                if analytic:
+                    r = net.predict_analytic(x, targets=t, noise_var=tau2)
+                elif qprobs:                                 # opt.quantile_probs: the same draws give the calibration too
                     qr = net.predict_quantiles(x, qprobs, targets=t, noise_var=tau2)
                     r = qr.moments
                     for pj, cj in zip(qprobs, qr.calibration):
@@ -169,7 +176,9 @@ class Main:
                 if "dev_noise_var" in pred:
                     pred["dev_noise_var"] += r.mean_noise_var
             elif opt.get("predictive"):    # the S-draw model average on the same minibatch (its own draws, after test()'s)
-                if getattr(net, "n_classes", 0) > 16:      # predict's head holds a row's classes in one 16-wide tile
+                if analytic:
+                    r = net.predict_analytic(x, targets=t, keep_probs=False)
+                elif getattr(net, "n_classes", 0) > 16:      # predict's head holds a row's classes in one 16-wide tile
                     r = net.predict_classes(x, targets=t, keep_probs=False)
                 else:
                     r = net.predict(x, targets=t)
