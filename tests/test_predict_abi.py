@@ -105,7 +105,8 @@ def _c_fn(c, name):
 
 def _host_orders():
     py = _ordered_calls(_src("predict"), r"lib\.(vbnn_[a-z0-9_]+)\(",
-                        {"self.%s(" % h: _src(h) for h in ("_predictive_plan", "_predict_wn_sample", "_predict_forward", "_consume_draws")},
+                        {"self.%s(" % h: _src(h) for h in ("_predictive_plan", "_draw_forward", "_predict_wn_sample", "_predict_forward",
+                                                           "_consume_draws")},
                         drop=HOST_ONLY_WN)
     _, lua = _lua()
     lu = _ordered_calls(_section(lua, "function FusedMLP:predict(", "function FusedMLP:_predict_forward("), r"\bC\.(vbnn_[a-z0-9_]+)\s*\(",

@@ -72,7 +72,7 @@ def test_the_three_hosts_issue_prune_calls_in_the_same_order():
     # placement: outside the ranges the predict lints slice, and outside run .. finish; the predict functions do not prune
     assert raw.index("function FusedMLP:loss_and_accuracy") < raw.index("function FusedMLP:prune(") < \
         raw.index("function FusedMLP:use_pruned(") < raw.index("function FusedMLP:predict(")
-    for fn in ("predict", "_predictive_plan", "_consume_draws", "_predict_forward"):
+    for fn in ("predict", "_predictive_plan", "_predictive_inputs", "_chunks", "_draw_forward", "_consume_draws", "_predict_forward"):
         assert "vbnn_prune" not in _src(fn) and "vbnn_snr" not in _src(fn), fn
     for fn in ("fm_predict", "fm_predict_forward"):
         assert "vbnn_prune" not in _c_fn(c, fn)

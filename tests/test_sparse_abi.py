@@ -85,7 +85,7 @@ def test_the_three_hosts_issue_sparse_calls_in_the_same_order():
     cc = _ordered_calls(_c_fn(c, "fm_predict_forward_sparse"), c_re, {})
     assert py == lu == cc == ["vbnn_pack_input", "vbnn_forward_sparse"], (py, lu, cc)
     # placement: the dense functions make no sparse call
-    for fn in ("predict", "_predictive_plan", "_consume_draws", "_predict_forward", "prune"):
+    for fn in ("predict", "_predictive_plan", "_predictive_inputs", "_chunks", "_draw_forward", "_consume_draws", "_predict_forward", "prune"):
         assert "vbnn_prune_compress" not in _src(fn) and "vbnn_forward_sparse" not in _src(fn), fn
     assert "self._predict_forward_sparse(" in _src("_predict_forward")
     assert raw.index("function FusedMLP:use_pruned(") < raw.index("function FusedMLP:compress(") < \

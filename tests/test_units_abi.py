@@ -74,8 +74,8 @@ def test_the_three_hosts_issue_unit_calls_in_the_same_order():
     for fn in ("unit_snr", "prune_units", "compact", "prune_units_curve"):
         assert callable(getattr(FusedMLP, fn)), fn
     for fn in ("_prune_descs", "snr", "prune", "_prune_mask", "use_pruned", "pruned", "prune_curve", "prune_curve_sparse", "_compress",
-               "_sparse_buffers", "_predict_forward_sparse", "predict", "_predictive_plan", "_consume_draws", "_predict_wn_sample",
-               "_predict_forward"):
+               "_sparse_buffers", "_predict_forward_sparse", "predict", "_predictive_plan", "_predictive_inputs", "_chunks",
+               "_draw_forward", "_consume_draws", "_predict_wn_sample", "_predict_forward"):
         assert "vbnn_unit_" not in _src(fn), fn
     assert raw.index("function FusedMLP:loss_and_accuracy") < raw.index("function FusedMLP:prune_units(") < \
         raw.index("function FusedMLP:compact(") < raw.index("function FusedMLP:prune(")

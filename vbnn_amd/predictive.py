@@ -2,13 +2,14 @@
 the sampling-free predict_analytic): forward-only passes on buffers of their own, dense or under a pruned view (pruning.py). A
 mixin of vbnn_amd/engine.py:FusedMLP."""
 import ctypes as C
+import functools
 import math
 import types
 
 import torch
 
 from . import _lib as L
-from .nn import _Packed, _VB, _ordered, _p
+from .nn import _Packed, _ordered, _p
 from .pruning import SparsePruneResult
 
 
@@ -20,6 +21,54 @@ def _off(t, row):
 def _chunk_sums(totals):
     """The chunks' totals (chunks x NT doubles on the device) added in chunk order; synchronises."""
     return [sum(col) for col in zip(*totals.cpu().tolist())]
+
+
+def _gemm(lib, ctx, code, w, xin, N, I, O, bias, y, ld_y):
+    """One single product of vbnn_forward: y = x w^T (+ bias), fp32 out (N x O, pitch ld_y)."""
+    fa = L.FwdArgs(w=w.ptr, w2=None, x=xin.ptr, x2=None, ld_w=w.ld, ld_x=xin.ld, N=N, I=I, O=O, bias=bias, y=y, ld_y=ld_y)
+    L.check(lib.vbnn_forward(ctx, code, C.byref(fa)))
+
+
+def _stamp(res, S, stacked, chunks):
+    """The pass a result came from: its draws, whether they ran stacked, its chunks."""
+    res.S, res.stacked, res.chunks = S, stacked, chunks
+    return res
+
+
+# ---- what the entry points (`what`, for the messages) check of their arguments before anything is prepared or allocated; each
+# returns the argument as the body uses it
+def _check_draws(what, S, max_S=None):
+    if S < 1:
+        raise ValueError(f"{what}: S = {S} draws (at least one)")
+    if max_S is not None and S > max_S:
+        raise ValueError(f"{what}: S = {S} draws (at most {max_S})")
+    return S
+
+
+def _check_noise_var(what, noise_var):
+    noise_var = None if noise_var is None else float(noise_var)
+    if noise_var is not None and not (noise_var > 0.0 and math.isfinite(noise_var)):
+        raise ValueError(f"{what}: noise_var = {noise_var} (a finite variance above zero, or None)")
+    return noise_var
+
+
+def _check_topk(what, topk, n_classes):
+    K = int(topk)
+    if not 0 <= K <= min(L.CLASS_MOMENTS_MAX_K, n_classes):
+        raise ValueError(f"{what}: topk = {K} (0 .. {L.CLASS_MOMENTS_MAX_K}, and at most n_classes = {n_classes})")
+    return K
+
+
+def _check_class_targets(what, targets, R):
+    if targets is not None and (targets.dtype != torch.int32 or not targets.is_cuda or targets.numel() != R):
+        raise ValueError(f"{what}: targets of shape {tuple(targets.shape)} (R = {R} int32 class indices on the device)")
+    return None if targets is None else targets.contiguous()
+
+
+def _check_regression_targets(what, targets, R, D):
+    if targets is not None and (targets.dtype != torch.float32 or not targets.is_cuda or tuple(targets.shape) != (R, D)):
+        raise ValueError(f"{what}: targets of shape {tuple(targets.shape)} (R x D = {R} x {D} fp32 on the device)")
+    return None if targets is None else targets.contiguous()
 
 
 class _PredictBuffers(list):
@@ -107,29 +156,35 @@ class QuantilePredictResult:
 
 
 class _Predictive:
-    def _predictive_plan(self, what, inputs, S, map, row0, max_S=None):
-        """What predict and predict_regression (`what`, for the messages) share ahead of their chunk loops: resolves S / map,
-        checks the inputs, prepares a fresh engine, checks the pruned view and decides the pass -- x (R rows), S, map, row0, lrt,
-        stacked, Rc minibatch rows per chunk (n_chunks of them, op_rows operand rows each), the buffers, WN's weights, d0."""
-        map = bool(map or self.opt.get("quicktest"))
-        S = 1 if map else int(self.opt["testSamples"] if S is None else S)
-        if S < 1:
-            raise ValueError(f"{what}: S = {S} draws (at least one)")
-        if max_S is not None and S > max_S:
-            raise ValueError(f"{what}: S = {S} draws (at most {max_S})")
+    def _predictive_inputs(self, what, inputs, row0):
+        """What every predictive (`what`, for the messages) does with its inputs ahead of any allocation: checks them, resolves
+        row0 (default: this rank's first row, as run()), prepares a fresh engine and refuses a stale pruned view. Returns x
+        (R x sizes[0]), R, row0."""
+        if inputs.dim() < 1 or inputs.shape[0] < 1 or inputs.numel() != inputs.shape[0] * self.sizes[0]:
+            raise ValueError(f"{what}: inputs of shape {tuple(inputs.shape)} (R x {self.sizes[0]}, R >= 1)")
         x = inputs.reshape(inputs.shape[0], -1)
+        if x.dtype != torch.float32 or not x.is_cuda:
+            raise ValueError(f"{what}: inputs are fp32 device tensors")
         R = x.shape[0]
-        assert x.shape[1] == self.sizes[0] and x.dtype == torch.float32 and x.is_cuda and R > 0
         row0 = self.rank * R if row0 is None else int(row0)
         if not self._shadows_ready:            # a fresh engine: the shadows test() would have prepared
             self.prepare()
-        if self._pruned is not None:           # a pruned view replaces the operand shadows: it must be of THESE parameters
-            if self.mode == "wn" and not map:
-                raise ValueError(f"{what}: weight-noise draws under a pruned view are not supported -- they sample from the fp32 "
-                                 "means / lvars, which the view does not replace (use map=True, or mode = 'lrt')")
-            if self._pruned.version != self._pver:
-                raise RuntimeError(f"{what}: the pruned view was taken from older parameters (update / prepare / init_parameters "
-                                   "ran since): prune() again, or use_pruned(None)")
+        # a pruned view replaces the operand shadows: it must be of THESE parameters
+        if self._pruned is not None and self._pruned.version != self._pver:
+            raise RuntimeError(f"{what}: the pruned view was taken from older parameters (update / prepare / init_parameters "
+                               "ran since): prune() again, or use_pruned(None)")
+        return x, R, row0
+
+    def _predictive_plan(self, what, inputs, S, map, row0, max_S=None):
+        """What the sampled predictives share ahead of their chunk loops: resolves S / map, _predictive_inputs, and decides the
+        pass -- x (R rows), S, map, row0, lrt, stacked, Rc minibatch rows per chunk (n_chunks of them, op_rows operand rows
+        each), the buffers, WN's weights, d0."""
+        map = bool(map or self.opt.get("quicktest"))
+        S = _check_draws(what, 1 if map else int(self.opt["testSamples"] if S is None else S), max_S)
+        x, R, row0 = self._predictive_inputs(what, inputs, row0)
+        if self._pruned is not None and self.mode == "wn" and not map:
+            raise ValueError(f"{what}: weight-noise draws under a pruned view are not supported -- they sample from the fp32 "
+                             "means / lvars, which the view does not replace (use map=True, or mode = 'lrt')")
         lrt = self.mode == "lrt" and not map
         stacked = self._predict_stacked(R, S, lrt)
         cap = max(1, int(self.opt.get("predict_rows", 32768)))
@@ -138,6 +193,29 @@ class _Predictive:
         return types.SimpleNamespace(x=x, R=R, S=S, map=map, row0=row0, lrt=lrt, stacked=stacked, Rc=Rc, n_chunks=(R + Rc - 1) // Rc,
                                      op_rows=op_rows, bufs=self._predict_buffers(op_rows, lrt),
                                      wts=self._predict_weights() if self.mode == "wn" else None, d0=self.draw + 1)   # (d0: draw 1's counter)
+
+    @staticmethod
+    def _chunks(p):
+        """The plan's chunks in order: (k, c0, rows, xc) -- chunk k is minibatch rows [c0, c0 + rows), xc of x."""
+        for k in range(p.n_chunks):
+            c0 = k * p.Rc
+            rows = min(p.Rc, p.R - c0)
+            yield k, c0, rows, p.x[c0:c0 + rows]
+
+    def _draw_forward(self, p, xc, rows, c0, s=None):
+        """The draw step of the chunk at row c0, the one place that says which noise a row sees: WN's weights for the draw, then
+        the pack and every VB layer's forward into p.bufs. s=None: all p.S draws in one pass, the chunk stacked S times as
+        operand rows (draw s = rows [s rows, (s + 1) rows); S = 1 under map or WN). Otherwise draw s alone, draw 0 packing the
+        chunk for the draws after it."""
+        if s is None:
+            N, rpd, draw, pack = p.S * rows, rows if p.S > 1 else 0, p.d0, True
+            wn_draw = None if p.map else p.d0
+        else:
+            N, rpd, draw, pack = rows, 0, p.d0 + s, s == 0
+            wn_draw = draw
+        if p.wts is not None:
+            self._predict_wn_sample(p.wts, wn_draw)
+        self._predict_forward(p.bufs, p.wts, xc, N, rpd, draw, p.row0 + c0, p.lrt, pack=pack)
 
     def _consume_draws(self, S, map):          # the draws test() would have consumed: the host counter and the device's
         if not map:
@@ -166,53 +244,35 @@ class _Predictive:
         if self.criterion != "nll":
             raise ValueError(f"predict: a class-probability predictive needs the NLL criterion (criterion = '{self.criterion}' has "
                              "none: use predict_regression)")
-        if targets is not None:                # (before the plan: nothing is prepared or allocated for a refused call)
-            assert targets.dtype == torch.int32 and targets.is_cuda and targets.numel() == inputs.shape[0]
-            targets = targets.contiguous()
+        targets = _check_class_targets("predict", targets, inputs.shape[0])   # (before the plan: nothing is prepared for a refused call)
         p = self._predictive_plan("predict", inputs, S, map, row0)
-        x, R, S, map, row0, lrt = p.x, p.R, p.S, p.map, p.row0, p.lrt
-        stacked, Rc, n_chunks, bufs, wts, d0 = p.stacked, p.Rc, p.n_chunks, p.bufs, p.wts, p.d0
+        R, S = p.R, p.S
         f32 = dict(dtype=torch.float32, device=self.device)
         res = PredictResult(torch.empty(R, Cn, **f32), torch.empty(R, Cn, **f32), torch.empty(R, **f32), torch.empty(R, **f32),
                             torch.empty(R, **f32), torch.empty(R, dtype=torch.int32, device=self.device))
-        totals = torch.zeros(n_chunks, 4, dtype=torch.float64, device=self.device) if targets is not None else None
-        state = torch.empty(Rc, Cn + 3, **f32) if not stacked else None
-        nl = len(self.vb)
-        a = L.PredictArgs(w3=self.w3_s.ptr, ld_w=self.w3_s.ld, bias=_p(self.bias3), H=self.sizes[-1], C=Cn, S=S,
-                          form=L.PREDICT_STACKED if stacked else L.PREDICT_ACCUMULATE, state=_p(state))
-        for k in range(n_chunks):
-            c0 = k * Rc
-            rows = min(Rc, R - c0)
-            xc = x[c0:c0 + rows]
-            a.h, a.ld_h = bufs[nl].x.ptr, bufs[nl].x.ld
+        totals = torch.zeros(p.n_chunks, 4, dtype=torch.float64, device=self.device) if targets is not None else None
+        state = torch.empty(p.Rc, Cn + 3, **f32) if not p.stacked else None
+        h = p.bufs[len(self.vb)].x
+        a = L.PredictArgs(h=h.ptr, ld_h=h.ld, w3=self.w3_s.ptr, ld_w=self.w3_s.ld, bias=_p(self.bias3), H=self.sizes[-1], C=Cn, S=S,
+                          form=L.PREDICT_STACKED if p.stacked else L.PREDICT_ACCUMULATE, state=_p(state))
+        for k, c0, rows, xc in self._chunks(p):
             a.R = rows
-            a.target = C.c_void_p(targets.data_ptr() + 4 * c0) if targets is not None else None
-            a.totals = C.c_void_p(totals[k].data_ptr()) if totals is not None else None
-            for name, t in (("probs", res.probs), ("log_probs", res.log_probs)):
-                setattr(a, name, C.c_void_p(t.data_ptr() + 4 * Cn * c0))
-            for name, t in (("entropy", res.entropy), ("expected_entropy", res.expected_entropy), ("mutual_info", res.mutual_info),
-                            ("pred", res.pred)):
-                setattr(a, name, C.c_void_p(t.data_ptr() + 4 * c0))
-            if stacked:                        # every draw in one pass: the chunk stacked S times as rows, draw s = rows [s rows, (s+1) rows)
-                if wts is not None:            # (weight noise: S = 1)
-                    self._predict_wn_sample(wts, None if map else d0)
-                self._predict_forward(bufs, wts, xc, S * rows, rows if S > 1 else 0, d0, row0 + c0, lrt)
+            a.target = _off(targets, c0)
+            a.totals = _p(totals[k]) if totals is not None else None
+            a.probs, a.log_probs = _off(res.probs, Cn * c0), _off(res.log_probs, Cn * c0)
+            a.entropy, a.expected_entropy, a.mutual_info = _off(res.entropy, c0), _off(res.expected_entropy, c0), _off(res.mutual_info, c0)
+            a.pred = _off(res.pred, c0)
+            if p.stacked:                      # every draw in one pass
+                self._draw_forward(p, xc, rows, c0)
                 L.check(lib.vbnn_head_predict(ctx, code, C.byref(a)))
                 continue
             for s in range(S):                 # one draw per forward, the running state between the head's launches
-                if wts is not None:
-                    self._predict_wn_sample(wts, d0 + s)
-                self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
+                self._draw_forward(p, xc, rows, c0, s)
                 a.first, a.final = int(s == 0), int(s == S - 1)
                 L.check(lib.vbnn_head_predict(ctx, code, C.byref(a)))
-        self._consume_draws(S, map)
-        if totals is not None:
-            tot = _chunk_sums(totals)
-            res.totals = tot
-            res.nll, res.accuracy = tot[0] / R, 100.0 * tot[1] / R
-            res.mean_draw_nll, res.mean_draw_accuracy = tot[2] / (R * S), 100.0 * tot[3] / (R * S)
-        res.S, res.stacked, res.chunks = S, stacked, n_chunks
-        return res
+        self._consume_draws(S, p.map)
+        self._class_moments_finish(res, totals, R, S, 0)
+        return _stamp(res, S, p.stacked, p.n_chunks)
 
     def _predict_stacked(self, R, S, lrt):
         """opt.predict_stacked: True / False / "auto" (default). Weight noise draws a weight matrix per draw: sequential always.
@@ -227,28 +287,29 @@ class _Predictive:
         rows = min(R, max(1, int(self.opt.get("predict_rows", 32768))))
         return rows * max(v.I * v.O for v in self.vb) < (1 << 32)
 
+    def _pingpong(self, n_layers, make):
+        """Activation buffers for the first n_layers VB layers, one ping-pong PAIR per width: layer li writes slot (O, li % 2), so
+        a layer never overwrites its own input and a buffer always holds one layout (its pads stay zero). Returns
+        [the input's buffer, layer 0's output, layer 1's, ...], each built by make(cols) on its slot's first use."""
+        slots, out = {}, []
+        for key in [(self.sizes[0], "in")] + [(v.O, li % 2) for li, v in enumerate(self.vb[:n_layers])]:
+            if key not in slots:
+                slots[key] = make(key[0])
+            out.append(slots[key])
+        return out
+
     def _predict_buffers(self, rows, lrt):
-        """predict's operands: the packed input, then one ping-pong PAIR of activation (+ square) buffers per hidden width --
-        layer li writes slot (O, li % 2), so a layer never overwrites its own input and a buffer always holds one layout (its
-        pads stay zero). bufs[li] is layer li's input, bufs[len(vb)] the head's. Kept across calls while the row count holds."""
+        """predict's operands (_pingpong): bufs[li] is layer li's input, bufs[len(vb)] the head's; x, and x2 (its square) where a
+        layer reads one. Kept across calls while the row count holds."""
         sq = lrt and self.dtype == "bf16"                       # (fp32: the forward forms x.x from x itself)
         key = (rows, sq)
         if self._pred_key != key:
             self._pred_bufs, self._pred_key = None, None
             dev, tdt, nl = self.device, self.tdt, len(self.vb)
-            slots = {}
-
-            def slot(cols, parity, square):
-                b = slots.get((cols, parity))
-                if b is None:
-                    b = slots[(cols, parity)] = _VB()
-                    b.x, b.x2 = _Packed(rows, cols, tdt, dev), None
-                if square and b.x2 is None:
-                    b.x2 = _Packed(rows, cols, tdt, dev)
-                return b
-            bufs = _PredictBuffers([slot(self.sizes[0], "in", sq)])
-            for li, v in enumerate(self.vb):
-                bufs.append(slot(v.O, li % 2, sq and li < nl - 1))
+            bufs = _PredictBuffers(self._pingpong(nl, lambda cols: types.SimpleNamespace(x=_Packed(rows, cols, tdt, dev), x2=None)))
+            if sq:                                              # (every VB layer reads its input's square; the head reads none)
+                for b in bufs[:nl]:
+                    b.x2 = b.x2 or _Packed(rows, b.x.cols, tdt, dev)
             bufs.r = _Packed(rows, max(v.O for v in self.vb), tdt, dev) if sq else None
             self._pred_bufs, self._pred_key = bufs, key
         return self._pred_bufs
@@ -320,19 +381,10 @@ class _Predictive:
         D = Wd // 2 if gauss else Wd
         if gauss and noise_var is not None:
             raise ValueError(f"{what}: criterion = 'gauss' predicts its own noise variance (noise_var must be None)")
-        if noise_var is not None:
-            noise_var = float(noise_var)
-            if not (noise_var > 0.0 and math.isfinite(noise_var)):
-                raise ValueError(f"{what}: noise_var = {noise_var} (a finite variance above zero, or None)")
-        if targets is not None:                # (before the plan, as predict)
-            R = inputs.shape[0]
-            if gauss and tuple(targets.shape) != (R, D):
-                raise ValueError(f"{what}: targets of shape {tuple(targets.shape)} (criterion = 'gauss' takes R x D = "
-                                 f"{R} x {D}: one target per mean)")
-            assert targets.dtype == torch.float32 and targets.is_cuda and tuple(targets.shape) == (R, D)
-            targets = targets.contiguous()
+        noise_var = _check_noise_var(what, noise_var)
+        targets = _check_regression_targets(what, targets, inputs.shape[0], D)      # (D: one target per mean; before the plan, as predict)
         p = self._predictive_plan(what, inputs, S, map, row0, max_S)
-        R, S, map, stacked, Rc, n_chunks = p.R, p.S, p.map, p.stacked, p.Rc, p.n_chunks
+        R, S = p.R, p.S
         f32 = dict(dtype=torch.float32, device=self.device)
         has_t = targets is not None
         res = RegressionPredictResult(torch.empty(R, D, **f32), torch.empty(R, D, **f32), torch.empty(R, **f32),
@@ -341,9 +393,9 @@ class _Predictive:
                                       torch.empty(S, R, Wd, **f32) if keep_draws else None)
         if gauss:
             res.noise_var, res.row_noise_var = torch.empty(R, D, **f32), torch.empty(R, **f32)
-        one_call = stacked and D <= (L.GAUSS_MOMENTS_STACKED_MAX_D if gauss else L.MOMENTS_STACKED_MAX_D)   # else: ACCUMULATE per draw
-        state = None if one_call else torch.empty(Rc, (3 if gauss else 2) * D + 2, **f32)
-        totals = torch.zeros(n_chunks, 5 if gauss else 4, dtype=torch.float64, device=self.device) if has_t else None
+        one_call = p.stacked and D <= (L.GAUSS_MOMENTS_STACKED_MAX_D if gauss else L.MOMENTS_STACKED_MAX_D)   # else: ACCUMULATE per draw
+        state = None if one_call else torch.empty(p.Rc, (3 if gauss else 2) * D + 2, **f32)
+        totals = torch.zeros(p.n_chunks, 5 if gauss else 4, dtype=torch.float64, device=self.device) if has_t else None
         form = L.MOMENTS_STACKED if one_call else L.MOMENTS_ACCUMULATE
         if gauss:
             a = L.GaussMomentsArgs(ld_y=Wd, ld_t=D, D=D, S=S, form=form, s_min=self.logvar_clamp[0], s_max=self.logvar_clamp[1],
@@ -356,14 +408,14 @@ class _Predictive:
         def point(c0, rows):                   # the chunk's targets and outputs
             a.R = rows
             a.target = _off(targets, c0 * D)
-            a.totals = C.c_void_p(totals[c0 // Rc].data_ptr()) if has_t else None
+            a.totals = _p(totals[c0 // p.Rc]) if has_t else None
             a.mean, a.var = _off(res.mean, c0 * D), _off(res.var, c0 * D)
             a.row_var, a.row_sq_err, a.row_log_lik = _off(res.row_var, c0), _off(res.row_sq_err, c0), _off(res.row_log_lik, c0)
             if gauss:
                 a.noise_var, a.row_noise_var = _off(res.noise_var, c0 * D), _off(res.row_noise_var, c0)
 
         self._moments_loop(p, Wd, res.draws, keep_draws, one_call, a, lambda: L.check(moments(ctx, C.byref(a))), point)
-        self._consume_draws(S, map)
+        self._consume_draws(S, p.map)
         if has_t:
             tot = _chunk_sums(totals)
             res.totals = tot
@@ -374,8 +426,7 @@ class _Predictive:
                 res.mean_draw_mse = tot[1] / (R * S * D)
             res.log_lik = tot[2] / R if (gauss or noise_var is not None) else None
             res.mean_var = tot[3] / (R * D)
-        res.S, res.stacked, res.chunks = S, stacked, n_chunks
-        return res
+        return _stamp(res, S, p.stacked, p.n_chunks)
 
     # ---- the regression predictive's quantiles (vbnn_predict_quantiles): predict_regression's pass with the draws kept, then ONE
     # launch over all rows of them -- per output the quantiles of the S-component mixture, and with targets the probability
@@ -439,27 +490,22 @@ class _Predictive:
         matrices are not stored (probs / log_probs None) -- the per-row uncertainties, pred and the top K only. keep_draws: the
         S x R x C logits are returned too. Returns a PredictResult of this rank's rows (no collective, as test())."""
         lib, ctx = L.lib(), self.ctx.h
-        Cn, K = self.n_classes, int(topk)
+        Cn = self.n_classes
         if self.criterion != "nll":
             raise ValueError(f"predict_classes: a class-probability predictive needs the NLL criterion (criterion = "
                              f"'{self.criterion}' has none: use predict_regression)")
-        if not 0 <= K <= min(L.CLASS_MOMENTS_MAX_K, Cn):
-            raise ValueError(f"predict_classes: topk = {K} (0 .. {L.CLASS_MOMENTS_MAX_K}, and at most n_classes = {Cn})")
-        if targets is not None:                # (before the plan, as predict)
-            assert targets.dtype == torch.int32 and targets.is_cuda and targets.numel() == inputs.shape[0]
-            targets = targets.contiguous()
+        K = _check_topk("predict_classes", topk, Cn)
+        targets = _check_class_targets("predict_classes", targets, inputs.shape[0])     # (before the plan, as predict)
         p = self._predictive_plan("predict_classes", inputs, S, map, row0)
-        R, S, map, stacked, Rc, n_chunks = p.R, p.S, p.map, p.stacked, p.Rc, p.n_chunks
-        one_call = stacked and Cn <= L.CLASS_MOMENTS_STACKED_MAX_C       # else: ACCUMULATE per draw
-        res, a, totals, point, _state = self._class_moments_plan(R, S, Rc, n_chunks, one_call, targets, K, keep_probs)
+        one_call = p.stacked and Cn <= L.CLASS_MOMENTS_STACKED_MAX_C     # else: ACCUMULATE per draw
+        res, a, totals, point, _state = self._class_moments_plan(p.R, p.S, p.Rc, p.n_chunks, one_call, targets, K, keep_probs)
         if keep_draws:
-            res.draws = torch.empty(S, R, Cn, dtype=torch.float32, device=self.device)
+            res.draws = torch.empty(p.S, p.R, Cn, dtype=torch.float32, device=self.device)
         self._moments_loop(p, Cn, res.draws, keep_draws, one_call, a,
                            lambda: L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a))), point)
-        self._consume_draws(S, map)
-        self._class_moments_finish(res, totals, R, S, K)
-        res.S, res.stacked, res.chunks = S, stacked, n_chunks
-        return res
+        self._consume_draws(p.S, p.map)
+        self._class_moments_finish(res, totals, p.R, p.S, K)
+        return _stamp(res, p.S, p.stacked, p.n_chunks)
 
     def _class_moments_plan(self, R, S, Rc, n_chunks, one_call, targets, K, keep_probs):
         """What predict_classes and predict_analytic set up for vbnn_predict_class_moments over R rows in n_chunks chunks of Rc:
@@ -482,7 +528,7 @@ class _Predictive:
         def point(c0, rows):                   # the chunk's targets and outputs
             a.R = rows
             a.target = _off(targets, c0)
-            a.totals = C.c_void_p(totals[c0 // Rc].data_ptr()) if has_t else None
+            a.totals = _p(totals[c0 // Rc]) if has_t else None
             a.probs, a.log_probs = _off(res.probs, c0 * Cn), _off(res.log_probs, c0 * Cn)
             a.entropy, a.expected_entropy, a.mutual_info = _off(res.entropy, c0), _off(res.expected_entropy, c0), _off(res.mutual_info, c0)
             a.pred, a.topk_idx, a.topk_prob = _off(res.pred, c0), _off(res.topk_idx, c0 * K), _off(res.topk_prob, c0 * K)
@@ -507,30 +553,19 @@ class _Predictive:
         entry point on `a` (its y / draw set here) after `point(c0, rows)` has aimed it at the chunk; one STACKED call
         (one_call), or a call per draw on the running state."""
         lib, ctx, code = L.lib(), self.ctx.h, self.code
-        x, R, S, map, row0, lrt = p.x, p.R, p.S, p.map, p.row0, p.lrt
-        stacked, Rc, n_chunks, op_rows, bufs, wts, d0 = p.stacked, p.Rc, p.n_chunks, p.op_rows, p.bufs, p.wts, p.d0
-        nl, H = len(self.vb), self.sizes[-1]
-        direct = keep_draws and (not stacked or n_chunks == 1)      # the final Linear writes into draws itself
-        ybuf = None
-        if not direct:                                               # the y buffer: kept with the predict buffers
-            ybuf = bufs.y_reg
-            if ybuf is None or tuple(ybuf.shape) != (op_rows, Wd):
-                ybuf = bufs.y_reg = torch.empty(op_rows, Wd, dtype=torch.float32, device=self.device)
+        S, bufs = p.S, p.bufs
+        direct = keep_draws and (not p.stacked or p.n_chunks == 1)  # the final Linear writes into draws itself
+        if not direct and (bufs.y_reg is None or tuple(bufs.y_reg.shape) != (p.op_rows, Wd)):     # the y buffer: kept with the predict buffers
+            bufs.y_reg = torch.empty(p.op_rows, Wd, dtype=torch.float32, device=self.device)
+        ybuf = None if direct else bufs.y_reg
 
         def final_linear(N, y_ptr):
-            fa = L.FwdArgs(w=self.w3_s.ptr, w2=None, x=bufs[nl].x.ptr, x2=None, ld_w=self.w3_s.ld, ld_x=bufs[nl].x.ld,
-                           N=N, I=H, O=Wd, bias=_p(self.bias3), y=y_ptr, ld_y=Wd)
-            L.check(lib.vbnn_forward(ctx, code, C.byref(fa)))
+            _gemm(lib, ctx, code, self.w3_s, bufs[len(self.vb)].x, N, self.sizes[-1], Wd, _p(self.bias3), y_ptr, Wd)
 
-        for k in range(n_chunks):
-            c0 = k * Rc
-            rows = min(Rc, R - c0)
-            xc = x[c0:c0 + rows]
+        for _, c0, rows, xc in self._chunks(p):
             point(c0, rows)
-            if stacked:                        # every draw in one forward: draw s = rows [s rows, (s+1) rows) of y
-                if wts is not None:
-                    self._predict_wn_sample(wts, None if map else d0)
-                self._predict_forward(bufs, wts, xc, S * rows, rows if S > 1 else 0, d0, row0 + c0, lrt)
+            if p.stacked:                      # every draw in one forward: draw s = rows [s rows, (s+1) rows) of y
+                self._draw_forward(p, xc, rows, c0)
                 y = draws if direct else ybuf
                 final_linear(S * rows, _p(y))
                 if one_call:
@@ -544,10 +579,8 @@ class _Predictive:
                     draws[:, c0:c0 + rows].copy_(ybuf[:S * rows].view(S, rows, Wd))
                 continue
             for s in range(S):                 # one draw per forward, the running moments in `state` between the launches
-                if wts is not None:
-                    self._predict_wn_sample(wts, d0 + s)
-                self._predict_forward(bufs, wts, xc, rows, 0, d0 + s, row0 + c0, lrt, pack=(s == 0))
-                yp = _off(draws, (s * R + c0) * Wd) if direct else _p(ybuf)
+                self._draw_forward(p, xc, rows, c0, s)
+                yp = _off(draws, (s * p.R + c0) * Wd) if direct else _p(ybuf)
                 final_linear(rows, yp)
                 a.y, a.draw = yp, s
                 call()
@@ -558,12 +591,7 @@ class _Predictive:
         """K-major operands of the sparse forward: T[0] the packed input's transpose, T[li + 1] layer li's hT (ping-pong per
         hidden width, as _predict_buffers). Kept across calls while the row count holds."""
         if self._sparse_key != rows:
-            slots = {}
-            T = [_Packed(self.sizes[0], rows, self.tdt, self.device)]
-            for li, v in enumerate(self.vb[:-1]):
-                if (v.O, li % 2) not in slots:
-                    slots[(v.O, li % 2)] = _Packed(v.O, rows, self.tdt, self.device)
-                T.append(slots[(v.O, li % 2)])
+            T = self._pingpong(len(self.vb) - 1, lambda cols: _Packed(cols, rows, self.tdt, self.device))
             self._sparse_bufs, self._sparse_key = T, rows
         return self._sparse_bufs
 
@@ -608,7 +636,6 @@ class _Predictive:
         criterion = "gauss" is refused (the clamp on the log variance makes its moments a separate piece of work). Both modes;
         dense pruned views, held masks and compact networks work through the operand shadows; compressed views are refused.
         Chunked by opt.predict_rows. Returns this rank's rows (no collective)."""
-        lib, ctx, code = L.lib(), self.ctx.h, self.code
         what = "predict_analytic"
         if self.criterion == "gauss":
             raise ValueError(f"{what}: criterion = 'gauss' is not supported -- the clamp on the log variance makes the moments of "
@@ -616,113 +643,94 @@ class _Predictive:
         if isinstance(self._pruned, SparsePruneResult):
             raise ValueError(f"{what}: a compressed pruned view is not supported (use the dense PruneResult it was compressed "
                              "from, or predict / predict_regression)")
-        nll = self.criterion == "nll"
-        Wd, K = self.n_classes, int(topk)
-        if inputs.dim() < 2 or inputs.shape[0] < 1 or inputs.numel() != inputs.shape[0] * self.sizes[0]:
-            raise ValueError(f"{what}: inputs of shape {tuple(inputs.shape)} (R x {self.sizes[0]}, R >= 1)")
-        x = inputs.reshape(inputs.shape[0], -1)
-        if x.dtype != torch.float32 or not x.is_cuda:
-            raise ValueError(f"{what}: inputs are fp32 device tensors")
-        R = x.shape[0]
-        if nll:
+        R = inputs.shape[0]
+        if self.criterion == "nll":
             if noise_var is not None:
                 raise ValueError(f"{what}: noise_var belongs to the regression predictive (criterion = 'nll')")
-            if not 0 <= K <= min(L.CLASS_MOMENTS_MAX_K, Wd):
-                raise ValueError(f"{what}: topk = {K} (0 .. {L.CLASS_MOMENTS_MAX_K}, and at most n_classes = {Wd})")
-            S = int(self.opt["testSamples"] if S is None else S)
-            if S < 1:
-                raise ValueError(f"{what}: S = {S} draws (at least one)")
-            if targets is not None:
-                if targets.dtype != torch.int32 or not targets.is_cuda or targets.numel() != R:
-                    raise ValueError(f"{what}: targets of shape {tuple(targets.shape)} (R = {R} int32 class indices on the device)")
-                targets = targets.contiguous()
-        else:
-            if K:
-                raise ValueError(f"{what}: topk belongs to the class predictive (criterion = 'mse')")
-            if S is not None or row0 is not None:
-                raise ValueError(f"{what}: S and row0 address the class predictive's logit draws (criterion = 'mse' draws nothing)")
-            if noise_var is not None:
-                noise_var = float(noise_var)
-                if not (noise_var > 0.0 and math.isfinite(noise_var)):
-                    raise ValueError(f"{what}: noise_var = {noise_var} (a finite variance above zero, or None)")
-            if targets is not None:
-                if targets.dtype != torch.float32 or not targets.is_cuda or tuple(targets.shape) != (R, Wd):
-                    raise ValueError(f"{what}: targets of shape {tuple(targets.shape)} (R x D = {R} x {Wd} fp32 on the device)")
-                targets = targets.contiguous()
-        row0 = self.rank * R if row0 is None else int(row0)
-        if not self._shadows_ready:
-            self.prepare()
-        if self._pruned is not None and self._pruned.version != self._pver:
-            raise RuntimeError(f"{what}: the pruned view was taken from older parameters (update / prepare / init_parameters "
-                               "ran since): prune() again, or use_pruned(None)")
+            K = _check_topk(what, topk, self.n_classes)
+            S = _check_draws(what, int(self.opt["testSamples"] if S is None else S))
+            return self._analytic_classes(what, inputs, _check_class_targets(what, targets, R), S, row0, K, keep_probs)
+        if int(topk):
+            raise ValueError(f"{what}: topk belongs to the class predictive (criterion = 'mse')")
+        if S is not None or row0 is not None:
+            raise ValueError(f"{what}: S and row0 address the class predictive's logit draws (criterion = 'mse' draws nothing)")
+        noise_var = _check_noise_var(what, noise_var)
+        return self._analytic_regression(what, inputs, _check_regression_targets(what, targets, R, self.n_classes), noise_var)
+
+    def _analytic_plan(self, what, inputs, row0):
+        """predict_analytic's plan: _predictive_inputs, the chunks (Rc rows each: nothing is stacked), the squared operands and the
+        buffers of its own -- none of predict's."""
+        x, R, row0 = self._predictive_inputs(what, inputs, row0)
         ops = self._analytic_operands()
         Rc = max(1, min(R, int(self.opt.get("predict_rows", 32768))))
-        n_chunks = (R + Rc - 1) // Rc
-        B = self._analytic_buffers(Rc)
+        return types.SimpleNamespace(x=x, R=R, row0=row0, Rc=Rc, n_chunks=(R + Rc - 1) // Rc, ops=ops, B=self._analytic_buffers(Rc))
+
+    def _propagate(self, B, ops, xc, rows, mean_ptr, var_ptr):
+        """The chunk's output mean and variance (rows x n_classes fp32 each) from its inputs xc: the moments through every layer."""
+        lib, ctx, code = L.lib(), self.ctx.h, self.code
+        nl, gemm = len(self.vb), functools.partial(_gemm, lib, ctx, code)
+        b0 = B.act[0]
+        L.check(lib.vbnn_pack_input(ctx, code, _p(xc), xc.stride(0), rows, self.sizes[0], b0.a.ptr, b0.q.ptr, b0.a.ld,
+                                    None, None, 0, 0))
+        for li, v in enumerate(self.vb):
+            xin, out, ld = B.act[li], B.act[li + 1], L.pad_ld(v.O)
+            gemm(ops.mu[li], xin.a, rows, v.I, v.O, _p(v.bias), _p(B.m), ld)
+            gemm(ops.var[li], xin.q, rows, v.I, v.O, None, _p(B.v1), ld)
+            if li > 0:                                           # (the first layer's input is deterministic: c = 0)
+                gemm(ops.mu2[li], xin.c, rows, v.I, v.O, None, _p(B.v2), ld)
+            ra = L.ReluMomentsArgs(m=_p(B.m), ld_m=ld, v1=_p(B.v1), v2=_p(B.v2) if li > 0 else None, ld_v=ld, N=rows, O=v.O,
+                                   a=out.a.ptr, q=out.q.ptr if li < nl - 1 else None, c=out.c.ptr, ld_out=out.a.ld)
+            L.check(lib.vbnn_relu_moments(ctx, code, C.byref(ra)))
+        H, Wd = self.sizes[-1], self.n_classes
+        gemm(self.w3_s, B.act[nl].a, rows, H, Wd, _p(self.bias3), mean_ptr, Wd)
+        gemm(ops.w3sq, B.act[nl].c, rows, H, Wd, None, var_ptr, Wd)
+
+    def _analytic_regression(self, what, inputs, targets, noise_var):
+        """predict_analytic, criterion "mse": the propagated mean and variance, finished with torch on the R x D outputs."""
+        p = self._analytic_plan(what, inputs, None)
+        R, Wd = p.R, self.n_classes
         f32 = dict(dtype=torch.float32, device=self.device)
-        nl, H = len(self.vb), self.sizes[-1]
+        res = RegressionPredictResult(torch.empty(R, Wd, **f32), torch.empty(R, Wd, **f32), None, None, None, None)
+        for _, c0, rows, xc in self._chunks(p):
+            self._propagate(p.B, p.ops, xc, rows, _off(res.mean, c0 * Wd), _off(res.var, c0 * Wd))
+        res.row_var = res.var.mean(dim=1)
+        if targets is not None:
+            d2 = (targets - res.mean) ** 2
+            res.row_sq_err = d2.sum(dim=1)
+            if noise_var is not None:
+                tv = res.var + noise_var
+                res.row_log_lik = (-0.5 * (torch.log(6.2831855 * tv) + d2 / tv)).sum(dim=1)
+            sq, vs = float(res.row_sq_err.double().sum()), float(res.var.double().sum())
+            ll = float(res.row_log_lik.double().sum()) if noise_var is not None else 0.0
+            res.totals = [sq, sq + vs, ll, vs]
+            res.mse, res.mean_var = sq / (R * Wd), vs / (R * Wd)
+            res.mean_draw_mse = (sq + vs) / (R * Wd)
+            res.log_lik = ll / R if noise_var is not None else None
+        return _stamp(res, 0, None, p.n_chunks)
 
-        def gemm(w, xin, N, I, O, bias, y, ld_y):                # one single product of vbnn_forward: y = x w^T (+ b), fp32 out
-            fa = L.FwdArgs(w=w.ptr, w2=None, x=xin.ptr, x2=None, ld_w=w.ld, ld_x=xin.ld, N=N, I=I, O=O, bias=bias, y=y, ld_y=ld_y)
-            L.check(lib.vbnn_forward(ctx, code, C.byref(fa)))
-
-        def propagate(xc, rows, mean_ptr, var_ptr):              # the chunk's output mean and variance (rows x Wd fp32 each)
-            b0 = B.act[0]
-            L.check(lib.vbnn_pack_input(ctx, code, _p(xc), xc.stride(0), rows, self.sizes[0], b0.a.ptr, b0.q.ptr, b0.a.ld,
-                                        None, None, 0, 0))
-            for li, v in enumerate(self.vb):
-                xin, out, ld = B.act[li], B.act[li + 1], L.pad_ld(v.O)
-                mu, var, mu2 = ops.mu[li], ops.var[li], ops.mu2[li]
-                gemm(mu, xin.a, rows, v.I, v.O, _p(v.bias), _p(B.m), ld)
-                gemm(var, xin.q, rows, v.I, v.O, None, _p(B.v1), ld)
-                if li > 0:                                       # (the first layer's input is deterministic: c = 0)
-                    gemm(mu2, xin.c, rows, v.I, v.O, None, _p(B.v2), ld)
-                ra = L.ReluMomentsArgs(m=_p(B.m), ld_m=ld, v1=_p(B.v1), v2=_p(B.v2) if li > 0 else None, ld_v=ld, N=rows, O=v.O,
-                                       a=out.a.ptr, q=out.q.ptr if li < nl - 1 else None, c=out.c.ptr, ld_out=out.a.ld)
-                L.check(lib.vbnn_relu_moments(ctx, code, C.byref(ra)))
-            gemm(self.w3_s, B.act[nl].a, rows, H, Wd, _p(self.bias3), mean_ptr, Wd)
-            gemm(ops.w3sq, B.act[nl].c, rows, H, Wd, None, var_ptr, Wd)
-
-        if not nll:
-            res = RegressionPredictResult(torch.empty(R, Wd, **f32), torch.empty(R, Wd, **f32), None, None, None, None)
-            for k in range(n_chunks):
-                c0 = k * Rc
-                rows = min(Rc, R - c0)
-                propagate(x[c0:c0 + rows], rows, _off(res.mean, c0 * Wd), _off(res.var, c0 * Wd))
-            res.row_var = res.var.mean(dim=1)
-            if targets is not None:
-                d2 = (targets - res.mean) ** 2
-                res.row_sq_err = d2.sum(dim=1)
-                if noise_var is not None:
-                    tv = res.var + noise_var
-                    res.row_log_lik = (-0.5 * (torch.log(6.2831855 * tv) + d2 / tv)).sum(dim=1)
-                sq, vs = float(res.row_sq_err.double().sum()), float(res.var.double().sum())
-                ll = float(res.row_log_lik.double().sum()) if noise_var is not None else 0.0
-                res.totals = [sq, sq + vs, ll, vs]
-                res.mse, res.mean_var = sq / (R * Wd), vs / (R * Wd)
-                res.mean_draw_mse = (sq + vs) / (R * Wd)
-                res.log_lik = ll / R if noise_var is not None else None
-            res.S, res.stacked, res.chunks = 0, None, n_chunks
-            return res
-
+    def _analytic_classes(self, what, inputs, targets, S, row0, K, keep_probs):
+        """predict_analytic, criterion "nll": S draws of the propagated logit distribution (vbnn_logit_draws), finished as
+        predict_classes finishes its forwards' logits (vbnn_predict_class_moments)."""
+        lib, ctx = L.lib(), self.ctx.h
+        p = self._analytic_plan(what, inputs, row0)
+        R, Wd, B = p.R, self.n_classes, p.B
+        f32 = dict(dtype=torch.float32, device=self.device)
         # keep_probs: the draws are returned, written straight into the S x R x C result (one chunk: one STACKED call; more: a call
         # per draw, each read in place). Otherwise they live in the chunk's own S x rows x C buffer, kept with the other buffers.
-        stacked = (n_chunks == 1 or not keep_probs) and Wd <= L.CLASS_MOMENTS_STACKED_MAX_C
-        res, a, totals, point, _state = self._class_moments_plan(R, S, Rc, n_chunks, stacked, targets, K, keep_probs)
+        stacked = (p.n_chunks == 1 or not keep_probs) and Wd <= L.CLASS_MOMENTS_STACKED_MAX_C
+        res, a, totals, point, _state = self._class_moments_plan(R, S, p.Rc, p.n_chunks, stacked, targets, K, keep_probs)
         res.logit_mean, res.logit_var = torch.empty(R, Wd, **f32), torch.empty(R, Wd, **f32)
         if keep_probs:
             res.draws = torch.empty(S, R, Wd, **f32)
-        elif B.y is None or B.y.numel() != S * Rc * Wd:
-            B.y = torch.empty(S * Rc * Wd, **f32)
+        elif B.y is None or B.y.numel() != S * p.Rc * Wd:
+            B.y = torch.empty(S * p.Rc * Wd, **f32)
         d0 = self.draw + 1
-        for k in range(n_chunks):
-            c0 = k * Rc
-            rows = min(Rc, R - c0)
+        for _, c0, rows, xc in self._chunks(p):
             mp, vp = _off(res.logit_mean, c0 * Wd), _off(res.logit_var, c0 * Wd)
-            propagate(x[c0:c0 + rows], rows, mp, vp)
+            self._propagate(B, p.ops, xc, rows, mp, vp)
             y0, stride = (_off(res.draws, c0 * Wd), R * Wd) if keep_probs else (_p(B.y), rows * Wd)
-            da = L.LogitDrawsArgs(m=mp, ld_m=Wd, v=vp, ld_v=Wd, R=rows, C=Wd, S=S, seed=self.seed, layer=nl, draw=d0,
-                                  row0=row0 + c0, y=y0, ld_y=Wd, draw_stride=stride)
+            da = L.LogitDrawsArgs(m=mp, ld_m=Wd, v=vp, ld_v=Wd, R=rows, C=Wd, S=S, seed=self.seed, layer=len(self.vb), draw=d0,
+                                  row0=p.row0 + c0, y=y0, ld_y=Wd, draw_stride=stride)
             L.check(lib.vbnn_logit_draws(ctx, C.byref(da)))
             point(c0, rows)
             if stacked:
@@ -734,8 +742,7 @@ class _Predictive:
                     L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a)))
         self._consume_draws(S, False)
         self._class_moments_finish(res, totals, R, S, K)
-        res.S, res.stacked, res.chunks = S, False, n_chunks
-        return res
+        return _stamp(res, S, False, p.n_chunks)
 
     def _analytic_operands(self):
         """predict_analytic's weight-side operands: mu and sigma^2 as the predictive reads them -- the pruned view's shadows, the
@@ -743,7 +750,7 @@ class _Predictive:
         none) -- and mu^2 and w3^2 squared from them AS THEY ARE (vbnn_square_shadow). Rebuilt when the parameter version or the
         pruned view changes, and after a graph replay (a captured update() changes the shadows without a new version); kept otherwise."""
         key = (self._pver, self._pruned)
-        st = getattr(self, "_ana_ops", None)
+        st = self._ana_ops
         if st is not None and st.key[0] == key[0] and st.key[1] is key[1] and not self._ana_ops_stale:
             return st
         self._ana_ops_stale = False
@@ -773,24 +780,16 @@ class _Predictive:
         """predict_analytic's own buffers for `rows` operand rows: act[li] = layer li's input moments (a, q, c packed; act[0] the
         packed input and its square), one ping-pong pair per hidden width as _predict_buffers; m, v1, v2: the three products'
         fp32 outputs (rows x the widest padded layer). Kept across calls while the row count holds."""
-        st = getattr(self, "_ana_bufs", None)
+        st = self._ana_bufs
         if st is not None and st.rows == rows:
             return st
         dev, tdt, nl = self.device, self.tdt, len(self.vb)
-        slots = {}
-
-        def slot(cols, parity, q, c):
-            b = slots.get((cols, parity))
-            if b is None:
-                b = slots[(cols, parity)] = types.SimpleNamespace(a=_Packed(rows, cols, tdt, dev), q=None, c=None)
-            if q and b.q is None:
-                b.q = _Packed(rows, cols, tdt, dev)
-            if c and b.c is None:
-                b.c = _Packed(rows, cols, tdt, dev)
-            return b
-        act = [slot(self.sizes[0], "in", True, False)]
-        for li, v in enumerate(self.vb):
-            act.append(slot(v.O, li % 2, li < nl - 1, True))
+        act = self._pingpong(nl, lambda cols: types.SimpleNamespace(a=_Packed(rows, cols, tdt, dev), q=None, c=None))
+        for j, b in enumerate(act):                              # q: what a VB layer reads of its input; c: what a layer writes
+            if j < nl:
+                b.q = b.q or _Packed(rows, b.a.cols, tdt, dev)
+            if j > 0:
+                b.c = b.c or _Packed(rows, b.a.cols, tdt, dev)
         wide = rows * max(L.pad_ld(v.O) for v in self.vb)
         f32 = dict(dtype=torch.float32, device=dev)
         st = types.SimpleNamespace(rows=rows, act=act, m=torch.zeros(wide, **f32), v1=torch.zeros(wide, **f32), v2=torch.zeros(wide, **f32),
