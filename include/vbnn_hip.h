@@ -70,6 +70,29 @@ const char* vbnn_last_error(void);
                                          whenever the operands allow it (also at sizes whose partial sums the tile form finishes in-launch) */
 #define VBNN_DEBUG_KMAJOR 6        /* K-major operands (gemm_v3.h AK / BK): 1 = use when the shape allows (default), 0 = never, 2 = gemm_v3 only */
 int vbnn_debug_set(int key, int value);
+/* The read side of the hook (additive, ABI 6). VBNN_DEBUG_LAST_HEAD_FORM: which form of the classifier head the LAST head call
+ * of this process launched (vbnn_head_forward, vbnn_head_forward_slots, vbnn_head_backward, vbnn_head_forward_backward;
+ * PROCESS-wide and host-side: written where the launch is chosen, nothing on the device), 0 before the first. A call that is
+ * two launches (vbnn_head_forward_backward outside its one-launch sizes) leaves the form of its second, the backward. The value:
+ *   bits 0-3   the entry: VBNN_HEAD_ENTRY_FORWARD (k_head_forward), _SLOTS (k_head_from_slots), _STEP (the one-launch
+ *              forward + backward), _TILE (the 64 x 64 tile backward), _STREAM (the streaming backward)
+ *   bit  4     the operand type: 0 = f32, 1 = bf16
+ *   bit  5     VEC  (tile backward: 16-byte accesses)      bit 6   FULL (tile backward: whole tiles, no bounds checks)
+ *   bits 8-15  CP   (tile backward: classes of the final weight kept in registers, 12 or 0)
+ *   bits 16-17 the finish of the row-chunk partial sums: VBNN_HEAD_FINISH_NONE (a forward, or no sum asked for),
+ *              _INLINE (the last arriver of the launch), _KERNEL (k_head_backward_finish follows)
+ * Any other key: -1. Nothing here changes what is launched. */
+#define VBNN_DEBUG_LAST_HEAD_FORM 11
+#define VBNN_HEAD_ENTRY_FORWARD 1
+#define VBNN_HEAD_ENTRY_SLOTS 2
+#define VBNN_HEAD_ENTRY_STEP 3
+#define VBNN_HEAD_ENTRY_TILE 4
+#define VBNN_HEAD_ENTRY_STREAM 5
+#define VBNN_HEAD_FINISH_NONE 0
+#define VBNN_HEAD_FINISH_INLINE 1
+#define VBNN_HEAD_FINISH_KERNEL 2
+#define VBNN_HEAD_FORM(entry, bf16, vec, full, cp, finish) ((entry) | ((bf16) << 4) | ((vec) << 5) | ((full) << 6) | ((cp) << 8) | ((finish) << 16))
+int vbnn_debug_get(int key);
 
 /* 1 when a GEMM with an M x N output and contraction length K would take the K-major form of the two-pass kernel
  * under the current selection (whole 256 x 256 tiles filling the CUs, K a multiple of 64, bf16): the host asks once
@@ -569,7 +592,9 @@ int vbnn_relu_backward(vbnn_ctx* ctx, const float* x, const float* g, float* gx,
  *   out = logsoftmax(logits); loss_sum_dev[0] += -sum_n out[n][t_n] * inv_n;
  *   correct_dev[0] += #rows whose arg-max equals the target (utils.lua:11-27);
  *   g_logits = (exp(out) - onehot) * inv_n     (= LogSoftMax:backward(ClassNLL:backward)).
- * inv_n = 1 / (global minibatch rows). Targets are 0-based int32. */
+ * inv_n = 1 / (global minibatch rows). Targets are 0-based int32. A target outside [0, C - 1] is clamped into it (a negative
+ * one counts as class 0, one past the end as class C - 1) for the loss, the gradient and the hit count alike: such a row
+ * is never read out of bounds and is never dropped. Of equal maxima the first (lowest class) is the arg-max. */
 int vbnn_logsoftmax_nll(vbnn_ctx* ctx, const float* logits, int64_t ld, const int32_t* target,
                         int64_t N, int64_t C, float inv_n, float* out, float* g_logits,
                         double* loss_sum_dev, int32_t* correct_dev);
@@ -608,7 +633,9 @@ int vbnn_gauss_nll_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const f
  * the hit count are summed in a fixed order inside the launch (bitwise reproducible) and stored to loss_sum_dev[0]
  * / correct_dev[0] when accumulate = 0, added to them when accumulate = 1 (the S draws of a minibatch,
  * mlp.lua:76-84): no memset of the two accumulators is needed. rows_per_draw > 0: stacked draws, row n's target is
- * target[n % rows_per_draw] (`target` holds one minibatch's rows_per_draw entries). */
+ * target[n % rows_per_draw] (`target` holds one minibatch's rows_per_draw entries). A target outside [0, C - 1] is clamped
+ * into it for the loss, g_logits and the hit count, as in vbnn_logsoftmax_nll (the same holds for vbnn_head_forward_slots and
+ * vbnn_head_forward_backward); of equal maxima the first is the arg-max. */
 int vbnn_head_forward(vbnn_ctx* ctx, int dtype, const void* h, int64_t ld_h, const void* w3, int64_t ld_w,
                       const float* bias, const int32_t* target, int64_t N, int64_t H, int64_t C, float inv_n,
                       float* logits, float* out, float* g_logits, int accumulate, double* loss_sum_dev,
@@ -1091,7 +1118,9 @@ int vbnn_unit_gather(vbnn_ctx* ctx, const vbnn_unit_gather_args* a);
 int vbnn_digest(vbnn_ctx* ctx, const void* buf, uint64_t n_words, uint64_t index0, uint64_t* out);
 
 /* The same criterion as separate modules, for the module-level call order of mlp.lua:77-80:
- * nn.LogSoftMax:updateOutput is vbnn_logsoftmax_nll with g_logits = loss = correct = NULL. */
+ * nn.LogSoftMax:updateOutput is vbnn_logsoftmax_nll with g_logits = loss = correct = NULL. Both clamp a target outside
+ * [0, C - 1] into it, as vbnn_logsoftmax_nll does: the row that vbnn_nll_forward charges to class 0 or C - 1 gets its
+ * gradient -inv_n at that same class from vbnn_nll_backward. loss_sum_dev / correct_dev are ADDED to (the caller clears them). */
 int vbnn_nll_forward(vbnn_ctx* ctx, const float* out, int64_t ld, const int32_t* target, int64_t N, int64_t C,
                      float inv_n, double* loss_sum_dev, int32_t* correct_dev);          /* criterion:forward  */
 int vbnn_nll_backward(vbnn_ctx* ctx, const int32_t* target, int64_t N, int64_t C, float inv_n, float* g); /* :backward */

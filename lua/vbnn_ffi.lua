@@ -15,6 +15,7 @@ typedef struct vbnn_ctx vbnn_ctx;
 int vbnn_abi_version(void);
 const char* vbnn_last_error(void);
 int vbnn_debug_set(int key, int value);
+int vbnn_debug_get(int key);
 int vbnn_kmajor_supported(int64_t M, int64_t N, int64_t K);
 int vbnn_kmajor_supported_dw(int64_t I, int64_t O, int64_t N, int bias_row);
 int vbnn_ctx_kmajor_supported(vbnn_ctx* ctx, int64_t M, int64_t N, int64_t K);

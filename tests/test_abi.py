@@ -32,6 +32,7 @@ def test_library_exports_every_declared_symbol():
     assert sorted(L.exported_symbols()) == names
     L.lib()
     assert L.lib().vbnn_abi_version() == 6
+    assert "vbnn_debug_get" in names and L.lib().vbnn_debug_get(11) >= 0 and L.lib().vbnn_debug_get(0) == -1      # additive: still ABI 6
 
 
 def test_no_gpu_is_an_error_not_a_fallback():

@@ -181,6 +181,7 @@ _SIGS = {
     "vbnn_abi_version": ([], _i),
     "vbnn_last_error": ([], C.c_char_p),
     "vbnn_debug_set": ([_i, _i], _i),
+    "vbnn_debug_get": ([_i], _i),
     "vbnn_kmajor_supported": ([_i64, _i64, _i64], _i),
     "vbnn_kmajor_supported_dw": ([_i64, _i64, _i64, _i], _i),
     "vbnn_ctx_kmajor_supported": ([_vp, _i64, _i64, _i64], _i),

@@ -748,7 +748,7 @@ __global__ __launch_bounds__(256) void k_nll_backward(const int32_t* __restrict_
     const int64_t total = N * C;
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
         const int64_t n = t / C, c = t - n * C;
-        g[t] = (c == (int64_t)target[n]) ? -inv_n : 0.f;
+        g[t] = (c == (int64_t)min(max(target[n], 0), (int32_t)C - 1)) ? -inv_n : 0.f;     // clamped as every forward clamps it
     }
 }
 __global__ __launch_bounds__(256) void k_logsoftmax_backward(const float* __restrict__ out, const float* __restrict__ g, float* gx,

@@ -1202,11 +1202,13 @@ extern "C" int vbnn_head_forward(vbnn_ctx* ctx, int dtype, const void* h, int64_
     unsigned* ticket = ctx->counters + VBNN_CNT_HEAD_FWD;
     if (dtype == VBNN_F32) {
         const int64_t Hp = (H + 15) / 16 * 16;
+        g_last_head_form = VBNN_HEAD_FORM(VBNN_HEAD_ENTRY_FORWARD, 0, 0, 0, 0, VBNN_HEAD_FINISH_NONE);
         hipLaunchKernelGGL(k_head_forward<float>, dim3(nb), dim3(64 * HEAD_FW), 0, ctx->stream, (const float*)h, ld_h, (const float*)w3,
                            ld_w, bias, target, N, Hp, (int)C, inv_n, out, g_logits, logits, loss_sum_dev, correct_dev, accumulate, part_loss,
                            part_corr, ticket, rows_per_draw);
     } else if (dtype == VBNN_BF16) {
         const int64_t Hp = (H + 31) / 32 * 32;
+        g_last_head_form = VBNN_HEAD_FORM(VBNN_HEAD_ENTRY_FORWARD, 1, 0, 0, 0, VBNN_HEAD_FINISH_NONE);
         hipLaunchKernelGGL(k_head_forward<bf16_t>, dim3(nb), dim3(64 * HEAD_FW), 0, ctx->stream, (const bf16_t*)h, ld_h,
                            (const bf16_t*)w3, ld_w, bias, target, N, Hp, (int)C, inv_n, out, g_logits, logits, loss_sum_dev,
                            correct_dev, accumulate, part_loss, part_corr, ticket, rows_per_draw);
@@ -1227,6 +1229,7 @@ extern "C" int vbnn_head_forward_slots(vbnn_ctx* ctx, const float* slots, int64_
     VBNN_REQUIRE((size_t)nb * 2 <= ctx->scratch_doubles, "minibatch too large for the reduction scratch");
     double* part_loss = ctx->scratch;                                       // [nb] doubles, then [nb] ints
     int32_t* part_corr = reinterpret_cast<int32_t*>(ctx->scratch + nb);
+    g_last_head_form = VBNN_HEAD_FORM(VBNN_HEAD_ENTRY_SLOTS, 0, 0, 0, 0, VBNN_HEAD_FINISH_NONE);
     hipLaunchKernelGGL(k_head_from_slots, dim3(nb), dim3(64), 0, ctx->stream, slots, (int)n_slots, bias, target, N, (int)C, inv_n, out,
                        g_logits, logits, loss_sum_dev, correct_dev, accumulate, part_loss, part_corr, ctx->counters + VBNN_CNT_HEAD_FWD,
                        rows_per_draw);
@@ -1345,6 +1348,8 @@ static int head_backward_t(vbnn_ctx* ctx, const T* h, int64_t ld_h, const T* w3,
                                gradBias_prev ? spbp : nullptr, sft, accumulate, gradWeight, gradBias, gradBias_prev)
             // the in-launch finish where the tickets reach (one per column block); VBNN_HEAD_INLINE_FINISH=0: the finish kernel (A/B)
             unsigned* sft = (sums && g_head_inline_finish && cb <= VBNN_CNT_TILES_MAX) ? ctx->counters + VBNN_CNT_TILES : nullptr;
+            g_last_head_form = VBNN_HEAD_FORM(VBNN_HEAD_ENTRY_STREAM, 1, 0, 0, 0,
+                                              !sums ? VBNN_HEAD_FINISH_NONE : sft ? VBNN_HEAD_FINISH_INLINE : VBNN_HEAD_FINISH_KERNEL);
             VBNN_HS_LAUNCH(SU, SWV);
 #undef VBNN_HS_LAUNCH
             if (sums && !sft) {
@@ -1356,7 +1361,10 @@ static int head_backward_t(vbnn_ctx* ctx, const T* h, int64_t ld_h, const T* w3,
             }
         }
     }
-    if (full && C <= 12 && !r_prev)
+    const bool cp12 = full && C <= 12 && !r_prev;
+    g_last_head_form = VBNN_HEAD_FORM(VBNN_HEAD_ENTRY_TILE, sizeof(T) == 2 ? 1 : 0, (vec ? 1 : 0), (full ? 1 : 0), (cp12 ? 12 : 0),
+                                      !sums ? VBNN_HEAD_FINISH_NONE : inline_fin ? VBNN_HEAD_FINISH_INLINE : VBNN_HEAD_FINISH_KERNEL);
+    if (cp12)
         hipLaunchKernelGGL((k_head_backward<T, true, true, 12>), grid, dim3(256), 0, ctx->stream, h, ld_h, w3, ld_w, g_logits, N, H, (int)C,
                            relu_mask, r_prev, r_prev_t, ld_r_prev, g_prev, gv_prev, ld_gp, gT_prev, gvT_prev, ld_gpT, rows_per_chunk,
                            pw, pb, pbp, ft, accumulate, gradWeight, gradBias, gradBias_prev);
@@ -1444,6 +1452,7 @@ extern "C" int vbnn_head_forward_backward(vbnn_ctx* ctx, int dtype, const vbnn_h
     float* partial_b = partial_w + R * C * H;
     float* partial_bp = partial_b + R * C;
     const int64_t Hp = (H + 15) / 16 * 16;
+    g_last_head_form = VBNN_HEAD_FORM(VBNN_HEAD_ENTRY_STEP, 0, 0, 0, 0, VBNN_HEAD_FINISH_INLINE);
     hipLaunchKernelGGL(k_head_step_f32<0>, dim3((unsigned)tiles_c, (unsigned)R), dim3(64 * HEAD_FW), 0, ctx->stream, (const float*)a->h,
                        a->ld_h, (const float*)a->w3, a->ld_w, a->bias, a->target, N, H, Hp, (int)C, a->inv_n, a->rows_per_draw, a->out,
                        a->g_logits, a->logits, a->loss_sum_dev, a->correct_dev, a->accumulate, part_loss, part_corr, a->relu_mask, (const float*)a->r_prev, a->ld_r_prev, (float*)a->g_prev,
