@@ -69,6 +69,8 @@ const char* vbnn_last_error(void);
                                          128-unit x 32-row tiles with a separate finish kernel), 0 = the tile form, 1 = the streaming form
                                          whenever the operands allow it (also at sizes whose partial sums the tile form finishes in-launch) */
 #define VBNN_DEBUG_KMAJOR 6        /* K-major operands (gemm_v3.h AK / BK): 1 = use when the shape allows (default), 0 = never, 2 = gemm_v3 only */
+#define VBNN_DEBUG_V3_FOLD_SERIAL 12  /* the two-pass kernel's LRT forward, the noise fold between its passes: 0 = the software-pipelined
+                                         form (default), 1 = the serial form, one quad at a time (additive; the same bits either way) */
 int vbnn_debug_set(int key, int value);
 /* The read side of the hook (additive, ABI 6). VBNN_DEBUG_LAST_HEAD_FORM: which form of the classifier head the LAST head call
  * of this process launched (vbnn_head_forward, vbnn_head_forward_slots, vbnn_head_backward, vbnn_head_forward_backward;

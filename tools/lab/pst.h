@@ -8,18 +8,24 @@
 // read at the end of the C cluster puts that latency into every slot: both were tried, both bend the picture.)
 //   V3_ST(10) M cluster starts   (11) C cluster starts: behind the M cluster's closing wait + barrier   (12) the C cluster's MFMAs are issued
 //   V3_ST(13) a pass starts      (14) a pass ends (results written by workgroup 8)
+//   V3_ST(5) the fold between the passes starts   (6) it ends: per wave of workgroup 8, in shader cycles (s_memtime) AND in ticks of the
+//   constant 100 MHz counter (s_memrealtime: microseconds without knowing the clock, and the clock from the two), kept per K class
+//   (nk <= 16: the K = 784 forward; longer: the 4096-deep launches) since a step runs both. Stamp 5 is read behind stamp 6's wait.
 #pragma once
 #include <hip/hip_runtime.h>
 static __device__ unsigned long long g_pst[8 * 8];           // [wave]: cycles M start -> C start, C, pass, phases counted
 static __device__ unsigned long long g_pst_raw[8 * 16];      // one K step's stamps as they are: [wave][phase][M start, C start, C end]
+static __device__ unsigned long long g_pst_fold[2 * 8 * 2];  // [nk > 16][wave]: the fold's cycles, its 10 ns ticks
 #define V3_ST_DECL unsigned long long pst_t10 = 0, pst_t11 = 0, pst_t12 = 0, pst_t13 = 0, pst_t14 = 0, pst_p10 = 0, pst_p11 = 0, pst_p12 = 0, \
-    pst_am = 0, pst_ac = 0, pst_ap = 0, pst_n = 0, pst_r0 = 0, pst_r1 = 0, pst_r2 = 0, pst_r3 = 0, pst_r4 = 0, pst_r5 = 0;
+    pst_am = 0, pst_ac = 0, pst_ap = 0, pst_n = 0, pst_r0 = 0, pst_r1 = 0, pst_r2 = 0, pst_r3 = 0, pst_r4 = 0, pst_r5 = 0, \
+    pst_t5 = 0, pst_t6 = 0, pst_u5 = 0, pst_u6 = 0;
 #define V3_ST_S(k) asm volatile("s_memtime %0" : "=s"(pst_t##k)::"memory")
 #define V3_ST_0() V3_ST_DECL
 #define V3_ST_1() do { } while (0)
 #define V3_ST_4() do { } while (0)
-#define V3_ST_5() do { } while (0)
-#define V3_ST_6() do { } while (0)
+#define V3_ST_5() asm volatile("s_memtime %0\n\ts_memrealtime %1" : "=s"(pst_t5), "=s"(pst_u5)::"memory")
+#define V3_ST_6() do { asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(pst_t6), "=s"(pst_u6), "+s"(pst_t5), "+s"(pst_u5)::"memory"); \
+        if (blockIdx.x == 8 && lane == 0) { unsigned long long* f_ = g_pst_fold + ((nk > 16 ? 8 : 0) + wave) * 2; f_[0] = pst_t6 - pst_t5; f_[1] = pst_u6 - pst_u5; } } while (0)
 #define V3_ST_10() V3_ST_S(10)
 // behind the M cluster's lgkmcnt(0): everything stamped before it is readable -- this phase's M start and the phase BEFORE's C start / end
 #define V3_ST_11() do { asm volatile("" : "+s"(pst_t10), "+s"(pst_t11), "+s"(pst_t12)); \
@@ -37,5 +43,10 @@ static __device__ unsigned long long g_pst_raw[8 * 16];      // one K step's sta
 extern "C" __attribute__((visibility("default"))) int PST_READER(unsigned long long* out) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pst), sizeof(g_pst)) != hipSuccess) return 1;
     return (int)hipMemcpyFromSymbol(out + 64, HIP_SYMBOL(g_pst_raw), sizeof(g_pst_raw));
+}
+#define PST_CAT_(a, b) a##b
+#define PST_CAT(a, b) PST_CAT_(a, b)
+extern "C" __attribute__((visibility("default"))) int PST_CAT(PST_READER, _fold)(unsigned long long* out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pst_fold), sizeof(g_pst_fold));
 }
 #endif

@@ -35,6 +35,15 @@ for tu in ("gemm_fwd", "gemm_dx", "gemm_dw"):
             continue
         print(f"  wave {w}: phases {n:4d}  M cluster (start -> C start, with its closing wait and barrier) {am / (n - 1):7.1f}   C cluster (32 MFMAs issued) {ac / (n - 1):7.1f}"
               f"   passes / phases {ap / n:7.1f}")
+    fold = (C.c_ulonglong * 32)()
+    if getattr(lib, "vbnn_lab_pst_" + tu + "_fold")(fold) == 0:
+        # the fold between the passes (V3_ST(5) .. V3_ST(6)), the last launch of each K class: cycles, microseconds (10 ns ticks)
+        for kc, name in ((0, "K <= 1024"), (1, "K  > 1024")):
+            cyc = [fold[(kc * 8 + w) * 2] for w in range(8)]
+            us = [fold[(kc * 8 + w) * 2 + 1] / 100.0 for w in range(8)]
+            if any(cyc):
+                print(f"  fold {name}: us per wave " + " ".join(f"{u:6.2f}" for u in us) + f"   mean {sum(us) / 8:6.2f} us, {sum(cyc) / 8:8.0f} cycles"
+                      f" ({sum(cyc) / max(sum(us), 1e-9) / 1e3:5.2f} GHz)")
     raw = [[buf[64 + w * 16 + k] for k in range(6)] for w in range(8)]
     t00 = min(r[0] for r in raw if r[0])
     print("  one K step, cycles from the first wave's M start: phase 0: M start, C start, C end | phase 1: M start, C start, C end")

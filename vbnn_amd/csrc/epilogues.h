@@ -244,6 +244,41 @@ struct EpiFwd {
         }
         return out;
     }
+    // FOLD_PIPE: fold_s in its two halves, for the staged fold's software pipeline (gemm_v3.h): the Philox words of a quad --
+    // 10 rounds of mad -> bitop3, all integer, four live registers -- and everything that follows from them. The kernel
+    // draws the words of the NEXT group's four quads while this group's staged rows make their trip through LDS, so no LDS
+    // wait is left exposed. fold_z . fold_words is normal4 and fold_sz is fold_s's loop, op for op: the two forms give the
+    // same bits (tests/test_forward_fold_gpu.py holds them against each other).
+    static constexpr int FOLD_PIPE = 1;
+    __device__ __forceinline__ vbnn_u32x4 fold_words(int um, int un, const Lane& ln) const {
+        return vbnn_philox4x32_10((uint32_t)((um + ln.ml) >> 2), (uint32_t)(row0 + un + ln.nl), draw, (layer << 8) | VBNN_STREAM_ZETA,
+                                  (uint32_t)seed, (uint32_t)(seed >> 32));
+    }
+    static __device__ __forceinline__ vbnn_f32x4 fold_z(const vbnn_u32x4& u) {
+        vbnn_f32x4 z;
+#ifndef VBNN_BF16_EXACT_NORMALS
+        if constexpr (sizeof(T) == 2) {
+            vbnn_box_muller_hw(u.v[0], u.v[1], &z.v[0], &z.v[1]);
+            vbnn_box_muller_hw(u.v[2], u.v[3], &z.v[2], &z.v[3]);
+            return z;
+        }
+#endif
+        vbnn_box_muller(u.v[0], u.v[1], &z.v[0], &z.v[1]);
+        vbnn_box_muller(u.v[2], u.v[3], &z.v[2], &z.v[3]);
+        return z;
+    }
+    static __device__ __forceinline__ f32x4 fold_sz(f32x4 v, const f32x4& b4, const vbnn_f32x4& z, float (&rv)[4]) {
+        f32x4 out;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool pos = v[j] > 0.f;
+            const float rs = __builtin_amdgcn_rsqf(v[j]);
+            const float sd = pos ? v[j] * rs : 0.f;
+            out[j] = fmaf(sd, z.v[j], b4[j]);
+            rv[j] = pos ? 0.5f * z.v[j] * rs : 0.f;
+        }
+        return out;
+    }
     struct FPre { f32x4 b; };
     __device__ __forceinline__ FPre fold_load(int um, int un, const Lane& ln) const {
         (void)un;

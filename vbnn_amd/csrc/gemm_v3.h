@@ -35,6 +35,10 @@ constexpr int V3_BTILE = 256 * 128;
 constexpr int V3_LDS = 4 * V3_APART + 3 * V3_BTILE;  // 163840: all of the CU's LDS
 
 inline int g_v3_min_k = 704;        // shortest K the shape selection gives to this kernel (vbnn_debug_set key 4)
+inline int g_v3_fold_serial = 0;    // 1: the forward's fold between the passes in its serial form (vbnn_debug_set key 12)
+// does the functor have the pipelined form of the staged fold (Epi::FOLD_PIPE, epilogues.h)?
+template <class Epi, class = void> struct v3_fold_pipe { static constexpr int value = 0; };
+template <class Epi> struct v3_fold_pipe<Epi, std::void_t<decltype(Epi::FOLD_PIPE)>> { static constexpr int value = Epi::FOLD_PIPE; };
 
 // Stamp hook: a build that wants in-kernel time stamps defines V3_ST(k) before including this file (tools/lab/pst.h: the K step's
 // clusters; tools/lab/ also has r03's); the library does not.
@@ -61,7 +65,9 @@ inline int g_v3_min_k = 704;        // shortest K the shape selection gives to t
 // AT m_dim() is the ones row: edge_row). LDS: A parts as a ring of four (A of step t in part t & 3), B triple-buffered as before.
 // (r02's form of this launch -- full-height tiles, each GEMM split again over two K halves that met through write-through slabs and
 // tickets -- lost to this one, 84 against 68 us in the step, and lives on in tools/lab/ only.)
-template <bool DUAL, bool AK, bool BK, class Epi, bool SPLIT = false, bool HM = false>
+// PIPE: the staged fold of a functor with FOLD_PIPE (EpiFwd) as a software pipeline (1, what the library launches) or in its serial
+// form (0: vbnn_debug_set(VBNN_DEBUG_V3_FOLD_SERIAL, 1); the same bits -- kept for the tests and for A/B).
+template <bool DUAL, bool AK, bool BK, class Epi, bool SPLIT = false, bool HM = false, int PIPE = v3_fold_pipe<Epi>::value>
 __global__ __launch_bounds__(512, 2) void gemm_nt_v3(const bf16_t* __restrict__ A, const bf16_t* __restrict__ A2, int64_t lda,
                                                      const bf16_t* __restrict__ B, const bf16_t* __restrict__ B2, int64_t ldb,
                                                      int M, int N, int nk, int tiles_m, int tiles_n, Epi epi_in) {
@@ -652,6 +658,107 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_v3(const bf16_t* __restrict__ 
             };
             fold_group(std::integral_constant<int, 0>());
             fold_group(std::integral_constant<int, 1>());
+        } else if constexpr (Epi::FOLD_STAGE != 0 && PIPE != 0) {
+            // The staged fold below as a software pipeline over its eight groups g = 4 G + j (m-blocks 4 G .. 4 G + 3 at n-block j;
+            // same tile, same addresses, same arithmetic: Epi::FOLD_PIPE, epilogues.h). The serial form below waits for an LDS
+            // round trip in front of every quad (its bias) and for two more behind every group (the staged rows): 40 exposed
+            // waits per wave. Here the bias quads of four m-blocks come in one batch per G, and per group:
+            //   1  the reads of group g - 1's staged rows are ISSUED
+            //   2  Box-Muller and the fold arithmetic of group g's four quads, four ds_write_b64 (same-wave LDS operations
+            //      complete in order: the writes cannot overtake the reads of 1, the tile needs no second row set)
+            //   3  the Philox words of group g + 1's four quads -- all integer, the words of g are dead by now
+            //   4  ONE s_waitcnt lgkmcnt(0), long since satisfied, and group g - 1's two row stores
+            // The read results and the words are operands of step 4's statement, which pins the words in front of the wait
+            // and keeps the compiler's hands off registers with a read in flight; the coordinates "depend" on each step, as
+            // in the serial form, so that no group's state is hoisted above pass 1 or into its neighbours.
+            // (What did NOT pay, LAB_NOTES.md section 3: the four Philox blocks of a group advanced round by round -- the
+            // same cycles at 16 more registers. The winner of a SIMD's issue arbitration runs at its own issue rate
+            // whatever its chains look like; the fold is bound by issue slots, not by result latency.)
+            typedef typename Epi::fold_st_t ST;
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            static_assert(sizeof(ST) == 2, "staging tile geometry: 64 m x 2 bytes = one 128-byte row segment");
+            constexpr int PITCH = 64 * (int)sizeof(ST) + 16;                   // bytes; 16 rows x 144 B = 2304 B per wave
+            constexpr int WSTG = 16 * PITCH + 512;                             // + the wave's 128 per-m addends (fp32)
+            static_assert(7 * WSTG <= V3_BTILE && WSTG <= V3_APART, "staging tiles must fit the free LDS");
+            const unsigned stg = (unsigned)(uintptr_t)(ldsb_t)(wave < 7 ? lds + 4 * V3_APART + 2 * V3_BTILE + wave * WSTG
+                                                                       : lds + 3 * V3_APART);
+            const unsigned wr_a = stg + fc16 * PITCH + 8 * fq4;                // this lane's 4 m of m-block b: + 32 b
+            int flane = lane;
+            asm volatile("" : "+v"(flane));
+            const unsigned bias_a = stg + 16 * fq4;                            // m-block i: + 16 PITCH + 64 i
+            const unsigned rd_a = stg + (flane >> 3) * PITCH + (flane & 7) * 16;   // row (lane >> 3) (+ 8), m chunk lane & 7
+            ST* const outp = epi.fold_st_ptr();
+            const int64_t old = epi.fold_st_ld();
+            const bool st_stream = epi.fold_st_stream();
+            const unsigned olane = (unsigned)((flane >> 3) * (int)old + (flane & 7) * 8);
+            auto words = [&](auto g_c, u32x4 (&u)[4]) {
+                constexpr int G = decltype(g_c)::value >> 2, j = decltype(g_c)::value & 3;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const vbnn_u32x4 w = epi.fold_words(fm0 + 16 * (4 * G + b), fn0 + 16 * j, fln);
+                    u[b] = u32x4{w.v[0], w.v[1], w.v[2], w.v[3]};
+                }
+            };
+            auto store_rows = [&](auto g_c, const bf16x8& r0, const bf16x8& r1) {
+                constexpr int G = decltype(g_c)::value >> 2, j = decltype(g_c)::value & 3;
+                ST* const row0p = outp + ((int64_t)(fn0 + 16 * j) * old + fm0 + 64 * G);
+                vbnn_store_stream(row0p, olane, r0, st_stream);
+                vbnn_store_stream(row0p + 8 * old, olane, r1, st_stream);
+            };
+            u32x4 uw[4];                                                       // the words of the group about to be folded
+            f32x4 b4[4];                                                       // the bias quads of m-blocks 4 G .. 4 G + 3
+#define V3_FOLD_READ_BIAS(G)                                                                                                        \
+    asm volatile("ds_read_b128 %0, %5 offset:%6\n\tds_read_b128 %1, %5 offset:%7\n\tds_read_b128 %2, %5 offset:%8\n\t"                    \
+                 "ds_read_b128 %3, %5 offset:%9"                                                                                     \
+                 : "=&v"(b4[0]), "=&v"(b4[1]), "=&v"(b4[2]), "=&v"(b4[3]), "+s"(fn0)                                                 \
+                 : "v"(bias_a), "n"(16 * PITCH + 256 * (G)), "n"(16 * PITCH + 256 * (G) + 64), "n"(16 * PITCH + 256 * (G) + 128),    \
+                   "n"(16 * PITCH + 256 * (G) + 192) : "memory")
+            V3_FOLD_READ_BIAS(0);
+            words(std::integral_constant<int, 0>(), uw);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(b4[0]), "+v"(b4[1]), "+v"(b4[2]), "+v"(b4[3]),
+                         "+v"(uw[0]), "+v"(uw[1]), "+v"(uw[2]), "+v"(uw[3]), "+s"(fn0), "+s"(fm0) :: "memory");
+            vbnn_static_for<0, 8>([&](auto g_c) {
+                constexpr int g = decltype(g_c)::value, G = g >> 2, j = g & 3;
+                [[maybe_unused]] bf16x8 r0, r1;
+                [[maybe_unused]] u32x4 un[4];
+                if constexpr (g > 0)
+                    asm volatile("ds_read_b128 %0, %3\n\tds_read_b128 %1, %3 offset:%4"
+                                 : "=&v"(r0), "=&v"(r1), "+s"(fn0) : "v"(rd_a), "n"(8 * PITCH) : "memory");
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const vbnn_f32x4 z = Epi::fold_z(vbnn_u32x4{{uw[b][0], uw[b][1], uw[b][2], uw[b][3]}});
+                    float sv[4];
+                    acc[4 * G + b][j] = Epi::fold_sz(acc[4 * G + b][j], b4[b], z, sv);
+                    const bf16x4 pk = bf16x4{Elt<ST>::to(sv[0]), Elt<ST>::to(sv[1]), Elt<ST>::to(sv[2]), Elt<ST>::to(sv[3])};
+                    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(wr_a), "v"(pk), "n"(32 * b) : "memory");
+                }
+                asm volatile("" : "+s"(fn0), "+s"(fm0)
+                             : "v"(acc[4 * G][j]), "v"(acc[4 * G + 1][j]), "v"(acc[4 * G + 2][j]), "v"(acc[4 * G + 3][j]));
+                if constexpr (g == 3) V3_FOLD_READ_BIAS(1);
+                if constexpr (g < 7) words(std::integral_constant<int, g + 1>(), un);
+                if constexpr (g == 0)
+                    asm volatile("" : "+v"(un[0]), "+v"(un[1]), "+v"(un[2]), "+v"(un[3]), "+s"(fn0), "+s"(fm0));
+                else if constexpr (g == 3)
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r0), "+v"(r1), "+v"(b4[0]), "+v"(b4[1]), "+v"(b4[2]), "+v"(b4[3]),
+                                 "+v"(un[0]), "+v"(un[1]), "+v"(un[2]), "+v"(un[3]), "+s"(fn0), "+s"(fm0) :: "memory");
+                else if constexpr (g < 7)
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r0), "+v"(r1), "+v"(un[0]), "+v"(un[1]), "+v"(un[2]), "+v"(un[3]),
+                                 "+s"(fn0), "+s"(fm0) :: "memory");
+                else
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r0), "+v"(r1), "+s"(fn0), "+s"(fm0) :: "memory");
+                if constexpr (g > 0) store_rows(std::integral_constant<int, g - 1>(), r0, r1);
+                if constexpr (g < 7) {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) uw[b] = un[b];
+                }
+            });
+            {
+                bf16x8 r0, r1;
+                asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:%3\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(r0), "=&v"(r1) : "v"(rd_a), "n"(8 * PITCH) : "memory");
+                store_rows(std::integral_constant<int, 7>(), r0, r1);
+            }
+#undef V3_FOLD_READ_BIAS
         } else if constexpr (Epi::FOLD_STAGE != 0) {
             // The fold's own output tensor ([n][m], element type ST) leaves through a per-wave LDS tile [16 n][64 m]: the
             // four quads of an (n-block, four m-blocks) group are written as they stand (lane (n = c16, 4 m)), read back
@@ -933,8 +1040,12 @@ static int launch_gemm_v3(vbnn_ctx* ctx, const T* A, const T* A2, int64_t lda, c
         if (!gemm_v3_possible(M, N, K, lda, ldb, AK, BK, epi)) { vbnn_set_error("gemm_v3: shape / outputs outside its fast path"); return VBNN_ERR_UNSUPPORTED; }
         const int tiles_m = (M + V3_BM - 1) / V3_BM, tiles_n = (N + V3_BN - 1) / V3_BN;
         const void* kern = (const void*)gemm_nt_v3<DUAL, AK, BK, Epi>;
-        static vbnn_per_device_flag configured_on;           // per instantiation and device
-        bool& configured = configured_on[ctx->device];
+        int form = 0;
+        if constexpr (DUAL && v3_fold_pipe<Epi>::value != 0) {
+            if (g_v3_fold_serial) { kern = (const void*)gemm_nt_v3<DUAL, AK, BK, Epi, false, false, 0>; form = 1; }
+        }
+        static vbnn_per_device_flag configured_on[2];        // per instantiation (and fold form) and device
+        bool& configured = configured_on[form][ctx->device];
         if (!configured) {
             hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS);
             if (e != hipSuccess) { vbnn_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return VBNN_ERR_HIP; }
