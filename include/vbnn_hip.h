@@ -917,6 +917,73 @@ typedef struct vbnn_quantiles_args {
 } vbnn_quantiles_args;
 int vbnn_predict_quantiles(vbnn_ctx* ctx, const vbnn_quantiles_args* a);
 
+/* Classifier calibration (additive, ABI 6; vbnn_amd/csrc/calibration.hip): the fifth member of the moments family. From the
+ * class probabilities of a predictive (R x C fp32, as vbnn_head_predict / vbnn_predict_class_moments write them), its predicted
+ * classes and the targets: per row the confidence, the hit, the Brier score and the confidence bin, and -- added to ONE integer
+ * accumulator -- what the reliability diagram, ECE, MCE, the Brier score and the accuracy of a whole test set are computed from.
+ * All arithmetic is fp32, operation by operation as written here (compiled without floating-point contraction). Per row r:
+ *   p = min(max(pred[r], 0), C - 1);  t = min(max(target[r], 0), C - 1)   (the family's rule for targets)
+ *   conf = probs[r, p];   hit = [p == t]
+ *   ss = sum_c probs[r, c] * probs[r, c]   by the family's row-sum rule (vbnn_predict_class_moments above: T = 64 threads while
+ *     C <= 256, 256 above; thread i adds to +0, in ascending order, the columns 4 q .. 4 q + 3 of its quads q = i, i + T, ...; the
+ *     xor butterfly 32, 16, .. 1 inside a wave; the four waves in wave order) -- its order depends on C alone
+ *   brier = max((ss - 2 * probs[r, t]) + 1, 0)       (sum_c (probs[c] - [c == t])^2, expanded)
+ *   bin = min(int(conf * float(M)), M - 1), M = bins   (evaluated as int(min(max(conf * float(M), 0), float(M - 1))), which is the
+ *     same number for every conf >= 0 and keeps any other value inside the M bins)
+ * A row whose conf or ss is NaN is SKIPPED: it adds 1 to n_nan and nothing else, its row outputs are NaN (conf, brier) and -1
+ * (hit, bin), and no other row changes by a bit. Probabilities are finite values in [0, 1] (a few ulps above 1 included) or NaN;
+ * the results for other values are unspecified (no access leaves the buffers). Pad columns (ld > C) are never read; the row
+ * takes 16-byte loads where ld is a multiple of 4 and probs is 16-byte aligned, 4-byte loads otherwise (chosen per launch; a
+ * row's last, partial quad always goes element by element) -- the same bits either way.
+ * acc: 3 M + 4 uint64 words that the call ADDS to and the caller zeroes:
+ *   [0, M) count[b];  [M, 2 M) hits[b];  [2 M, 3 M) conf_fix[b] += (uint64)(max(conf, 0) * 2^32)  (the product is exact in fp32; the
+ *   conversion truncates nothing once conf >= 2^-9);  [3 M] brier_fix += (uint64)(brier * 2^32);  [3 M + 1] n_rows (the rows
+ *   counted: not the NaN ones);  [3 M + 2] n_nan;  [3 M + 3] reserved (untouched).
+ * Every accumulated value is an integer, so acc is bit for bit independent of the grid, the arrival order, the chunking, the
+ * number of calls and -- summed on the host -- the number of ranks. Each workgroup reduces its rows in LDS first and issues at
+ * most one global add per word (64-bit vector integer atomics). From the integers, in float64 on the host:
+ *   ECE = sum_b |hits[b] - conf_fix[b] / 2^32| / n_rows;  MCE = max_b |hits[b] - conf_fix[b] / 2^32| / count[b];
+ *   Brier = brier_fix / 2^32 / n_rows;  accuracy = sum_b hits[b] / n_rows. */
+#define VBNN_CALIBRATION_MAX_BINS 64   /* most bins */
+typedef struct vbnn_calibration_args {
+    const float* probs; int64_t ld;     /* R x C class probabilities, ld >= C */
+    const int32_t* pred;                /* R predicted classes */
+    const int32_t* target;              /* R class indices (required) */
+    int64_t R, C;                       /* rows (1 .. 2^31 - 1), classes (>= 1) */
+    int32_t bins;                       /* M: 1 .. VBNN_CALIBRATION_MAX_BINS equal-width confidence bins */
+    int32_t reserved;
+    /* per-row outputs, each optional (NULL to skip) */
+    float* conf; int32_t* hit; float* brier; int32_t* bin;   /* R each */
+    uint64_t* acc;                      /* 3 bins + 4 words: the call ADDS, the caller zeroes (8-byte aligned) */
+} vbnn_calibration_args;
+int vbnn_predict_calibration(vbnn_ctx* ctx, const vbnn_calibration_args* a);
+
+/* Selective prediction (same file): the risk against the coverage at chosen ranks. score (R fp32, lower = more certain: an
+ * entropy, a mutual information, 1 - conf) orders the rows, hit (R int32, nonzero = correct) says which were right. Scores order
+ * as floats by their bits: with u the bits of a score, key = u ^ (u >> 31 ? 0xffffffff : 0x80000000), compared as unsigned
+ * integers -- -0 sorts right below +0, -inf first; every NaN counts as the positive quiet NaN 0x7fc00000, above +inf (rows
+ * with a NaN score rank last). For each of the Q ranks k[j] (1-based, 1 <= k <= R; any order, repeats allowed):
+ *   tau[j] = the score of the k[j]-th smallest key (the quiet NaN when that is a NaN);
+ *   counts[4 j ..] = { n_below, hits_below, n_tied, hits_tied }: the rows whose key is below tau's and the hits among them, the
+ *   rows whose key EQUALS tau's and the hits among them (n_below < k <= n_below + n_tied).
+ * Ties are NOT broken by row order: the accuracy at rank k is the expectation over a random tie-break,
+ *   acc@k = (hits_below + (k - n_below) * hits_tied / n_tied) / k   (float64, on the host),
+ * so scores that are all equal (the mutual information of a MAP or one-draw prediction is exactly 0 on every row) give the
+ * overall accuracy at every k, not the accuracy of the first k rows. An exact radix select on integer counts in one workgroup
+ * (R is a test set; R < 2^31): no float atomics, no allocation, no host synchronisation; tau and counts are WRITTEN. */
+#define VBNN_SELECTIVE_MAX_Q 32        /* most ranks */
+typedef struct vbnn_selective_args {
+    const float* score;                 /* R */
+    const int32_t* hit;                 /* R */
+    int64_t R;
+    int32_t Q;                          /* ranks in k */
+    int32_t reserved;
+    int64_t k[32];                      /* VBNN_SELECTIVE_MAX_Q entries; the first Q are read */
+    float* tau;                         /* Q */
+    uint64_t* counts;                   /* Q x 4 (8-byte aligned) */
+} vbnn_selective_args;
+int vbnn_selective(vbnn_ctx* ctx, const vbnn_selective_args* a);
+
 /* ---- the sampling-free predictive by moment propagation (additive, ABI 6; vbnn_amd/csrc/propagate.hip; not in the reference) --
  * A factorised-Gaussian posterior needs no draws to predict: one pass carries (mean a, second moment q, variance c) of every
  * activation through the network. A hidden layer is three SINGLE products of vbnn_forward (w2 = NULL, y out, no ReLU):

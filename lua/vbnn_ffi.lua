@@ -325,6 +325,28 @@ typedef struct vbnn_quantiles_args {
     uint64_t* count_le;
 } vbnn_quantiles_args;
 int vbnn_predict_quantiles(vbnn_ctx* ctx, const vbnn_quantiles_args* a);
+typedef struct vbnn_calibration_args {
+    const float* probs; int64_t ld;
+    const int32_t* pred;
+    const int32_t* target;
+    int64_t R, C;
+    int32_t bins;
+    int32_t reserved;
+    float* conf; int32_t* hit; float* brier; int32_t* bin;
+    uint64_t* acc;
+} vbnn_calibration_args;
+int vbnn_predict_calibration(vbnn_ctx* ctx, const vbnn_calibration_args* a);
+typedef struct vbnn_selective_args {
+    const float* score;
+    const int32_t* hit;
+    int64_t R;
+    int32_t Q;
+    int32_t reserved;
+    int64_t k[32];
+    float* tau;
+    uint64_t* counts;
+} vbnn_selective_args;
+int vbnn_selective(vbnn_ctx* ctx, const vbnn_selective_args* a);
 typedef struct vbnn_relu_moments_args {
     const float* m; int64_t ld_m;
     const float* v1; const float* v2; int64_t ld_v;

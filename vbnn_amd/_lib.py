@@ -141,6 +141,22 @@ QUANTILES_MAX_S = 128                 # VBNN_QUANTILES_MAX_S
 QUANTILES_MAX_Q = 8                   # VBNN_QUANTILES_MAX_Q
 
 
+class CalibrationArgs(C.Structure):   # vbnn_calibration_args
+    _fields_ = [("probs", _vp), ("ld", _i64), ("pred", _vp), ("target", _vp), ("R", _i64), ("C", _i64), ("bins", C.c_int32),
+                ("reserved", C.c_int32), ("conf", _vp), ("hit", _vp), ("brier", _vp), ("bin", _vp), ("acc", _vp)]
+
+
+CALIBRATION_MAX_BINS = 64             # VBNN_CALIBRATION_MAX_BINS
+
+
+class SelectiveArgs(C.Structure):     # vbnn_selective_args
+    _fields_ = [("score", _vp), ("hit", _vp), ("R", _i64), ("Q", C.c_int32), ("reserved", C.c_int32), ("k", _i64 * 32),
+                ("tau", _vp), ("counts", _vp)]
+
+
+SELECTIVE_MAX_Q = 32                  # VBNN_SELECTIVE_MAX_Q
+
+
 class ReluMomentsArgs(C.Structure):   # vbnn_relu_moments_args
     _fields_ = [("m", _vp), ("ld_m", _i64), ("v1", _vp), ("v2", _vp), ("ld_v", _i64), ("N", _i64), ("O", _i64),
                 ("a", _vp), ("q", _vp), ("c", _vp), ("ld_out", _i64)]
@@ -270,6 +286,8 @@ _SIGS = {
     "vbnn_predict_gauss_moments": ([_vp, C.POINTER(GaussMomentsArgs)], _i),
     "vbnn_predict_class_moments": ([_vp, C.POINTER(ClassMomentsArgs)], _i),
     "vbnn_predict_quantiles": ([_vp, C.POINTER(QuantilesArgs)], _i),
+    "vbnn_predict_calibration": ([_vp, C.POINTER(CalibrationArgs)], _i),
+    "vbnn_selective": ([_vp, C.POINTER(SelectiveArgs)], _i),
     "vbnn_relu_moments": ([_vp, _i, C.POINTER(ReluMomentsArgs)], _i),
     "vbnn_square_shadow": ([_vp, _i, _vp, _i64, _i64, _i64, _vp, _i64], _i),
     "vbnn_logit_draws": ([_vp, C.POINTER(LogitDrawsArgs)], _i),

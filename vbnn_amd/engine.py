@@ -8,7 +8,8 @@ epilogue), final Linear + LogSoftMax + ClassNLL, backward (gradInput GEMMs with 
 dL/dv hand-off in the epilogue, accGradParameters GEMMs with the gradSum / KL-gradient epilogue).
 
 Everything here is argument plumbing around include/vbnn_hip.h; torch is device memory, the
-stream and torch.distributed. The posterior predictives (predictive.py), pruning (pruning.py) and checkpoints (checkpoint.py) are mixins of
+stream and torch.distributed. The posterior predictives (predictive.py), their calibration (calibration.py), pruning (pruning.py) and
+checkpoints (checkpoint.py) are mixins of
 FusedMLP.
 """
 import contextlib
@@ -22,6 +23,7 @@ from . import _lib as L
 from . import partition
 from .nn import Context, _DT, _Packed, _VB, _ordered, _p, fill_normal
 from .predictive import PredictResult, QuantilePredictResult, RegressionPredictResult, _Predictive       # noqa: F401  (the result classes: re-exported)
+from .calibration import CalibrationResult, SelectiveResult, _Calibration      # noqa: F401
 from .pruning import PruneResult, SparsePruneResult, UnitPruneResult, _Pruning      # noqa: F401
 from .checkpoint import CheckpointError, _Checkpoint, digest      # noqa: F401
 
@@ -63,7 +65,7 @@ class _StepGraph:
             self.h = None
 
 
-class FusedMLP(_Predictive, _Pruning, _Checkpoint):
+class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
     def __init__(self, opt, device=None, world_size=1, rank=0, process_group=None, force_reduce=False, stream=None):
         """stream: a torch.cuda.Stream for this engine's launches (a library context of its own, hence its own reduction
         scratch and tickets): two engines on two streams may compute on one device at the same time. Default: the

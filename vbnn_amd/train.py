@@ -22,6 +22,11 @@ opt.checkpoint = True (off by default): save() also writes `<network_name>/model
 trainer = {epoch, indices, rng}; opt.network_to_load = <dir> loads `<dir>/model` into the engine and restores the trainer, and the run
 continues bit for bit as the uninterrupted one would have (checkpoint.py says why).
 
+opt.calibration_bins = M (0 = off, the default) with opt.predictive and the NLL criterion: the dev pass accumulates ONE
+CalibrationResult over its minibatches (FusedMLP.calibration, into=) and logs `dev_ece`, `dev_mce`, `dev_brier`;
+opt.selective_coverages = [c, ...] adds `dev_acc@cov<c>`, the accuracy over the fraction c of the dev rows the predictive entropy
+ranks most certain (FusedMLP.selective).
+
 Differences from main.lua, all deliberate: the loop ends after `epochs` (the reference loops forever, :164); a last
 short minibatch is skipped rather than padded with uninitialised rows (data.lua:9-20); targets are 0-based.
 """
@@ -154,6 +159,12 @@ class Main:
             raise ValueError("opt.quantile_probs needs the sampled predictive (opt.predictive = True): predict_analytic has no quantiles")
         for pj in qprobs:
             pred[f"dev_cal@{pj:g}"] = 0.0
+        # opt.calibration_bins = M (0 = off, the default) with a class predictive: ONE CalibrationResult accumulated over the dev
+        # minibatches on the device (FusedMLP.calibration, into=) gives `dev_ece`, `dev_mce`, `dev_brier`; opt.selective_coverages
+        # adds `dev_acc@cov<c>`, the accuracy over the fraction c of the rows the predictive entropy ranks most certain
+        # (FusedMLP.selective). Both need the R x C probabilities, which the predictive then keeps.
+        cal_bins = int(opt.get("calibration_bins") or 0) if (opt.get("predictive") and not regression) else 0
+        cal = None
         for t0 in starts:
             inputs, targets = dataset.create_minibatch(t0, bs, n, opt.get("geometry"))
             x, t = self._to_device(inputs, targets)
@@ -177,15 +188,23 @@ class Main:
                     pred["dev_noise_var"] += r.mean_noise_var
             elif opt.get("predictive"):    # the S-draw model average on the same minibatch (its own draws, after test()'s)
                 if analytic:
-                    r = net.predict_analytic(x, targets=t, keep_probs=False)
+                    r = net.predict_analytic(x, targets=t, keep_probs=bool(cal_bins))
                 elif getattr(net, "n_classes", 0) > 16:      # predict's head holds a row's classes in one 16-wide tile
-                    r = net.predict_classes(x, targets=t, keep_probs=False)
+                    r = net.predict_classes(x, targets=t, keep_probs=bool(cal_bins))
                 else:
                     r = net.predict(x, targets=t)
+                if cal_bins:
+                    cal = net.calibration(r, t, bins=cal_bins, into=cal)
                 pred["devacc_pred"] += r.accuracy
                 pred["devnll_pred"] += r.nll
                 pred["dev_mi"] += float(r.mutual_info.double().mean())
         self.predictive = {k: v / len(starts) for k, v in pred.items()} if opt.get("predictive") else None
+        if cal is not None:                                  # (sums over the whole dev set, not means of minibatch values)
+            self.predictive.update(dev_ece=cal.ece, dev_mce=cal.mce, dev_brier=cal.brier)
+            covs = [float(c) for c in (opt.get("selective_coverages") or [])]
+            if covs:
+                sel = net.selective(cal.entropy, cal.hit, covs)
+                self.predictive.update({f"dev_acc@cov{c:g}": a for c, a in zip(covs, sel.accuracy)})
         return accuracy / len(starts), error / len(starts)
 
     def _prune_series(self, testSet):
@@ -256,11 +275,11 @@ class Main:
             rec.update(self._prune_series(testSet))       # opt.prune_report / opt.prune_eval (both off by default)
             if self.log:
                 for k in ("devacc", "trainacc", "deverr", "trainerr", "lc", "devacc_pred", "devnll_pred", "dev_mi", "devll_pred", "dev_epi_var",
-                          "dev_noise_var"):   # main.lua:169-177 (+ opt.predictive)
+                          "dev_noise_var", "dev_ece", "dev_mce", "dev_brier"):   # main.lua:169-177 (+ opt.predictive, opt.calibration_bins)
                     if k in rec:
                         self.log.add(k, rec[k])
                 for k in rec:
-                    if k in ("pruned count", "pruned var mean", "held fraction") or k.startswith(("devacc_pruned@", "dev_cal@")):
+                    if k in ("pruned count", "pruned var mean", "held fraction") or k.startswith(("devacc_pruned@", "dev_cal@", "dev_acc@cov")):
                         self.log.add(k, rec[k])
                 self.log.flush()
                 self.save()                                                                # main.lua:181
