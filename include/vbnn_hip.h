@@ -628,6 +628,28 @@ int vbnn_gauss_nll_forward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const fl
 int vbnn_gauss_nll_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
                             float inv_nd, float s_min, float s_max, float* g, int64_t ld_g);
 
+/* The Bernoulli likelihood (additive, ABI 6; not in the reference): D independent sigmoid outputs per row -- binary
+ * classification with D = 1, multi-label classification with D labels. y holds the final Linear's N x D logits (ld_y >= D),
+ * target is N x D fp32 in [0, 1] (0 / 1 labels; soft labels are allowed). criterion:forward + :backward in ONE pass over y and
+ * target, the shape of vbnn_mse_forward: g is N x D (ld_g >= D; optional in the forward), inv_nd = 1 / (GLOBAL rows x D). Each
+ * of the three streams takes the 16-byte or the scalar access path on its own leading dimension and base address. All element
+ * arithmetic is fp32, operation by operation as written (compiled without floating-point contraction; expf and logf are the
+ * library functions, the divisions are correctly rounded). Per element, z the logit and t the target:
+ *   u = expf(-|z|);   w = 1 + u;   l1p = (logf(w) * u) / (w - 1)  (u itself where w == 1) -- log1p(u) in the moments family's
+ *     form (vbnn_predict_class_moments below), not the library's log1pf;
+ *   e = (fmaxf(z, 0) - z * t) + l1p          -- -[t log sigmoid(z) + (1 - t) log(1 - sigmoid(z))], stable for any finite z;
+ *   sig = z >= 0 ? 1 / w : u / w;
+ *   loss_sum_dev[0] (+)= inv_nd * sum e;     g = inv_nd * (sig - t).
+ * The sum is formed in double in a fixed order (block partials + one finish block, no float atomics: bitwise reproducible);
+ * accumulate = 0 stores it, 1 adds to it. correct_dev (optional, NULL to skip): the number of label hits, elements with
+ * (z > 0) == (t > 0.5f), is ADDED to correct_dev[0] by an integer atomic -- exact for any grid; the caller zeroes it. A NaN logit
+ * is a miss. Logits are finite or NaN; a NaN reaches the loss and its own gradient element, and nothing else.
+ * vbnn_bce_backward: g alone, the same bits. */
+int vbnn_bce_forward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
+                     float inv_nd, float* g, int64_t ld_g, int accumulate, double* loss_sum_dev, int32_t* correct_dev);
+int vbnn_bce_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
+                      float inv_nd, float* g, int64_t ld_g);
+
 /* mlp.lua:29-32 fused for a small class count (C <= 16): final nn.Linear + nn.LogSoftMax +
  * nn.ClassNLLCriterion as streaming kernels over the packed N x H activation `h` (dtype) and the packed
  * final weight `w3` (C x ld_w, dtype). Forward: logits = h w3^T + bias, out = logsoftmax,
@@ -866,6 +888,58 @@ typedef struct vbnn_class_moments_args {
     double* totals;
 } vbnn_class_moments_args;
 int vbnn_predict_class_moments(vbnn_ctx* ctx, const vbnn_class_moments_args* a);
+
+/* The multi-label posterior predictive (additive, ABI 6): the moments over S draws of the Bernoulli head of vbnn_bce_forward,
+ * from the final Linear's f32 logits y_s (R x D per draw). The sixth member of the moments family. Everything stated for
+ * vbnn_predict_moments holds here -- fp32 op by op as written (no contraction; correctly rounded divisions; expf / logf /
+ * log1pf the library functions), the row-to-thread assignment (T = 64 threads for D <= 256 with four rows per workgroup,
+ * T = 256 above; thread i owns the quads q = i, i + T, ...), the xor butterfly and then the waves in wave order, so that every
+ * row sum's order depends on D alone, the 16-byte and the scalar access path chosen per launch, pad columns never read, the
+ * two forms bitwise equal -- with the element and row operations below.
+ * Per element (r, d) and draw, with zc = min(max(z, -80), 80) (a NaN z stays NaN). The clamp floors every probability at
+ * e^-80 (a normal fp32), so the sums P and Q below are strictly positive and no log of an average is ever -inf:
+ *   u = expf(-|zc|);   w = 1 + u;   l1p = (logf(w) * u) / (w - 1)  (u itself where w == 1)
+ *   p = zc >= 0 ? 1 / w : u / w;    q = zc >= 0 ? u / w : 1 / w          -- sigmoid(z) and 1 - sigmoid(z), each on its own
+ *   lp = fminf(zc, 0) - l1p;        ln = fminf(-zc, 0) - l1p             -- log p and log q
+ *   P = P + p;   Q = Q + q;   Hs = Hs + -(p * lp + q * ln)               (draw 0 sets each)
+ *   with a target t:  the element's term of a_s is  t * lp + (1 - t) * ln.
+ * Per row and draw, with a target: a_s = sum_d of the element terms (the draw's log-likelihood of the whole label vector); the
+ * running sum of -a_s is kept (draw 0 starts it; divided by R S D it is test()'s number for the same draws); a_s goes into the
+ * online logsumexp: draw 0 sets L = a_0, every later draw L = max(L, a) + log1pf(expf(-|L - a|)).
+ * Finish per element:  pm = P / float(S);  qm = Q / float(S);  log_p = logf(pm);  log_q = logf(qm);
+ *   probs = pm;  entropy = -(pm * log_p + qm * log_q);  expected_entropy = Hs / float(S);
+ *   mutual_info = entropy - expected_entropy (the per-label BALD score), stored as +0 when S = 1, by definition;
+ *   the label is predicted 1 iff P > Q (a tie predicts 0); with a target it is a hit iff that equals (t > 0.5f).
+ * Finish per row:  row_entropy = sum_d entropy;  row_mutual_info = sum_d mutual_info;  with a target
+ *   row_log_lik = L - logf(float(S))                            -- the JOINT mixture over draws of the whole label vector;
+ *   row_marg_log_lik = sum_d (t * log_p + (1 - t) * log_q)      -- the product of the per-label marginals;
+ *   row_hits = the number of hits among the D labels (counted in fp32: exact, D < 2^24).
+ * A NaN logit makes P, Q, Hs and every float output of its element NaN, the float row values of its row NaN and the float
+ * totals NaN; its label counts as a miss; every other element of the row and every other row keep their bits.
+ * VBNN_MOMENTS_STACKED: y holds all S draws (draw s = rows [s R, (s+1) R)); one call walks them with P, Q, Hs in registers
+ * (D <= VBNN_LABEL_MOMENTS_STACKED_MAX_D; draw / state ignored). VBNN_MOMENTS_ACCUMULATE: y holds ONE draw, number `draw`; the
+ * running values live in `state` between the S calls, any D. Both forms run one device function per draw. */
+#define VBNN_LABEL_MOMENTS_STACKED_MAX_D 4096   /* largest D the STACKED form takes */
+typedef struct vbnn_label_moments_args {
+    const float* y; int64_t ld_y;       /* f32 logits: S R x D (STACKED; draw s = rows [s R, (s+1) R)) or R x D (ACCUMULATE); ld_y >= D */
+    const float* target; int64_t ld_t;  /* R x D labels in [0, 1], or NULL */
+    int64_t R, D, S;                    /* minibatch rows, labels per row (>= 1, any), draws of the WHOLE prediction (>= 1) */
+    int32_t form;                       /* VBNN_MOMENTS_STACKED or VBNN_MOMENTS_ACCUMULATE */
+    int32_t draw;                       /* ACCUMULATE: 0-based index of this draw; 0 starts the state (nothing is read from it), S - 1 finishes */
+    float* state;                       /* ACCUMULATE: R x (3 D + 2) floats, row r = { P[D], Q[D], Hs[D], sum_s -a_s, L } */
+    /* outputs of the finish, each optional (NULL to skip) */
+    float* probs; float* entropy; float* mutual_info; int64_t ld_out;   /* R x D each */
+    float* row_entropy;                 /* R: sum_d entropy */
+    float* row_mutual_info;             /* R: sum_d mutual_info */
+    float* row_log_lik;                 /* R (needs target) */
+    float* row_marg_log_lik;            /* R (needs target) */
+    int32_t* row_hits;                  /* R (needs target) */
+    /* with target: 5 doubles WRITTEN by the finish, { sum_r row_log_lik, sum_r row_marg_log_lik, sum_{r,s} -a_s, sum_r row_hits,
+     * sum_r [row_hits = D] }, each summed over rows in double in a fixed order (workgroup partials, one finish block; no float
+     * atomics). NULL to skip. */
+    double* totals;
+} vbnn_label_moments_args;
+int vbnn_predict_label_moments(vbnn_ctx* ctx, const vbnn_label_moments_args* a);
 
 /* Regression predictive quantiles (additive, ABI 6): the fourth member of the moments family. Per element (r, d) the
  * predictive is the equal-weight mixture of S components, one per draw of the final Linear's f32 outputs; this call gives its

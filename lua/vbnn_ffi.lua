@@ -207,6 +207,10 @@ int vbnn_gauss_nll_forward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const fl
                            float inv_nd, float s_min, float s_max, float* g, int64_t ld_g, int accumulate, double* loss_sum_dev);
 int vbnn_gauss_nll_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
                             float inv_nd, float s_min, float s_max, float* g, int64_t ld_g);
+int vbnn_bce_forward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
+                     float inv_nd, float* g, int64_t ld_g, int accumulate, double* loss_sum_dev, int32_t* correct_dev);
+int vbnn_bce_backward(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* target, int64_t ld_t, int64_t N, int64_t D,
+                      float inv_nd, float* g, int64_t ld_g);
 int vbnn_head_forward(vbnn_ctx* ctx, int dtype, const void* h, int64_t ld_h, const void* w3, int64_t ld_w,
                       const float* bias, const int32_t* target, int64_t N, int64_t H, int64_t C, float inv_n,
                       float* logits, float* out, float* g_logits, int accumulate, double* loss_sum_dev,
@@ -308,6 +312,22 @@ typedef struct vbnn_class_moments_args {
     double* totals;
 } vbnn_class_moments_args;
 int vbnn_predict_class_moments(vbnn_ctx* ctx, const vbnn_class_moments_args* a);
+typedef struct vbnn_label_moments_args {
+    const float* y; int64_t ld_y;
+    const float* target; int64_t ld_t;
+    int64_t R, D, S;
+    int32_t form;
+    int32_t draw;
+    float* state;
+    float* probs; float* entropy; float* mutual_info; int64_t ld_out;
+    float* row_entropy;
+    float* row_mutual_info;
+    float* row_log_lik;
+    float* row_marg_log_lik;
+    int32_t* row_hits;
+    double* totals;
+} vbnn_label_moments_args;
+int vbnn_predict_label_moments(vbnn_ctx* ctx, const vbnn_label_moments_args* a);
 enum { VBNN_QUANT_EMPIRICAL = 0, VBNN_QUANT_FIXED_NOISE = 1, VBNN_QUANT_GAUSS = 2 };
 typedef struct vbnn_quantiles_args {
     const float* y; int64_t ld_y;

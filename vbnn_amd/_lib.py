@@ -129,6 +129,16 @@ CLASS_MOMENTS_STACKED_MAX_C = 4096    # VBNN_CLASS_MOMENTS_STACKED_MAX_C
 CLASS_MOMENTS_MAX_K = 8               # VBNN_CLASS_MOMENTS_MAX_K
 
 
+class LabelMomentsArgs(C.Structure):  # vbnn_label_moments_args
+    _fields_ = [("y", _vp), ("ld_y", _i64), ("target", _vp), ("ld_t", _i64), ("R", _i64), ("D", _i64), ("S", _i64),
+                ("form", C.c_int32), ("draw", C.c_int32), ("state", _vp), ("probs", _vp), ("entropy", _vp), ("mutual_info", _vp),
+                ("ld_out", _i64), ("row_entropy", _vp), ("row_mutual_info", _vp), ("row_log_lik", _vp), ("row_marg_log_lik", _vp),
+                ("row_hits", _vp), ("totals", _vp)]
+
+
+LABEL_MOMENTS_STACKED_MAX_D = 4096    # VBNN_LABEL_MOMENTS_STACKED_MAX_D
+
+
 class QuantilesArgs(C.Structure):     # vbnn_quantiles_args
     _fields_ = [("y", _vp), ("ld_y", _i64), ("draw_stride", _i64), ("target", _vp), ("ld_t", _i64), ("R", _i64), ("D", _i64),
                 ("S", _i64), ("kind", C.c_int32), ("Q", C.c_int32), ("p", _f * 8), ("noise_var", _f), ("s_min", _f), ("s_max", _f),
@@ -284,6 +294,9 @@ _SIGS = {
     "vbnn_gauss_nll_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _f, _f, _vp, _i64, _i, _vp], _i),
     "vbnn_gauss_nll_backward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _f, _f, _vp, _i64], _i),
     "vbnn_predict_gauss_moments": ([_vp, C.POINTER(GaussMomentsArgs)], _i),
+    "vbnn_bce_forward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _vp, _i64, _i, _vp, _vp], _i),
+    "vbnn_bce_backward": ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f, _vp, _i64], _i),
+    "vbnn_predict_label_moments": ([_vp, C.POINTER(LabelMomentsArgs)], _i),
     "vbnn_predict_class_moments": ([_vp, C.POINTER(ClassMomentsArgs)], _i),
     "vbnn_predict_quantiles": ([_vp, C.POINTER(QuantilesArgs)], _i),
     "vbnn_predict_calibration": ([_vp, C.POINTER(CalibrationArgs)], _i),

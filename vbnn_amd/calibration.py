@@ -137,6 +137,9 @@ class _Calibration:
         bins, from this engine) adds to ITS accumulator instead -- a test set over many minibatches, without a synchronisation
         -- and appends this call's per-row conf, hit, entropy and mutual_info. Returns the CalibrationResult."""
         what = "calibration"
+        if getattr(self, "criterion", "nll") == "bce":       # (per-label reliability is a follow-up)
+            raise ValueError(f"{what}: criterion = 'bce' has no class predictive to calibrate: use predict_labels (its "
+                             "label_accuracy, log_lik and per-label mutual_info); per-label calibration is not supported yet")
         probs = getattr(result, "probs", None)
         if probs is None:
             raise ValueError(f"{what}: the result holds no class probabilities (probs is None) -- run the predictive with "

@@ -50,7 +50,7 @@ class Dataset(dict):
         t = np.asarray(self["targets"])
         if t.ndim == 1:
             targets = np.zeros(batchSize, dtype=np.int64)
-        else:                                               # regression targets (criterion "mse" / "gauss"): [n, D] floats
+        else:                                               # regression targets (criterion "mse" / "gauss") or labels ("bce"): [n, D] floats
             targets = np.zeros((batchSize,) + tuple(t.shape[1:]), dtype=np.float32)
         inputs[: hi - index, 0] = x[index:hi]
         targets[: hi - index] = self["targets"][index:hi]
@@ -81,6 +81,21 @@ def synthetic_digits(n_train, n_test, classes=10, geometry=(28, 28), seed=3, noi
         t = rs.randint(0, classes, n)
         x = protos[t] + noise * protos.std() * rs.randn(n, *geometry).astype(np.float32)
         return _finish(x, t)
+    return split(n_train), split(n_test)
+
+
+def synthetic_multilabel(n_train, n_test, n_labels, seed=3, noise=0.5, features=16):
+    """A multi-label problem for criterion "bce": inputs are `features` standard normals per row (geometry (1, features)), label
+    l of a row is the sign of a fixed random linear function of the input plus noise, [x . w_l / sqrt(features) + noise eps > 0],
+    as 0 / 1 fp32 targets [n, n_labels]. The functions are drawn once per seed and shared by both splits. Same seed -> same
+    data."""
+    rs = np.random.RandomState(seed)
+    w = rs.randn(features, n_labels).astype(np.float32) / np.float32(np.sqrt(features))
+
+    def split(n):
+        x = rs.randn(n, 1, features).astype(np.float32)
+        y = x[:, 0] @ w + noise * rs.randn(n, n_labels).astype(np.float32)
+        return Dataset(inputs=x, targets=(y > 0).astype(np.float32))
     return split(n_train), split(n_test)
 
 

@@ -22,7 +22,8 @@ import torch
 from . import _lib as L
 from . import partition
 from .nn import Context, _DT, _Packed, _VB, _ordered, _p, fill_normal
-from .predictive import PredictResult, QuantilePredictResult, RegressionPredictResult, _Predictive       # noqa: F401  (the result classes: re-exported)
+from .predictive import (LabelPredictResult, PredictResult, QuantilePredictResult, RegressionPredictResult,       # noqa: F401
+                         _Predictive)                                            # (the result classes: re-exported)
 from .calibration import CalibrationResult, SelectiveResult, _Calibration      # noqa: F401
 from .pruning import PruneResult, SparsePruneResult, UnitPruneResult, _Pruning      # noqa: F401
 from .checkpoint import CheckpointError, _Checkpoint, digest      # noqa: F401
@@ -130,9 +131,11 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
         # "nll": LogSoftMax + ClassNLLCriterion (mlp.lua:30-32); "mse": nn.MSECriterion on the final Linear's outputs
         # (BASELINE.json configs[4], a regression target of n_classes dimensions -- not in the reference); "gauss": the
         # heteroscedastic Gaussian likelihood (vbnn_gauss_nll_forward) -- the final Linear's n_classes = 2 D outputs are D means
-        # and D log noise variances, the targets R x D; opt.logvar_clamp = (s_min, s_max) clamps the log variance
+        # and D log noise variances, the targets R x D; opt.logvar_clamp = (s_min, s_max) clamps the log variance; "bce": the
+        # Bernoulli likelihood (vbnn_bce_forward) -- n_classes = D >= 1 independent sigmoid outputs, the targets R x D fp32 in
+        # [0, 1]: binary classification with D = 1, multi-label classification with D labels
         self.criterion = opt.get("criterion", "nll")
-        assert self.criterion in ("nll", "mse", "gauss")
+        assert self.criterion in ("nll", "mse", "gauss", "bce")
         self.logvar_clamp = tuple(float(v) for v in opt.get("logvar_clamp", (-20.0, 20.0)))
         if self.criterion == "gauss":
             if int(opt["n_classes"]) % 2:
@@ -513,7 +516,7 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
             self.run(inputs, targets, backward=False)
             loss, correct = self.loss_and_accuracy()
             err += loss * self.world            # the criterion divides by the global batch; this is the local mean
-            acc += 100.0 * correct / N
+            acc += 100.0 * correct / (N * (self.n_classes if self.criterion == "bce" else 1))     # ("bce" counts label hits)
         return err / draws, acc / draws
 
     # ---- mlp.lua:69-74
@@ -553,6 +556,12 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
                                                self.logvar_clamp[1], _p(self.g_logits), Cn, accumulate, _p(self._acc)))
             if not accumulate:
                 L.check(lib.vbnn_buf_zero(ctx, _p(self._corr), 4))
+        elif self.criterion == "bce":
+            assert targets.dtype == torch.float32 and tuple(targets.shape) == (N, Cn) and targets.is_contiguous()
+            if not accumulate:                          # vbnn_bce_forward adds the label hits into its counter
+                L.check(lib.vbnn_buf_zero(ctx, _p(self._corr), 4))
+            L.check(lib.vbnn_bce_forward(ctx, _p(self.logits), Cn, _p(targets), Cn, N, Cn, inv_n / Cn, _p(self.g_logits), Cn,
+                                         accumulate, _p(self._acc), _p(self._corr)))
         else:
             if not accumulate:                          # vbnn_logsoftmax_nll adds into its accumulators
                 L.check(lib.vbnn_buf_zero(ctx, _p(self._acc), 16))
@@ -680,6 +689,11 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
         all-reduce sums that already contain other ranks' contributions, and the exchange stream's in-place write would
         race with the next draw's accumulate epilogue -- so earlier draws only accumulate."""
         lib, ctx, code = L.lib(), self.ctx.h, self.code
+        if self.criterion == "bce":                   # the label hits of a minibatch's draws add up in an int32 counter
+            draws = self._draws if self._rpd else max(1, int(self.S))
+            if inputs.shape[0] * self.n_classes * draws >= 1 << 31:
+                raise ValueError(f"criterion = 'bce': {inputs.shape[0]} rows x {self.n_classes} labels x {draws} draws reach 2^31 "
+                                 "label hits, more than the int32 hit counter of a minibatch holds: use smaller minibatches")
         if backward:
             self._draws_run += 1
             if last_draw is None:
@@ -1090,13 +1104,15 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
     def synthetic_targets(self, x, row0=0):
         """bench / tests: class targets uniform in 0..n_classes-1 by GLOBAL row (data.lua:16 convention, 0-based); for the
         regression criteria y* = x R / sqrt(I) with a fixed Philox-drawn R (D columns: n_classes
-        for "mse", n_classes / 2 for "gauss") -- data preparation outside the timed step, so a plain torch matmul."""
+        for "mse", n_classes / 2 for "gauss") -- data preparation outside the timed step, so a plain torch matmul; for "bce" the
+        0 / 1 labels [y* > 0] of that teacher (n_classes columns, fp32)."""
         N = x.shape[0]
-        if self.criterion in ("mse", "gauss"):
-            D = self.n_classes if self.criterion == "mse" else self.n_classes // 2
+        if self.criterion in ("mse", "gauss", "bce"):
+            D = self.n_classes // 2 if self.criterion == "gauss" else self.n_classes
             R = torch.empty(x.shape[1], D, dtype=torch.float32, device=x.device)
             fill_normal(R, self.seed, L.STREAM_DATA, 1, 0)
-            return (x @ R / math.sqrt(x.shape[1])).contiguous()
+            y = (x @ R / math.sqrt(x.shape[1])).contiguous()
+            return (y > 0).to(torch.float32) if self.criterion == "bce" else y
         return ((torch.arange(N, device=x.device, dtype=torch.int64) + row0) * 2654435761 % self.n_classes).to(torch.int32)
 
     def _adam_slot(self, v, key, like, cfg):

@@ -1,5 +1,5 @@
-"""The posterior predictives of the fused engine (FusedMLP.predict / predict_classes / predict_regression / predict_quantiles, and
-the sampling-free predict_analytic): forward-only passes on buffers of their own, dense or under a pruned view (pruning.py). A
+"""The posterior predictives of the fused engine (FusedMLP.predict / predict_classes / predict_regression / predict_quantiles /
+predict_labels, and the sampling-free predict_analytic): forward-only passes on buffers of their own, dense or under a pruned view (pruning.py). A
 mixin of vbnn_amd/engine.py:FusedMLP."""
 import ctypes as C
 import functools
@@ -71,6 +71,13 @@ def _check_regression_targets(what, targets, R, D):
     return None if targets is None else targets.contiguous()
 
 
+def _refuse_bce(what, criterion):
+    """The predictives of the other likelihoods on a Bernoulli engine: the remedy is predict_labels."""
+    if criterion == "bce":
+        raise ValueError(f"{what}: criterion = 'bce' (independent sigmoid outputs) has a multi-label predictive of its own: "
+                         "use predict_labels")
+
+
 class _PredictBuffers(list):
     """predict's operands per layer input (+ .r, the sequential bf16 forwards' throwaway noise factor; .y_reg: predict_regression's y)."""
     r = y_reg = None
@@ -121,6 +128,26 @@ class RegressionPredictResult:
         self.row_sq_err, self.row_log_lik, self.draws = row_sq_err, row_log_lik, draws
         self.totals = self.mse = self.mean_draw_mse = self.log_lik = self.mean_var = None
         self.noise_var = self.row_noise_var = self.mean_noise_var = self.mean_draw_nll = None
+        self.S, self.stacked, self.chunks = None, None, None
+
+
+class LabelPredictResult:
+    """FusedMLP.predict_labels' outputs for R minibatch rows of D labels (criterion "bce"). Device tensors, R x D: probs (the
+    S-draw average 1/S sum_s sigmoid(f_s(x)) per label), entropy (the binary entropy of probs: total uncertainty per label),
+    mutual_info (entropy minus the draws' mean entropy: the epistemic part, BALD per label; exactly 0 for S = 1); R:
+    row_entropy, row_mutual_info (their sums over the labels); with targets (R x D in [0, 1]) row_log_lik (R: the log of the
+    equal-weight mixture over draws of the JOINT likelihood of the row's label vector), row_marg_log_lik (R: the log-likelihood
+    under the product of the per-label marginals probs), row_hits (R int32: labels predicted right, a label being predicted 1 iff
+    its probability exceeds that of 0); draws (S x R x D logits) with keep_draws. With targets also Python floats: totals (the
+    library's five sums), log_lik and marg_log_lik (means over rows), mean_draw_bce (the mean over draws of each draw's
+    criterion: test()'s number), label_accuracy (percent of the R D labels) and exact_match (percent of rows with every label
+    right). None without targets."""
+
+    def __init__(self, probs, entropy, mutual_info, row_entropy, row_mutual_info):
+        self.probs, self.entropy, self.mutual_info = probs, entropy, mutual_info
+        self.row_entropy, self.row_mutual_info = row_entropy, row_mutual_info
+        self.row_log_lik = self.row_marg_log_lik = self.row_hits = self.draws = self.totals = None
+        self.log_lik = self.marg_log_lik = self.mean_draw_bce = self.label_accuracy = self.exact_match = None
         self.S, self.stacked, self.chunks = None, None, None
 
 
@@ -239,6 +266,7 @@ class _Predictive:
         this rank's first row, as run()). Returns a PredictResult of this rank's rows (no collective, as test())."""
         lib, ctx, code = L.lib(), self.ctx.h, self.code
         Cn = self.n_classes
+        _refuse_bce("predict", self.criterion)
         if Cn > 16:
             raise ValueError(f"predict: the predictive head takes at most 16 classes (n_classes = {Cn})")
         if self.criterion != "nll":
@@ -373,6 +401,7 @@ class _Predictive:
     def _regression_predict(self, what, inputs, S, targets, noise_var, map, row0, keep_draws, max_S=None):
         """predict_regression's body, which predict_quantiles (`what`, for the messages) runs too."""
         lib, ctx = L.lib(), self.ctx.h
+        _refuse_bce(what, self.criterion)
         if self.criterion not in ("mse", "gauss"):
             raise ValueError(f"{what}: the regression predictive needs the MSE criterion or the Gaussian one "
                              "(criterion = 'nll': use predict)")
@@ -491,6 +520,7 @@ class _Predictive:
         S x R x C logits are returned too. Returns a PredictResult of this rank's rows (no collective, as test())."""
         lib, ctx = L.lib(), self.ctx.h
         Cn = self.n_classes
+        _refuse_bce("predict_classes", self.criterion)
         if self.criterion != "nll":
             raise ValueError(f"predict_classes: a class-probability predictive needs the NLL criterion (criterion = "
                              f"'{self.criterion}' has none: use predict_regression)")
@@ -506,6 +536,60 @@ class _Predictive:
         self._consume_draws(p.S, p.map)
         self._class_moments_finish(res, totals, p.R, p.S, K)
         return _stamp(res, p.S, p.stacked, p.n_chunks)
+
+    # ---- the Bernoulli criterion's posterior predictive (vbnn_predict_label_moments): predict_regression's contract, buffers and
+    # route -- the final Linear as _generic_head runs it (f32 logits), then the moments of the family over the S draws'
+    # sigmoids -- with the per-label uncertainties. Nothing of the training step is written.
+    @_ordered
+    def predict_labels(self, inputs, S=None, targets=None, map=False, row0=None, keep_draws=False):
+        """p(y_d = 1 | x, D) ~ 1/S sum_s sigmoid(f_s(x)_d) per label over draws self.draw + 1 .. self.draw + S, with the per-label
+        entropy and mutual information (BALD per label); S, map and row0 as predict(), and `self.draw` advances by S likewise.
+        targets: R x D fp32 labels in [0, 1] (D = n_classes). keep_draws: the S x R x D logits are returned too. Chunked by
+        opt.predict_rows; pruned, compressed, compact and held-mask networks and WN (sequential) as predict_regression. Returns a
+        LabelPredictResult of this rank's rows (no collective, as test())."""
+        lib, ctx = L.lib(), self.ctx.h
+        what = "predict_labels"
+        if self.criterion != "bce":
+            raise ValueError(f"{what}: the multi-label predictive needs the Bernoulli criterion (criterion = '{self.criterion}': use "
+                             + ("predict_regression)" if self.criterion in ("mse", "gauss") else "predict or predict_classes)"))
+        D = self.n_classes
+        targets = _check_regression_targets(what, targets, inputs.shape[0], D)       # (R x D fp32; before the plan, as predict)
+        p = self._predictive_plan(what, inputs, S, map, row0)
+        R, S = p.R, p.S
+        f32 = dict(dtype=torch.float32, device=self.device)
+        has_t = targets is not None
+        res = LabelPredictResult(torch.empty(R, D, **f32), torch.empty(R, D, **f32), torch.empty(R, D, **f32), torch.empty(R, **f32),
+                                 torch.empty(R, **f32))
+        if has_t:
+            res.row_log_lik, res.row_marg_log_lik = torch.empty(R, **f32), torch.empty(R, **f32)
+            res.row_hits = torch.empty(R, dtype=torch.int32, device=self.device)
+        if keep_draws:
+            res.draws = torch.empty(S, R, D, **f32)
+        one_call = p.stacked and D <= L.LABEL_MOMENTS_STACKED_MAX_D          # else: ACCUMULATE per draw
+        state = None if one_call else torch.empty(p.Rc, 3 * D + 2, **f32)
+        totals = torch.zeros(p.n_chunks, 5, dtype=torch.float64, device=self.device) if has_t else None
+        a = L.LabelMomentsArgs(ld_y=D, ld_t=D, D=D, S=S, form=L.MOMENTS_STACKED if one_call else L.MOMENTS_ACCUMULATE,
+                               state=_p(state), ld_out=D)
+
+        def point(c0, rows):                   # the chunk's targets and outputs
+            a.R = rows
+            a.target = _off(targets, c0 * D)
+            a.totals = _p(totals[c0 // p.Rc]) if has_t else None
+            a.probs, a.entropy, a.mutual_info = _off(res.probs, c0 * D), _off(res.entropy, c0 * D), _off(res.mutual_info, c0 * D)
+            a.row_entropy, a.row_mutual_info = _off(res.row_entropy, c0), _off(res.row_mutual_info, c0)
+            a.row_log_lik, a.row_marg_log_lik = _off(res.row_log_lik, c0), _off(res.row_marg_log_lik, c0)
+            a.row_hits = _off(res.row_hits, c0)
+
+        self._moments_loop(p, D, res.draws, keep_draws, one_call, a,
+                           lambda: L.check(lib.vbnn_predict_label_moments(ctx, C.byref(a))), point)
+        self._consume_draws(S, p.map)
+        if has_t:
+            tot = _chunk_sums(totals)
+            res.totals = tot
+            res.log_lik, res.marg_log_lik = tot[0] / R, tot[1] / R
+            res.mean_draw_bce = tot[2] / (R * S * D)
+            res.label_accuracy, res.exact_match = 100.0 * tot[3] / (R * D), 100.0 * tot[4] / R
+        return _stamp(res, S, p.stacked, p.n_chunks)
 
     def _class_moments_plan(self, R, S, Rc, n_chunks, one_call, targets, K, keep_probs):
         """What predict_classes and predict_analytic set up for vbnn_predict_class_moments over R rows in n_chunks chunks of Rc:
@@ -637,6 +721,7 @@ class _Predictive:
         dense pruned views, held masks and compact networks work through the operand shadows; compressed views are refused.
         Chunked by opt.predict_rows. Returns this rank's rows (no collective)."""
         what = "predict_analytic"
+        _refuse_bce(what, self.criterion)      # (the moments of sigmoid(z) under a Gaussian logit are a follow-up)
         if self.criterion == "gauss":
             raise ValueError(f"{what}: criterion = 'gauss' is not supported -- the clamp on the log variance makes the moments of "
                              "exp(s) a separate piece of work (the follow-up); use predict_regression")

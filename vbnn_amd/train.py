@@ -27,6 +27,11 @@ CalibrationResult over its minibatches (FusedMLP.calibration, into=) and logs `d
 opt.selective_coverages = [c, ...] adds `dev_acc@cov<c>`, the accuracy over the fraction c of the dev rows the predictive entropy
 ranks most certain (FusedMLP.selective).
 
+opt.criterion = "bce" (the Bernoulli likelihood: multi-label classification, binary with one label): targets are R x D fp32
+labels, the accuracy is the label accuracy 100 correct / (rows S D), and with opt.predictive the dev pass calls
+FusedMLP.predict_labels and logs `devll_pred` (the joint log-likelihood of a row's label vector), `dev_label_acc`,
+`dev_exact_match` and `dev_label_mi` (the mean per-label mutual information).
+
 Differences from main.lua, all deliberate: the loop ends after `epochs` (the reference loops forever, :164); a last
 short minibatch is skipped rather than padded with uninitialised rows (data.lua:9-20); targets are 0-based.
 """
@@ -91,7 +96,7 @@ class Main:
 
     def _to_device(self, inputs, targets):
         x = torch.from_numpy(np.ascontiguousarray(inputs, dtype=np.float32)).to(self.device)
-        regression = getattr(self.net, "criterion", "nll") in ("mse", "gauss")           # R x D fp32 targets; class labels otherwise
+        regression = getattr(self.net, "criterion", "nll") in ("mse", "gauss", "bce")    # R x D fp32 targets; class labels otherwise
         t = torch.from_numpy(np.ascontiguousarray(targets)).to(self.device, dtype=torch.float32 if regression else torch.int32)
         return x, t
 
@@ -122,7 +127,8 @@ class Main:
                 # loss and the last layer's gradients still show it (tests: test_nan_in_the_backward_...). No update on such a step.
                 raise FloatingPointError(f"minibatch {batch_index}: the loss is {loss} -- the run has diverged; no parameter was updated")
             error += loss * net.world / S
-            accuracy += 100.0 * correct / (bs * S)
+            labels = net.n_classes if getattr(net, "criterion", "nll") == "bce" else 1    # "bce" counts label hits: rows x S x D
+            accuracy += 100.0 * correct / (bs * S * labels)
             log_update = bool(self.log and opt.get("log_update") and net.mode == "lrt")
             net.update(opt, log=log_update)
             if log_update:                                                                # VBLinear.lua:149-164, per layer
@@ -143,6 +149,8 @@ class Main:
         # with opt.noise_var), the epistemic variance and, for gauss, the aleatoric one -- FusedMLP.predict_regression
         tau2 = opt.get("noise_var") if criterion == "mse" else None
         pred = {"devacc_pred": 0.0, "devnll_pred": 0.0, "dev_mi": 0.0}
+        if criterion == "bce":            # the multi-label predictive (FusedMLP.predict_labels)
+            pred = {"devll_pred": 0.0, "dev_label_acc": 0.0, "dev_exact_match": 0.0, "dev_label_mi": 0.0}
         if regression:
             pred = {"dev_epi_var": 0.0}
             if criterion == "gauss":
@@ -163,7 +171,7 @@ class Main:
         # minibatches on the device (FusedMLP.calibration, into=) gives `dev_ece`, `dev_mce`, `dev_brier`; opt.selective_coverages
         # adds `dev_acc@cov<c>`, the accuracy over the fraction c of the rows the predictive entropy ranks most certain
         # (FusedMLP.selective). Both need the R x C probabilities, which the predictive then keeps.
-        cal_bins = int(opt.get("calibration_bins") or 0) if (opt.get("predictive") and not regression) else 0
+        cal_bins = int(opt.get("calibration_bins") or 0) if (opt.get("predictive") and not regression and criterion != "bce") else 0
         cal = None
         for t0 in starts:
             inputs, targets = dataset.create_minibatch(t0, bs, n, opt.get("geometry"))
@@ -171,7 +179,16 @@ class Main:
             err, acc = net.test(x, t)
             accuracy += acc
             error += err
-            if opt.get("predictive") and regression:
+            if opt.get("predictive") and criterion == "bce":
+                if analytic:
+                    raise ValueError("opt.predictive = 'analytic' does not support criterion = 'bce' yet: use opt.predictive = True "
+                                     "(predict_labels)")
+                r = net.predict_labels(x, targets=t)
+                pred["devll_pred"] += r.log_lik
+                pred["dev_label_acc"] += r.label_accuracy
+                pred["dev_exact_match"] += r.exact_match
+                pred["dev_label_mi"] += float(r.mutual_info.double().mean())
+            elif opt.get("predictive") and regression:
                 if analytic:
                     r = net.predict_analytic(x, targets=t, noise_var=tau2)
                 elif qprobs:                                 # opt.quantile_probs: the same draws give the calibration too
