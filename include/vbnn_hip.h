@@ -83,7 +83,7 @@ int vbnn_debug_set(int key, int value);
  *   bits 8-15  CP   (tile backward: classes of the final weight kept in registers, 12 or 0)
  *   bits 16-17 the finish of the row-chunk partial sums: VBNN_HEAD_FINISH_NONE (a forward, or no sum asked for),
  *              _INLINE (the last arriver of the launch), _KERNEL (k_head_backward_finish follows)
- * Any other key: -1. Nothing here changes what is launched. */
+ * Any key but this one and VBNN_DEBUG_LAST_GEMM_FORM (below): -1. Nothing here changes what is launched. */
 #define VBNN_DEBUG_LAST_HEAD_FORM 11
 #define VBNN_HEAD_ENTRY_FORWARD 1
 #define VBNN_HEAD_ENTRY_SLOTS 2
@@ -94,6 +94,43 @@ int vbnn_debug_set(int key, int value);
 #define VBNN_HEAD_FINISH_INLINE 1
 #define VBNN_HEAD_FINISH_KERNEL 2
 #define VBNN_HEAD_FORM(entry, bf16, vec, full, cp, finish) ((entry) | ((bf16) << 4) | ((vec) << 5) | ((full) << 6) | ((cp) << 8) | ((finish) << 16))
+/* VBNN_DEBUG_LAST_GEMM_FORM (additive, ABI 6): which GEMM launch the LAST call of vbnn_forward, vbnn_grad_input,
+ * vbnn_acc_grad_parameters or vbnn_backward_pair chose in this process -- PROCESS-wide and host-side, written by the launcher where
+ * it has picked its kernel (after every return that launches nothing; a launcher that answers VBNN_ERR_UNSUPPORTED and lets its
+ * caller fall back leaves the value alone), 0 before the first. vbnn_backward_pair outside its one-launch sizes leaves the form of
+ * its second call, gradInput. Nothing on the device, and nothing that selects a kernel, reads it. The value:
+ *   bits 0-3   the kernel: VBNN_GEMM_KERNEL_V0 (the latency kernel, gemm_v0.h), _V0_PAIR (its backward-pair launch), _V1 (the
+ *              general kernel, gemm_v1.h), _V1_PAIR, _V2 (the pipelined kernel, gemm_v2.h), _V3 (the two-pass 256 x 256 kernel,
+ *              gemm_v3.h), _V3_SPLIT (its half-height pair-split launch)
+ *   bits 4-5   the tile. V0 / V0_PAIR: 0 = 16 x 16 (narrow), 1 = 16 x 32 (wide; the pair: of its gradInput problem). V1: 0 = 32 x 32,
+ *              1 = 64 x 64, 2 = 128 x 128. V2: 0 = 256 x 128, 1 = 128 x 128, 2 = 128 x 128 with the two-stage ring (two workgroups
+ *              per CU). Else 0.
+ *   bits 6-7   V2: the schedule / 2 (VBNN_DEBUG_V2_SCHEDULE 0, 2, 4 -> 0, 1, 2) after the tile's own limit. Else 0.
+ *   bit  8     DUAL: both accumulators of the LRT pair in one workgroup (0: one accumulator per workgroup)
+ *   bit  9     the pair split (V2, V3_SPLIT): the pair's two GEMMs in different workgroups of one grid
+ *   bits 10-11 the `part` handed to the functor (vbnn_dw_args.part: 0, 1, 2)
+ *   bit  12    A K-major        bit 13   B K-major   (0: K-contiguous, the packed form)
+ *   bits 14-15 SQ: 1 = B2 = B . B, 2 = A2 = A . A formed in registers (fp32), 0 = both squares given
+ *   bit  16    the row of ones (gradBias) synthesised by the kernel (fp32 K-major); 0 = stored in the operand, or none
+ *   bit  17    the operand type: 0 = f32, 1 = bf16
+ *   bit  18    fast_ok() of the epilogue functor at launch: whole tiles take the fast protocol, the others the guarded one
+ *              (the pair launches: of both functors)
+ *   bit  19    V3: the forward's fold between the passes in its serial form (VBNN_DEBUG_V3_FOLD_SERIAL)
+ *   bits 20-21 the family: VBNN_GEMM_CLASS_FWD, _DX, _DW (the pair launches: _DW, whose DUAL and row of ones they record) */
+#define VBNN_DEBUG_LAST_GEMM_FORM 13
+#define VBNN_GEMM_KERNEL_V0 1
+#define VBNN_GEMM_KERNEL_V0_PAIR 2
+#define VBNN_GEMM_KERNEL_V1 3
+#define VBNN_GEMM_KERNEL_V1_PAIR 4
+#define VBNN_GEMM_KERNEL_V2 5
+#define VBNN_GEMM_KERNEL_V3 6
+#define VBNN_GEMM_KERNEL_V3_SPLIT 7
+#define VBNN_GEMM_CLASS_FWD 1
+#define VBNN_GEMM_CLASS_DX 2
+#define VBNN_GEMM_CLASS_DW 3
+#define VBNN_GEMM_FORM(kernel, tile, sched, dual, psplit, part, ak, bk, sq, ones, bf16, fast, serial, cls)                        \
+    ((kernel) | ((tile) << 4) | ((sched) << 6) | ((dual) << 8) | ((psplit) << 9) | ((part) << 10) | ((ak) << 12) | ((bk) << 13) | \
+     ((sq) << 14) | ((ones) << 16) | ((bf16) << 17) | ((fast) << 18) | ((serial) << 19) | ((cls) << 20))
 int vbnn_debug_get(int key);
 
 /* 1 when a GEMM with an M x N output and contraction length K would take the K-major form of the two-pass kernel
@@ -295,7 +332,9 @@ typedef struct vbnn_dw_args {
     /* optional (fused total gradients only, dtype BF16): the packed operand shadows mu_s, var_s = exp(lvars) (O x ld_w,
      * as vbnn_prepare / vbnn_update leave them). When given, the epilogue reads mu and sigma^2 FROM THEM -- 4 B per weight
      * instead of 8, and no exp -- i.e. d/dlvars = (gv^T x.x) . s2 + KL'(s2), d/dmeans = g^T x + KL'(mu) with s2, mu the
-     * values the forward GEMMs multiplied by (bf16-rounded); means / lvars are then not read. NULL: fp32 means / lvars.
+     * values the forward GEMMs multiplied by (bf16-rounded); means / lvars are then not read -- except by gradSum (and the
+     * weight-noise d/dlvars), whose stdv stays exp(lvars / 2) of the fp32 parameter when the same call asks for it. NULL: fp32
+     * means / lvars.
      * REQUIRED by the K-major launches (x / g given, xT / gT NULL): their epilogue reads the shadows only, so a caller that
      * passes K-major operands without mu_s / var_s gets VBNN_ERR_INVALID -- keep the transposed operands for that case. */
     const void* mu_s; const void* var_s; int64_t ld_w;

@@ -33,6 +33,7 @@ def test_library_exports_every_declared_symbol():
     L.lib()
     assert L.lib().vbnn_abi_version() == 6
     assert "vbnn_debug_get" in names and L.lib().vbnn_debug_get(11) >= 0 and L.lib().vbnn_debug_get(0) == -1      # additive: still ABI 6
+    assert L.lib().vbnn_debug_get(13) >= 0 and L.lib().vbnn_debug_get(12) == -1 and L.lib().vbnn_debug_get(14) == -1  # VBNN_DEBUG_LAST_GEMM_FORM
 
 
 def test_no_gpu_is_an_error_not_a_fallback():

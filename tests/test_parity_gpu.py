@@ -33,6 +33,32 @@ def assert_close(got, want, tol, what):
     assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} off, max err {err.max():.3e} (tol at worst {np.max(tol):.3e})"
 
 
+GEMM_KERNELS = {0: "none", 1: "latency", 2: "latency pair", 3: "general", 4: "general pair", 5: "pipelined", 6: "two-pass", 7: "two-pass split"}
+
+
+def gemm_form():
+    """VBNN_DEBUG_LAST_GEMM_FORM (include/vbnn_hip.h) of the last GEMM launch: (kernel, A K-major, family 1 FWD / 2 DX / 3 DW, value)"""
+    from vbnn_amd import _lib as L
+    f = L.lib().vbnn_debug_get(13)
+    return f & 15, (f >> 12) & 1, (f >> 20) & 3, f
+
+
+def check_forced_kernel(forced, what):
+    """After a launch of the MODULE path under VBNN_DEBUG_GEMM_KERNEL = forced: 1 and 2 take every bf16 launch (packed pitches are
+    multiples of 64), asserted. 3 means "the two-pass kernel whenever the shape and outputs allow it": whole 256 x 256 tiles AND
+    the fused outputs alone -- the module path asks for y / gx / gradWeight in fp32, so today it runs another kernel there, and
+    this says which. (The two-pass kernel's own cases: tests/test_gemm_forms_gpu.py.)"""
+    k, _, _, f = gemm_form()
+    if forced == 1:
+        assert k == 3, f"{what}: forced the general kernel, ran the {GEMM_KERNELS[k]} kernel"
+    elif forced == 2:
+        assert k == 5, f"{what}: forced the pipelined kernel, ran the {GEMM_KERNELS[k]} kernel"
+    else:
+        assert k in (3, 5, 6), f"{what}: ran the {GEMM_KERNELS[k]} kernel (form {f:#x})"
+        if k != 6:
+            print(f"{what}: VBNN_DEBUG_GEMM_KERNEL = {forced} did not take this launch, the {GEMM_KERNELS[k]} kernel ran (form {f:#x})")
+
+
 @pytest.fixture(scope="module")
 def nnmod():
     from vbnn_amd import nn
@@ -570,6 +596,8 @@ def test_split_two_pass_gradient_against_rounding_emulation(oracle, nnmod, hidde
         for _ in range(3):
             eng.resetGradients(); eng.run(eng_x(eng, oracle, N, I0), eng_t(N))
             assert torch.equal(eng.grads, g1)
+        k, ak, fam, f = gemm_form()                      # the step's last GEMM: an accGradParameters on the split launch
+        assert k == 7 and ak and fam == 3, f"the last launch was the {GEMM_KERNELS[k]} kernel (form {f:#x}), not the split launch"
     finally:
         L.check(L.lib().vbnn_debug_set(8, -1))
 
@@ -640,6 +668,8 @@ def test_full_size_wide_step_against_rounding_emulation(oracle, nnmod):
     2e-3 Frobenius / 2e-2 of the largest entry, as the small cases."""
     eng = _check_bf16_step_against_emulation(oracle, [4096, 4096], 784, 4096, True)
     assert eng.vb[1].dw_km and eng.vb[1].dx_km and eng.vb[0].dw_km      # the K-major launches were the ones checked
+    k, ak, fam, f = gemm_form()                                         # the step's last GEMM: a K-major accGradParameters
+    assert k in (6, 7) and ak and fam == 3, f"the last launch was the {GEMM_KERNELS[k]} kernel (form {f:#x})"
 
 
 def test_full_size_layer2_backward_launches_against_float64(oracle, nnmod):
@@ -676,6 +706,8 @@ def test_full_size_layer2_backward_launches_against_float64(oracle, nnmod):
     lib, ctx = L.lib(), eng.ctx.h
     # ---- updateGradInput
     L.check(lib.vbnn_grad_input(ctx, eng.code, C.byref(eng._dx_args(1, N))))
+    k, ak, fam, f = gemm_form()
+    assert k == 6 and ak and fam == 2, f"gradInput ran the {GEMM_KERNELS[k]} kernel (form {f:#x}), not the K-major two-pass launch"
     t1 = g.astype(f8) @ mu
     t2 = 2 * x.astype(f8) * (gv.astype(f8) @ var)
     want = np.where(x > 0, t1 + t2, 0.0)
@@ -688,6 +720,8 @@ def test_full_size_layer2_backward_launches_against_float64(oracle, nnmod):
     assert (np.abs(got_gv - want_gv) <= (tol + 2.0 ** -8 * np.abs(want)) * np.abs(rp) + 2.0 ** -8 * np.abs(want_gv)).all()
     # ---- accGradParameters with the fused KL gradient
     L.check(lib.vbnn_acc_grad_parameters(ctx, eng.code, C.byref(eng._dw_args(1, N, 0))))
+    k, ak, fam, f = gemm_form()
+    assert k == 6 and ak and fam == 3, f"accGradParameters ran the {GEMM_KERNELS[k]} kernel (form {f:#x}), not the K-major two-pass launch"
     gw = g.astype(f8).T @ x.astype(f8)
     gs2 = gv.astype(f8).T @ x2
     var32 = np.exp(lv).astype(f8)
@@ -749,8 +783,11 @@ def _filled(nnmod, rows, cols, stream, layer, draw, row0):
                 ids=["general-kernel", "pipelined-256x128", "pipelined-128x128", "pipelined-128x128-pairs",
                      "two-pass-256x256", "pipelined-256x128-pairsplit"])
 def gemm_kernel(request, nnmod):
-    """Run a bf16 test once per GEMM kernel (gemm_v1.h / gemm_v2.h in its block tiles and with the pair split / gemm_v3.h),
-    whatever the shape heuristics say."""
+    """Run a bf16 test once per SETTING of the kernel keys (gemm_v1.h / gemm_v2.h in its block tiles and with the pair split /
+    gemm_v3.h), whatever the shape heuristics say. Settings 1 and 2 take every launch of the module path; the last setting,
+    "two-pass-256x256", only asks for gemm_v3.h where shape and outputs allow it, and the module path's fp32 outputs never do:
+    those cases run the general or the pipelined kernel (check_forced_kernel prints which). The two-pass kernel is held by
+    tests/test_gemm_forms_gpu.py and by the engine tests."""
     from vbnn_amd import _lib as L
     kernel, tile, psplit = request.param
     L.check(L.lib().vbnn_debug_set(0, kernel))
@@ -775,8 +812,10 @@ def test_bf16_gemm_exact_on_integers(nnmod, gemm_kernel, N, I, O):
     g = rng.integers(-2, 3, (N, O)).astype(np.float32)
     m = nnmod.Linear(I, O, dict(dtype="bf16"))
     m.weight.copy_(dev(W)); m.bias.copy_(dev(b))
-    for _ in range(3):                                   # repeated launches: a race would not repeat exactly
+    for it in range(3):                                  # repeated launches: a race would not repeat exactly
         y = host(m.updateOutput(dev(x)))
+        if it == 0:
+            check_forced_kernel(gemm_kernel[0], f"forward {N}x{I}x{O}")
         assert np.array_equal(y, x @ W.T + b)
         m.gradWeight.zero_(); m.gradBias.zero_()
         gx = host(m.backward(dev(x), dev(g), 1.0))
@@ -787,8 +826,10 @@ def test_bf16_gemm_exact_on_integers(nnmod, gemm_kernel, N, I, O):
 
 @pytest.mark.parametrize("N,I,O", [(256, 64, 256), (256, 128, 512), (512, 192, 256), (256, 256, 256), (512, 320, 256)])
 def test_two_pass_kernel_short_k(nnmod, N, I, O):
-    """gemm_v3's peeled pipeline (prologue of two steps, unguarded main loop, guarded last two steps) at 1, 2, 3, 4 and 5
-    K steps in each of its three roles (forced with debug key 0 = 3; the shape rule would never pick it for these)."""
+    """nn.Linear at whole 256 x 256 tiles and 1, 2, 3, 4 and 5 K steps under debug key 0 = 3. Written for gemm_v3's peeled pipeline
+    (prologue of two steps, unguarded main loop, guarded last two steps) -- but the module path's fp32 outputs keep these launches
+    off the two-pass kernel (check_forced_kernel prints which kernel ran): what this holds is the fall-back of key 3. The peeled
+    pipeline at these K in each of its three roles is run by tests/test_gemm_forms_gpu.py::test_two_pass_kernel."""
     from vbnn_amd import _lib as L
     L.check(L.lib().vbnn_debug_set(0, 3))
     try:
@@ -799,8 +840,11 @@ def test_two_pass_kernel_short_k(nnmod, N, I, O):
         g = rng.integers(-2, 3, (N, O)).astype(np.float32)
         m = nnmod.Linear(I, O, dict(dtype="bf16"))
         m.weight.copy_(dev(W)); m.bias.copy_(dev(b))
-        for _ in range(2):
-            assert np.array_equal(host(m.updateOutput(dev(x))), x @ W.T + b)
+        for it in range(2):
+            y = host(m.updateOutput(dev(x)))
+            if it == 0:
+                check_forced_kernel(3, f"forward {N}x{I}x{O}")
+            assert np.array_equal(y, x @ W.T + b)
             m.gradWeight.zero_(); m.gradBias.zero_()
             assert np.array_equal(host(m.backward(dev(x), dev(g), 1.0)), g @ W)
             assert np.array_equal(host(m.gradWeight), g.T @ x)
@@ -846,6 +890,7 @@ def test_layer_bf16_against_rounded_operands(nnmod, oracle, gemm_kernel, N, I, O
     g = rng.normal(0, 1.0 / N, (N, O)).astype(np.float32)
     m.sample()
     y = host(m.updateOutput(dev(x))).astype(np.float64)
+    check_forced_kernel(gemm_kernel[0], f"LRT forward {N}x{I}x{O}")
     zeta = oracle.fill_normal(N, O, SEED, 2, 0, m.draw, 0).astype(np.float64)
     xr, mur = rb(x).astype(np.float64), rb(om.means).astype(np.float64)
     x2r = rb(rb(x) * rb(x)).astype(np.float64)

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include "../../include/vbnn_hip.h"
 #include "../../include/vbnn_philox.h"
 
@@ -73,6 +74,20 @@ constexpr int VBNN_CNT_HEAD_FWD = 0, VBNN_CNT_PREDICT = 1, VBNN_CNT_TILES = 16, 
 
 void vbnn_set_error(const char* fmt, ...);
 inline int g_last_head_form = 0; // vbnn_debug_get key 11 (VBNN_DEBUG_LAST_HEAD_FORM): VBNN_HEAD_FORM(...) of the last head launch chosen by this process
+inline int g_last_gemm_form = 0; // vbnn_debug_get key 13 (VBNN_DEBUG_LAST_GEMM_FORM): VBNN_GEMM_FORM(...) of the last GEMM launch chosen by this process
+// The launchers of gemm_v0.h .. gemm_v3.h call this where they have picked their kernel, after the last return that launches
+// nothing: host-side, one store, read by nothing that selects a kernel. The functor's class and `part` are taken from it when it
+// has them (EpiFwd / EpiDx / EpiDw: CLASS; EpiDw: part); a lab functor without them records 0.
+template <class Epi, class = void> struct vbnn_epi_class { static constexpr int value = 0; };
+template <class Epi> struct vbnn_epi_class<Epi, std::void_t<decltype(Epi::CLASS)>> { static constexpr int value = Epi::CLASS; };
+template <class Epi, class = void> struct vbnn_epi_part { static int of(const Epi&) { return 0; } };
+template <class Epi> struct vbnn_epi_part<Epi, std::void_t<decltype(std::declval<const Epi&>().part)>> { static int of(const Epi& e) { return e.part; } };
+template <typename T, class Epi>
+static inline void vbnn_note_gemm_form(int kernel, int tile, int sched, bool dual, bool psplit, bool ak, bool bk, int sq, bool ones,
+                                       bool serial, const Epi& epi) {
+    g_last_gemm_form = VBNN_GEMM_FORM(kernel, tile, sched, dual ? 1 : 0, psplit ? 1 : 0, vbnn_epi_part<Epi>::of(epi), ak ? 1 : 0, bk ? 1 : 0, sq,
+                                      ones ? 1 : 0, sizeof(T) == 2 ? 1 : 0, epi.fast_ok() ? 1 : 0, serial ? 1 : 0, vbnn_epi_class<Epi>::value);
+}
 inline int g_head_stream = -1;   // vbnn_debug_set key 10 (VBNN_DEBUG_HEAD_BACKWARD): the head's backward -- -1 by shape, 0 tile form, 1 streaming form whenever the operands allow
 
 // hipFuncSetAttribute (the dynamic-LDS opt-in of the pipelined kernels) is per DEVICE: a per-instantiation flag that

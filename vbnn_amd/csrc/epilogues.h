@@ -70,6 +70,7 @@ struct EpiFwd {
     // head sums the slots in order). The head's forward then never re-reads h (33 MB at 4096 x 4096).
     const T* head_w3 = nullptr; int64_t head_ld_w = 0; int head_C = 0; float* head_slots = nullptr;
     static constexpr bool HEAD = sizeof(T) == 2;
+    static constexpr int CLASS = VBNN_GEMM_CLASS_FWD;   // (host-side: vbnn_note_gemm_form)
 
     static constexpr bool SPLITTABLE = false;     // every output needs both GEMMs of the pair
     static constexpr bool EDGE_FAST = false;      // ragged wave tiles take the guarded form
@@ -336,6 +337,7 @@ struct EpiDx {
     static constexpr bool SPLITTABLE = false;
     static constexpr bool EDGE_FAST = false;
     static constexpr bool HEAD = false;
+    static constexpr int CLASS = VBNN_GEMM_CLASS_DX;
     __device__ __forceinline__ void bind_draw() {}                 // (no noise in gradInput: r comes from the forward)
     __host__ __device__ __forceinline__ bool has_draw_dev() const { return false; }
     __device__ __forceinline__ void edge_row(int, float) const {}
@@ -488,6 +490,7 @@ struct EpiDw {
     int part = 0;
     static constexpr bool SPLITTABLE = true;
     static constexpr bool HEAD = false;
+    static constexpr int CLASS = VBNN_GEMM_CLASS_DW;
     __device__ __forceinline__ void set_part(int p) { part = p; }
     __device__ __forceinline__ void bind_draw() { if (draw_dev) draw += *draw_dev; }
     __host__ __device__ __forceinline__ bool has_draw_dev() const { return draw_dev != nullptr; }
@@ -532,6 +535,14 @@ struct EpiDw {
         }
         if (var_s && want_lv && (grad_mu || grad_lv)) {
             load4<bf16_t>(var_s + (int64_t)n * ld_w + m, var, valid, true);
+            // stdv stays exp(lvars / 2) of the fp32 parameter (vbnn_dw_args.gradSum): the shadows replace mu and sigma^2 of the
+            // fused total gradients alone. (Left at 0 here, a call that asked for gradSum AND gave the shadows got gradSum += 0.)
+            if (lvars && (gradSum || !lrt)) {
+                float lv4[4];
+                load4<float>(lvars + base, lv4, valid, vec);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (j < valid) sd[j] = sqrtf(expf(lv4[j]));
+            }
         } else if (lvars && want_lv) {
             float lv4[4];
             load4<float>(lvars + base, lv4, valid, vec);

@@ -16,7 +16,11 @@ extern "C" int vbnn_debug_set(int key, int value) {
     vbnn_set_error("vbnn_debug_set: unknown key %d / value %d", key, value);
     return VBNN_ERR_INVALID;
 }
-extern "C" int vbnn_debug_get(int key) { return key == VBNN_DEBUG_LAST_HEAD_FORM ? g_last_head_form : -1; }
+extern "C" int vbnn_debug_get(int key) {
+    if (key == VBNN_DEBUG_LAST_HEAD_FORM) return g_last_head_form;
+    if (key == VBNN_DEBUG_LAST_GEMM_FORM) return g_last_gemm_form;
+    return -1;
+}
 
 extern "C" int vbnn_kmajor_supported(int64_t M, int64_t N, int64_t K) { return kmajor_selected(M, N, K) ? 1 : 0; }
 extern "C" int vbnn_ctx_kmajor_supported(vbnn_ctx* ctx, int64_t M, int64_t N, int64_t K) {

@@ -303,10 +303,12 @@ static int launch_gemm_v0(hipStream_t stream, const float* A, const float* A2, i
     // forward / gradInput forms: 16 x 32 when that fills the chip (lab, 784-400-400-10 at batch 256: 6.6 vs 7.5 us, 4.9 vs 5.2)
     if (!(TA && TB) && v0_wide_tile(M, N)) {
         const int gx = (M + 15) / 16, gy = (N + 31) / 32;
+        vbnn_note_gemm_form<float>(VBNN_GEMM_KERNEL_V0, 1, 0, DUAL, false, TA, TB, SQ, ones_row >= 0, false, epi);
         hipLaunchKernelGGL((gemm_nt_v0<1, 2, DUAL, Epi, TA, TB, SQ>), dim3(gx * gy), dim3(64 * V0_W), 0, stream, A, A2, lda, B, B2, ldb, M, N, K,
                            ones_row, gx, epi);
     } else {
         const int gx = (M + 15) / 16, gy = (N + 15) / 16;
+        vbnn_note_gemm_form<float>(VBNN_GEMM_KERNEL_V0, 0, 0, DUAL, false, TA, TB, SQ, ones_row >= 0, false, epi);
         hipLaunchKernelGGL((gemm_nt_v0<1, 1, DUAL, Epi, TA, TB, SQ>), dim3(gx * gy), dim3(64 * V0_W), 0, stream, A, A2, lda, B, B2, ldb, M, N, K,
                            ones_row, gx, epi);
     }

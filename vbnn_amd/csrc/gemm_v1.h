@@ -377,6 +377,7 @@ static int launch_gemm_v1_form(hipStream_t stream, const T* A, const T* A2, int6
         const int Kp = (K + KE - 1) / KE * KE;
         if (!need(Kp)) return VBNN_ERR_INVALID;
         dim3 grid((M + 127) / 128, (N + 127) / 128);
+        vbnn_note_gemm_form<T>(VBNN_GEMM_KERNEL_V1, 2, 0, DUAL, false, TA, TB, SQ, ones_row >= 0, false, epi);
         hipLaunchKernelGGL((gemm_nt_v1<T, DUAL, 4, 1, Epi, TA, TB, SQ>), grid, dim3(256), 0, stream, A, A2, lda, B, B2, ldb, M, N, Kp, K, ones_row, epi);
     } else {
         constexpr int KS = 2;                                     // 128 B of K per row per step: 32 f32 / 64 bf16
@@ -386,6 +387,7 @@ static int launch_gemm_v1_form(hipStream_t stream, const T* A, const T* A2, int6
         const long blocks64 = (long)((M + 63) / 64) * ((N + 63) / 64);
         if (blocks64 >= 96) {
             dim3 grid((M + 63) / 64, (N + 63) / 64);
+            vbnn_note_gemm_form<T>(VBNN_GEMM_KERNEL_V1, 1, 0, DUAL, false, TA, TB, SQ, ones_row >= 0, false, epi);
             hipLaunchKernelGGL((gemm_nt_v1<T, DUAL, 2, KS, Epi, TA, TB, SQ>), grid, dim3(256), 0, stream, A, A2, lda, B, B2, ldb, M, N, Kp, K, ones_row, epi);
         } else {        // latency-bound sizes (the 256 x 400 outputs of the small MLP): the latency kernel, or 32 x 32 tiles, 4x the blocks
             if constexpr (sizeof(T) == 4) {
@@ -395,6 +397,7 @@ static int launch_gemm_v1_form(hipStream_t stream, const T* A, const T* A2, int6
                 }
             }
             dim3 grid((M + 31) / 32, (N + 31) / 32);
+            vbnn_note_gemm_form<T>(VBNN_GEMM_KERNEL_V1, 0, 0, DUAL, false, TA, TB, SQ, ones_row >= 0, false, epi);
             hipLaunchKernelGGL((gemm_nt_v1<T, DUAL, 1, KS, Epi, TA, TB, SQ>), grid, dim3(256), 0, stream, A, A2, lda, B, B2, ldb, M, N, Kp, K, ones_row, epi);
         }
     }
@@ -442,6 +445,8 @@ static int launch_gemm_v1_pair(hipStream_t stream, const float* A, const float* 
         const int gxa = (M + 15) / 16, gya = wide ? (N + 31) / 32 : (N + 15) / 16, gxb = (M2 + 15) / 16, gyb = (N2 + 15) / 16;
         V0Problem<EpiA> qa{A, A2, lda, B, B2, ldb, M, N, K, -1, gxa, gxa * gya, epi_a};
         V0Problem<EpiB> qb{xA, nullptr, ldx, gB, gvB, ldg, M2, N2, K2, ones_row, gxb, gxb * gyb, epi_b};
+        vbnn_note_gemm_form<float>(VBNN_GEMM_KERNEL_V0_PAIR, wide ? 1 : 0, 0, DUAL, false, true, true, DUAL ? 2 : 0, ones_row >= 0, false, epi_b);
+        if (!epi_a.fast_ok()) g_last_gemm_form &= ~VBNN_GEMM_FORM(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0);      // bit 18: of both functors
         if (wide)
             hipLaunchKernelGGL((gemm_nt_v0_pair<1, 2, DUAL, EpiA, true, false, 0, 1, 1, DUAL, EpiB, true, true, (DUAL ? 2 : 0)>),
                                dim3(qa.blocks + qb.blocks), dim3(64 * V0_W), 0, stream, qa, qb);
@@ -455,6 +460,8 @@ static int launch_gemm_v1_pair(hipStream_t stream, const float* A, const float* 
     V1Problem<float, EpiB> pb{xA, nullptr, ldx, gB, gvB, ldg, M2, N2, (K2 + KE2 - 1) / KE2 * KE2, K2, ones_row, (M2 + 31) / 32,
                               ((M2 + 31) / 32) * ((N2 + 31) / 32), epi_b};
     if (ldb < pa.Kp && ldb < K) return VBNN_ERR_UNSUPPORTED;
+    vbnn_note_gemm_form<float>(VBNN_GEMM_KERNEL_V1_PAIR, 0, 0, DUAL, false, true, true, DUAL ? 2 : 0, ones_row >= 0, false, epi_b);
+    if (!epi_a.fast_ok()) g_last_gemm_form &= ~VBNN_GEMM_FORM(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0);          // bit 18: of both functors
     hipLaunchKernelGGL((gemm_nt_v1_pair<float, DUAL, EpiA, true, false, 0, DUAL, EpiB, true, true, (DUAL ? 2 : 0)>), dim3(pa.blocks + pb.blocks),
                        dim3(256), 0, stream, pa, pb);
     return vbnn_check_launch("gemm_nt_v1_pair");

@@ -705,6 +705,9 @@ static int launch_gemm_v2(vbnn_ctx* ctx, const T* A, const T* A2, int64_t lda, c
         Epi epi_ = epi;
         int psplit_ = psplit ? 1 : 0;
         void* args[] = {&a, &a2, &lda_, &b, &b2, &ldb_, &M_, &N_, &nk_, &tm_, &tn_, &psplit_, &epi_};
+        // (the K-major pair split has the schedules 2 and 4 only: asked for 0 it runs 2, and that is what is recorded)
+        vbnn_note_gemm_form<T>(VBNN_GEMM_KERNEL_V2, vi0, (psplit && kmajor && sched != 4) ? 1 : si, DUAL && !psplit, psplit, kmajor, kmajor, 0,
+                               false, false, epi);
         hipError_t e = hipLaunchKernel(kern, dim3(tiles_m * tiles_n * (psplit ? 2 : 1)), dim3(threads), args, lds_bytes, stream);
         if (e != hipSuccess) { vbnn_set_error("launch of gemm_nt_v2 failed: %s", hipGetErrorString(e)); return VBNN_ERR_HIP; }
         return vbnn_check_launch("gemm_nt_v2");

@@ -1057,6 +1057,7 @@ static int launch_gemm_v3(vbnn_ctx* ctx, const T* A, const T* A2, int64_t lda, c
         int64_t lda_ = lda, ldb_ = ldb;
         Epi epi_ = epi;
         void* args[] = {&a, &a2, &lda_, &b, &b2, &ldb_, &M_, &N_, &nk_, &tm_, &tn_, &epi_};
+        vbnn_note_gemm_form<T>(VBNN_GEMM_KERNEL_V3, 0, 0, DUAL, false, AK, BK, 0, false, form == 1, epi);
         hipError_t e = hipLaunchKernel(kern, dim3(tiles_m * tiles_n), dim3(512), args, V3_LDS, ctx->stream);
         if (e != hipSuccess) { vbnn_set_error("launch of gemm_nt_v3 failed: %s", hipGetErrorString(e)); return VBNN_ERR_HIP; }
         return vbnn_check_launch("gemm_nt_v3");
@@ -1105,6 +1106,7 @@ static int launch_gemm_v3_split(vbnn_ctx* ctx, const T* A, const T* A2, int64_t 
         int64_t lda_ = lda, ldb_ = ldb;
         Epi epi_ = epi;
         void* args[] = {&a, &a2, &lda_, &b, &b2, &ldb_, &M_, &N_, &nk_, &tm_, &tn_, &epi_};
+        vbnn_note_gemm_form<T>(VBNN_GEMM_KERNEL_V3_SPLIT, 0, 0, false, true, true, true, 0, false, false, epi);
         hipError_t e = hipLaunchKernel(kern, dim3(tiles_m * tiles_n * 2), dim3(512), args, V3_LDS, ctx->stream);
         if (e != hipSuccess) { vbnn_set_error("launch of gemm_nt_v3 (pair split) failed: %s", hipGetErrorString(e)); return VBNN_ERR_HIP; }
         return vbnn_check_launch("gemm_nt_v3 pair split");
