@@ -178,14 +178,18 @@ int vbnn_buf_download(vbnn_ctx* ctx, void* dst_host, const void* src_dev, size_t
 /* rows x cols standard normals (include/vbnn_philox.h contract):
  * out[r][c] = lane c&3 of vbnn_normal4(seed, stream, layer, draw, row0 + r, c >> 2), times `scale`.
  * Replaces randomkit.normal at VBLinear.lua:26-28 (means init) and mlp.lua:53 (He init);
- * also the synthetic-input generator of bench.py. */
+ * also the synthetic-input generator of bench.py.
+ * Held by tests/test_sweeps_gpu.py: out[r][c] is bit for bit fl(z scale), ONE fp32 multiply of the contract's normal; the row
+ * word of the counter is (uint32_t)(row0 + r), so rows wrap at 2^32. Elements c >= cols of a row (the pitch's pads) are never
+ * written. `out` / `ld` may be anything: 16-byte stores when out is 16-byte aligned and ld % 4 == 0, scalar stores otherwise. */
 int vbnn_fill_normal(vbnn_ctx* ctx, float* out, int64_t rows, int64_t cols, int64_t ld,
                      uint64_t seed, uint32_t stream, uint32_t layer, uint32_t draw, int64_t row0,
                      float scale);
 /* The same normals in the form the bf16 forward draws them: the same Philox words, Box-Muller on them by the hardware's
  * log2 / sqrt / sin / cos instead of the contract's bit-exact polynomial forms (csrc/common.h, vbnn_normal4_hw): equal to
  * vbnn_fill_normal's to a few 1e-7 absolute, a quarter of the instructions. The fp32 path (held sample for sample against the
- * oracle) draws the exact form; this entry exists so that a host or a test can see exactly what a bf16 forward used. */
+ * oracle) draws the exact form; this entry exists so that a host or a test can see exactly what a bf16 forward used.
+ * Held to |out - z scale| <= 2e-6 |scale| + 2^-24 |z scale| against the contract's z; pads and alignment as vbnn_fill_normal. */
 int vbnn_fill_normal_hw(vbnn_ctx* ctx, float* out, int64_t rows, int64_t cols, int64_t ld,
                         uint64_t seed, uint32_t stream, uint32_t layer, uint32_t draw, int64_t row0,
                         float scale);
@@ -201,13 +205,22 @@ int vbnn_box_muller_forms(vbnn_ctx* ctx, const uint32_t* x0, const uint32_t* x1,
  *   stats[1] = sum(lvars)
  *   stats[2] = var_hat (as double)  -- read by later kernels on the device, no host sync
  * Optional caches (NULL to skip), exactly the reference's: vars (:78), stdv (:79), mu_sqe (:82).
- * `stats` is a device array of 4 doubles. */
+ * `stats` is a device array of 4 doubles; stats[3] = W.
+ * Held by tests/test_sweeps_gpu.py. Op for op in fp32 (no contraction): v = expf(l) (within 2 ulp of the exact exponential: the
+ * one figure that is bounded, not bitwise), stdv = sqrtf(v) (the correctly rounded root of the stored vars), mu_sqe = fl(m m);
+ * a term of stats[0] is fl(v + fl(m m)) widened to double; the sums are double, in an order that is fixed for a given W, and are
+ * held to 1e-10 of the sum of their terms' magnitudes; stats[2] = (1 / W) stats[0] in double. means, lvars and the three caches
+ * take 16-byte accesses when ALL that are given are 16-byte aligned, and 4-byte accesses otherwise (any float alignment works). */
 int vbnn_compute_prior(vbnn_ctx* ctx, const float* means, const float* lvars, int64_t W,
                        float* vars, float* stdv, float* mu_sqe, double* stats);
 
 /* VBLinear:sample (VBLinear.lua:49-64): weight = means + stdv (.) e, e ~ N(0,1) of shape O x I
  * regenerated from the Philox counter (stream EPS). e_out may be NULL (the reference keeps
- * self.e; the kernels never need it stored). stdv == NULL: use exp(lvars/2) of `lvars`. */
+ * self.e; the kernels never need it stored). stdv == NULL: use exp(lvars/2) of `lvars`.
+ * Held by tests/test_sweeps_gpu.py: e_out is the contract's normal of (seed, EPS, layer, draw, row o, quad i >> 2) bit for bit;
+ * weight = fl(means + fl(sd e)), two fp32 roundings, bit for bit when stdv is given; without it sd = sqrtf(expf(lvars)), expf
+ * within 2 ulp. The five pointers take 16-byte accesses when I % 4 == 0 and all that are given are 16-byte aligned, 4-byte
+ * accesses otherwise. */
 int vbnn_wn_sample(vbnn_ctx* ctx, const float* means, const float* stdv, const float* lvars,
                    float* weight, float* e_out, int64_t O, int64_t I,
                    uint64_t seed, uint32_t layer, uint32_t draw);
@@ -216,7 +229,13 @@ int vbnn_wn_sample(vbnn_ctx* ctx, const float* means, const float* stdv, const f
  *   f = COPY | EXP | SQUARE | MUL (src * src2) | RELU | RELU_SQUARE;
  * dst is rows x ld_dst, dstT (optional) is the transpose, cols x ld_dstT. Pads are not
  * written (keep them zero). Produces every GEMM operand of the module-level path:
- * mu/sigma^2 shadows, x and x.x, g and g.r. */
+ * mu/sigma^2 shadows, x and x.x, g and g.r.
+ * Held by tests/test_sweeps_gpu.py, every function x dtype x {dst, dstT, both}: COPY, MUL, RELU are T(fl(f)) bit for bit; SQUARE
+ * and RELU_SQUARE square the value AFTER rounding it to T (T(fl(T(h)^2)), what the GEMM epilogues produce); EXP is expf, within
+ * 2 ulp before the rounding to T. dstT holds the very values of dst. RELU is fmaxf(a, 0): a NaN gives +0 (RELU_SQUARE: +0), and
+ * -0.0 gives +0 (IEEE 754 leaves that sign open; gfx950's maximum orders -0 below +0), as vbnn_relu_forward. Accesses are element-wise:
+ * src, ld_src and both outputs may have any alignment and pitch; elements c >= cols of a dst row and r >= rows of a dstT row
+ * are never written. */
 int vbnn_pack(vbnn_ctx* ctx, int dtype, int func, const float* src, const float* src2, int64_t ld_src,
               int64_t rows, int64_t cols, void* dst, int64_t ld_dst, void* dstT, int64_t ld_dstT);
 
@@ -364,7 +383,14 @@ int vbnn_acc_grad_bias(vbnn_ctx* ctx, int dtype, const void* g, int64_t ld_g, in
 
 /* Per-step parameter sweep of the fused path: one read of means/lvars writes the packed GEMM
  * shadows mu_s, var_s = exp(lvars) (O x ld_w) and, if asked, their transposes (I x ld_wT), and the
- * statistics of VBLinear:compute_prior (VBLinear.lua:77-88) into stats[0..3] as vbnn_compute_prior. */
+ * statistics of VBLinear:compute_prior (VBLinear.lua:77-88) into stats[0..3] as vbnn_compute_prior.
+ * Held by tests/test_sweeps_gpu.py (this entry and vbnn_prepare, which leave the same bits): mu_s = T(means) bit for bit;
+ * var_s = T(expf(lvars)), expf within 2 ulp; the transposes hold the very values of the row-major shadows; the statistics as
+ * vbnn_compute_prior states them, whichever form the sweep takes (64 x 64 tiles, or flat when no transposes are asked for).
+ * ALIGNMENT. mu_s / var_s are written with 4-element vector stores unconditionally: their bases must be 16-byte aligned and
+ * ld_w a multiple of 4 elements (the convention is VBNN_KPAD). muT_s / varT_s take vector stores when ld_wT % 4 == 0 (their
+ * bases aligned likewise) and element stores otherwise. means / lvars take 16-byte loads when I % 4 == 0 and both are 16-byte
+ * aligned, 4-byte loads otherwise. Pad elements (c >= I of a shadow row, r >= O of a transposed row) are never written. */
 int vbnn_prep_layer(vbnn_ctx* ctx, int dtype, const float* means, const float* lvars, int64_t O, int64_t I,
                     void* mu_s, void* var_s, int64_t ld_w, void* muT_s, void* varT_s, int64_t ld_wT,
                     double* stats);
@@ -372,7 +398,9 @@ int vbnn_prep_layer(vbnn_ctx* ctx, int dtype, const float* means, const float* l
 /* The same sweep for every VB layer of a model in ONE call (n_layers <= 8), plus optionally the plain packing of one
  * more small f32 matrix (the final nn.Linear's weight, mlp.lua:29: dst rows x ld_dst and its transpose cols x
  * ld_dstT, either may be NULL): one sweep kernel per layer and a single finish kernel for all the statistics and the
- * extra matrix -- two launches fewer per step than n_layers x vbnn_prep_layer + vbnn_pack. */
+ * extra matrix -- two launches fewer per step than n_layers x vbnn_prep_layer + vbnn_pack.
+ * Each layer is held to vbnn_prep_layer's contract (alignment included) and its four statistics are its own. The extra matrix
+ * is T(src) bit for bit in dst and in dstT, each with its own pitch, stored element-wise (any alignment); pads are not written. */
 typedef struct vbnn_prep_desc {
     const float* means; const float* lvars; int64_t O, I;
     void* mu_s; void* var_s; int64_t ld_w;
@@ -390,7 +418,11 @@ int vbnn_prepare(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prep_desc* l
 /* VBLinear:compute_mugrads (VBLinear.lua:90-93): gradWeight /= S in place; lcg = means / (B var_hat).
  * VBLinear:compute_vargrads (:95-98): gradSum = gradSum / (2S) . stdv in place;
  *                                      lcg = ((-1/vars + 1/var_hat) / (2B)) . vars.
- * var_hat is read from stats[2] on the device. vars/stdv NULL: derived from lvars. */
+ * var_hat is read from stats[2] on the device. vars/stdv NULL: derived from lvars.
+ * Held by tests/test_sweeps_gpu.py, bit for bit, in this fp32 order: den = (float)((double) B stats[2]); lcg = means / den;
+ * gradWeight = gradWeight / S.  inv_vh = (float)(1.0 / stats[2]); a = -(1 / v) + inv_vh; lcg = (a / (2 B)) v;
+ * gradSum = (gradSum / (2 S)) stdv. Without vars / stdv: v = expf(lvars) (within 2 ulp), stdv = sqrtf(v). Either output may
+ * be NULL. Accesses are 4-byte: any float alignment. */
 int vbnn_compute_mugrads(vbnn_ctx* ctx, const float* means, const double* stats, float B, float S,
                          float* gradWeight, float* lcg, int64_t W);
 int vbnn_compute_vargrads(vbnn_ctx* ctx, const float* lvars, const float* vars, const float* stdv,
@@ -400,7 +432,11 @@ int vbnn_compute_vargrads(vbnn_ctx* ctx, const float* lvars, const float* vars, 
  * lc_sum_dev[0] = sum_w [log sqrt(var_hat) - log sqrt(vars) + (mu_sqe + vars - var_hat) / (2 var_hat)] / B.
  * lc_elem (optional) receives the per-weight tensor the Lua method returns.
  * vars / mu_sqe: the caches of the last compute_prior (the reference reads exactly those, so its
- * LC is one optimiser step stale, main.lua:174-177); NULL: derive from means / lvars. */
+ * LC is one optimiser step stale, main.lua:174-177); NULL: derive from means / lvars.
+ * Held by tests/test_sweeps_gpu.py. Per weight, in fp32: first = -logf(sqrtf(v)) + (float) log(sqrt(var_hat));
+ * second = (q + (v - (float) var_hat)) / (2 (float) var_hat); lc = (first + second) (1 / B) -- within an ABSOLUTE bound derived
+ * from these roundings (tests/_sweeps_np.py), meaningful where the halves cancel (a fresh layer). The sum is the double sum of
+ * those very fp32 elements (to 1e-10 of their magnitudes) and the same bits with and without lc_elem. 4-byte accesses. */
 int vbnn_calc_lc(vbnn_ctx* ctx, const float* means, const float* lvars, const float* vars, const float* mu_sqe,
                  const double* stats, float B, float* lc_elem, double* lc_sum_dev, int64_t W);
 
@@ -408,7 +444,12 @@ int vbnn_calc_lc(vbnn_ctx* ctx, const float* means, const float* lvars, const fl
  * and their transposes (I x ld_xT); x2_s / xT_s / x2T_s optional. Replaces the host->device copies of
  * main.lua:22-25 plus two vbnn_pack calls. rows_per_draw > 0 (vbnn_fwd_args.rows_per_draw): the N operand rows are several
  * Monte-Carlo draws of ONE minibatch of rows_per_draw rows -- operand row n is src row n % rows_per_draw, so the host never
- * materialises the S-fold input. 0: off. */
+ * materialises the S-fold input. 0: off.
+ * Held by tests/test_sweeps_gpu.py, bit for bit: x_s = T(x), x2_s = T(fl(T(x)^2)) (the square of the ROUNDED x), and the
+ * transposes hold the very values of the row-major outputs. ALIGNMENT. x_s / x2_s are written with 4-element vector stores
+ * unconditionally: bases 16-byte aligned, ld_x a multiple of 4 (checked; the convention is VBNN_KPAD). xT_s / x2T_s take vector
+ * stores when ld_xT % 4 == 0 (bases aligned likewise), element stores otherwise. src takes 16-byte loads when it is 16-byte
+ * aligned and ld_src % 4 == 0, 4-byte loads otherwise. Pad elements are never written. */
 int vbnn_pack_input(vbnn_ctx* ctx, int dtype, const float* src, int64_t ld_src, int64_t N, int64_t I, void* x_s,
                     void* x2_s, int64_t ld_x, void* xT_s, void* x2T_s, int64_t ld_xT, int64_t rows_per_draw);
 

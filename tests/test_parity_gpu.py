@@ -277,6 +277,8 @@ def test_layer_forward_backward_f32(nnmod, oracle, mode, N, I, O):
         if mode == "wn":
             np.testing.assert_allclose(host(m.weight), om.weight, rtol=0, atol=2e-7 * np.abs(om.weight).max())
             assert np.array_equal(host(m.e).view(np.uint32), om.e.view(np.uint32))
+            # and bit for bit from the device's own cached stdv (the oracle's differs by its libm's expf): two fp32 roundings
+            assert np.array_equal(host(m.weight).view(np.uint32), (host(m.means) + host(m.stdv) * host(m.e)).view(np.uint32))
         y = m.updateOutput(dev(x))
         want_y = om.updateOutput(x)
         w_eff = np.abs(om.weight) if mode == "wn" else np.abs(om.means)
