@@ -83,7 +83,7 @@ int vbnn_debug_set(int key, int value);
  *   bits 8-15  CP   (tile backward: classes of the final weight kept in registers, 12 or 0)
  *   bits 16-17 the finish of the row-chunk partial sums: VBNN_HEAD_FINISH_NONE (a forward, or no sum asked for),
  *              _INLINE (the last arriver of the launch), _KERNEL (k_head_backward_finish follows)
- * Any key but this one and VBNN_DEBUG_LAST_GEMM_FORM (below): -1. Nothing here changes what is launched. */
+ * Any key but this one, VBNN_DEBUG_LAST_GEMM_FORM and VBNN_DEBUG_LAST_CHAINED (below): -1. Nothing here changes what is launched. */
 #define VBNN_DEBUG_LAST_HEAD_FORM 11
 #define VBNN_HEAD_ENTRY_FORWARD 1
 #define VBNN_HEAD_ENTRY_SLOTS 2
@@ -375,6 +375,21 @@ int vbnn_acc_grad_parameters(vbnn_ctx* ctx, int dtype, const vbnn_dw_args* a);
  * latency chain with the chip a fraction busy) -- it does, each tile computed exactly as by its own launch (bitwise the same
  * outputs); everywhere else this IS the two calls, accGradParameters first. */
 int vbnn_backward_pair(vbnn_ctx* ctx, int dtype, const vbnn_dx_args* dx, const vbnn_dw_args* dw);
+
+/* The same two calls for the bf16 layers whose two gradients each run on the two-pass 256 x 256 kernel (additive, ABI 6). Where
+ * dtype is BF16 and BOTH blocks would on their own take that kernel's plain K-major LRT form (whole 256 x 256 tiles that fill the
+ * device, part = 0, accumulate = 0, no gradBias row, no transposed outputs, the fast / folded epilogue protocols), ONE launch
+ * carries both: workgroup t computes tile t of the first problem, issues its stores and goes straight on to tile t of the second,
+ * so the first tile's stores drain under the second tile's matrix passes. No workgroup waits for another; every tile is computed
+ * exactly as by its own launch (bitwise the same outputs). Everywhere else this IS the two calls. `order` says which problem
+ * comes first, in the one launch and in the two calls alike. VBNN_DEBUG_LAST_GEMM_FORM reads as after the two calls;
+ * vbnn_debug_get(VBNN_DEBUG_LAST_CHAINED) is 1 if the last call of this process went out as one launch, else 0;
+ * vbnn_debug_set(VBNN_DEBUG_CHAIN_OFF, 1) makes every call the two calls (A/B, tests). */
+#define VBNN_CHAIN_DX_FIRST 0
+#define VBNN_CHAIN_DW_FIRST 1
+#define VBNN_DEBUG_LAST_CHAINED 15
+#define VBNN_DEBUG_CHAIN_OFF 16
+int vbnn_backward_chain(vbnn_ctx* ctx, int dtype, const vbnn_dx_args* dx, const vbnn_dw_args* dw, int order);
 
 /* gradBias += scale * sum_n g[n][o]  (the parent call at VBLinear.lua:113). g is N x ld_g of
  * `dtype` (F32: the module's gradOutput; BF16: a packed operand of the fused path). */

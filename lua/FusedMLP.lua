@@ -96,6 +96,11 @@ function FusedMLP.new(opt)
         wmin, wmax = math.min(wmin, sizes[k] * sizes[k + 1]), math.max(wmax, sizes[k] * sizes[k + 1])
     end
     self.dx_first = (not self.comm) and (2 * wmin <= wmax)
+    -- the chained backward launch (engine.py: chain_backward; bf16 without an exchange): updateGradInput's tile first where dx_first
+    -- holds, else off; opt.chain_backward = 'dx' / 'dw' / false overrides
+    local chain = opt.chain_backward
+    if chain == nil then chain = self.dx_first and 'dx' or false end
+    self.chain = (self.dtype == C.VBNN_BF16 and not self.comm) and chain or nil
     self:prepare()
     return self
 end
@@ -335,6 +340,22 @@ function FusedMLP:run(inputs, ld, targets, N)
             if li < #self.vb and not v.bias_from_dw then
                 check(C.vbnn_acc_grad_bias(vb.ctx, self.dtype, v.g_s.p, v.g_s.ld, N, v.O, 1, accumulate, v.gradBias))
             end
+        end
+    elseif self.chain then
+        -- updateGradInput and accGradParameters of a layer as ONE chained launch where both run on the two-pass 256 x 256 kernel
+        -- (vbnn_backward_chain); the first layer's accGradParameters is a launch of its own, last
+        local order = self.chain == 'dw' and 1 or 0               -- VBNN_CHAIN_DW_FIRST / VBNN_CHAIN_DX_FIRST
+        for li = #self.vb, 2, -1 do
+            local v = self.vb[li]
+            check(C.vbnn_backward_chain(vb.ctx, self.dtype, dx_block(li), dw_block(li), order))
+            if li < #self.vb and not v.bias_from_dw then
+                check(C.vbnn_acc_grad_bias(vb.ctx, self.dtype, v.g_s.p, v.g_s.ld, N, v.O, 1, accumulate, v.gradBias))
+            end
+        end
+        local v = self.vb[1]
+        check(C.vbnn_acc_grad_parameters(vb.ctx, self.dtype, dw_block(1)))
+        if 1 < #self.vb and not v.bias_from_dw then
+            check(C.vbnn_acc_grad_bias(vb.ctx, self.dtype, v.g_s.p, v.g_s.ld, N, v.O, 1, accumulate, v.gradBias))
         end
     elseif self.dx_first then
         for li = #self.vb, 2, -1 do

@@ -97,7 +97,7 @@ typedef struct {
 } layer_t;
 
 typedef struct {
-    int dtype, esize, n_layers, n_classes, world, rank, dx_first;
+    int dtype, esize, n_layers, n_classes, world, rank, dx_first, chain;
     int sharded;              /* --sharded: the sharded-update exchange (reduce-scatter by layer rows, slice update, shadow all-gather) */
     double* stat_parts;       /* [world][layers][4] doubles: every rank's statistics of its row slices */
     int n_head_slots; float* head_slots;   /* vbnn_forward_head_slots x N x 16 floats, or 0 / NULL */
@@ -193,6 +193,10 @@ static void fm_new(fused_mlp* m, int dtype, const int64_t* sizes, int n_layers, 
         if (w > wmax) wmax = w;
     }
     m->dx_first = !m->comm && (2 * wmin <= wmax);
+    /* the chained backward launch (engine.py: chain_backward; bf16 only): updateGradInput's tile first where dx_first holds, else
+       off; VBNN_CHAIN_BACKWARD = dx / dw / 0 overrides */
+    const char* cb = getenv("VBNN_CHAIN_BACKWARD");
+    m->chain = m->dtype != VBNN_BF16 ? 0 : cb ? (!strcmp(cb, "dx") ? 1 : !strcmp(cb, "dw") ? 2 : 0) : (m->dx_first ? 1 : 0);
     fm_prepare(m);
 }
 
@@ -392,6 +396,21 @@ static void fm_run(fused_mlp* m, const float* inputs, int64_t ld, const int32_t*
             if (li < nl - 1 && !v->bias_from_dw)
                 CHECK(vbnn_acc_grad_bias(g_ctx, m->dtype, v->g_s.p, v->g_s.ld, N, v->O, 1.0f, accumulate, v->gradBias));
         }
+    } else if (m->chain && !m->comm) {
+        /* bf16, no exchange: updateGradInput and accGradParameters of a layer as ONE chained launch where both run on the two-pass
+           256 x 256 kernel (vbnn_backward_chain); the first layer's accGradParameters is a launch of its own, last */
+        for (int li = nl - 1; li >= 1; --li) {
+            layer_t* v = &m->vb[li];
+            dw_block(m, li, N, accumulate, &dd);
+            dx_block(m, li, N, &xa);
+            CHECK(vbnn_backward_chain(g_ctx, m->dtype, &xa, &dd, m->chain == 2 ? VBNN_CHAIN_DW_FIRST : VBNN_CHAIN_DX_FIRST));
+            if (li < nl - 1 && !v->bias_from_dw)
+                CHECK(vbnn_acc_grad_bias(g_ctx, m->dtype, v->g_s.p, v->g_s.ld, N, v->O, 1.0f, accumulate, v->gradBias));
+        }
+        dw_block(m, 0, N, accumulate, &dd);
+        CHECK(vbnn_acc_grad_parameters(g_ctx, m->dtype, &dd));
+        if (0 < nl - 1 && !m->vb[0].bias_from_dw)
+            CHECK(vbnn_acc_grad_bias(g_ctx, m->dtype, m->vb[0].g_s.p, m->vb[0].g_s.ld, N, m->vb[0].O, 1.0f, accumulate, m->vb[0].gradBias));
     } else if (m->dx_first) {
         for (int li = nl - 1; li >= 1; --li) {
             dx_block(m, li, N, &xa);

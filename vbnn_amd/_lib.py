@@ -14,6 +14,8 @@ CSRC = os.path.join(_HERE, "csrc")
 
 OK = 0
 F32, BF16 = 0, 1
+CHAIN_DX_FIRST, CHAIN_DW_FIRST = 0, 1      # VBNN_CHAIN_DX_FIRST, VBNN_CHAIN_DW_FIRST (vbnn_backward_chain's order)
+DEBUG_LAST_CHAINED, DEBUG_CHAIN_OFF = 15, 16   # VBNN_DEBUG_LAST_CHAINED (vbnn_debug_get), VBNN_DEBUG_CHAIN_OFF (vbnn_debug_set)
 PACK_COPY, PACK_EXP, PACK_SQUARE, PACK_MUL, PACK_RELU, PACK_RELU_SQUARE = range(6)
 KPAD = 64
 STREAM_EPS, STREAM_ZETA, STREAM_INIT, STREAM_DATA, STREAM_HEINIT = 1, 2, 3, 4, 5
@@ -235,6 +237,7 @@ _SIGS = {
     "vbnn_grad_input": ([_vp, _i, C.POINTER(DxArgs)], _i),
     "vbnn_acc_grad_parameters": ([_vp, _i, C.POINTER(DwArgs)], _i),
     "vbnn_backward_pair": ([_vp, _i, C.POINTER(DxArgs), C.POINTER(DwArgs)], _i),
+    "vbnn_backward_chain": ([_vp, _i, C.POINTER(DxArgs), C.POINTER(DwArgs), _i], _i),
     "vbnn_head_forward_backward": ([_vp, _i, C.POINTER(HeadArgs)], _i),
     "vbnn_head_predict": ([_vp, _i, C.POINTER(PredictArgs)], _i),
     "vbnn_predict_moments": ([_vp, C.POINTER(MomentsArgs)], _i),

@@ -13,12 +13,14 @@ extern "C" int vbnn_debug_set(int key, int value) {
     if (key == VBNN_DEBUG_V0 && (value == 0 || value == 1)) { g_v0 = value; return VBNN_OK; }
     if (key == VBNN_DEBUG_HEAD_BACKWARD && value >= -1 && value <= 1) { g_head_stream = value; return VBNN_OK; }
     if (key == VBNN_DEBUG_V3_FOLD_SERIAL && (value == 0 || value == 1)) { g_v3_fold_serial = value; return VBNN_OK; }
+    if (key == VBNN_DEBUG_CHAIN_OFF && (value == 0 || value == 1)) { g_v3_chain_off = value; return VBNN_OK; }
     vbnn_set_error("vbnn_debug_set: unknown key %d / value %d", key, value);
     return VBNN_ERR_INVALID;
 }
 extern "C" int vbnn_debug_get(int key) {
     if (key == VBNN_DEBUG_LAST_HEAD_FORM) return g_last_head_form;
     if (key == VBNN_DEBUG_LAST_GEMM_FORM) return g_last_gemm_form;
+    if (key == VBNN_DEBUG_LAST_CHAINED) return g_v3_last_chained;
     return -1;
 }
 

@@ -67,10 +67,13 @@ template <class Epi> struct v3_fold_pipe<Epi, std::void_t<decltype(Epi::FOLD_PIP
 // tickets -- lost to this one, 84 against 68 us in the step, and lives on in tools/lab/ only.)
 // PIPE: the staged fold of a functor with FOLD_PIPE (EpiFwd) as a software pipeline (1, what the library launches) or in its serial
 // form (0: vbnn_debug_set(VBNN_DEBUG_V3_FOLD_SERIAL, 1); the same bits -- kept for the tests and for A/B).
+// The kernel's body is a device function of the workgroup's index in its launch (`wg`: what the block -> tile mapping below starts
+// from), so that one launch can run the bodies of two independent GEMMs one after the other (gemm_nt_v3_chain below). It owns all of
+// the workgroup's dynamic LDS from its first DMA to its last staged store.
 template <bool DUAL, bool AK, bool BK, class Epi, bool SPLIT = false, bool HM = false, int PIPE = v3_fold_pipe<Epi>::value>
-__global__ __launch_bounds__(512, 2) void gemm_nt_v3(const bf16_t* __restrict__ A, const bf16_t* __restrict__ A2, int64_t lda,
-                                                     const bf16_t* __restrict__ B, const bf16_t* __restrict__ B2, int64_t ldb,
-                                                     int M, int N, int nk, int tiles_m, int tiles_n, Epi epi_in) {
+__device__ __forceinline__ void gemm_nt_v3_body(const int wg, const bf16_t* __restrict__ A, const bf16_t* __restrict__ A2, int64_t lda,
+                                                const bf16_t* __restrict__ B, const bf16_t* __restrict__ B2, int64_t ldb,
+                                                int M, int N, int nk, int tiles_m, int tiles_n, const Epi& epi_in) {
     static_assert(!(SPLIT && DUAL), "the split form computes one GEMM of the pair per workgroup");
     static_assert(SPLIT == HM && (!HM || (AK && BK)), "the pair-split launch is the half-height K-major form");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_v3(const bf16_t* __restrict__ 
 
     // ---- block -> tile mapping: as gemm_v2.h (blocks that share an XCD get a compact 4 x 8 group of tiles)
     const int nblk = tiles_m * tiles_n * (SPLIT ? 2 : 1);
-    int bid = blockIdx.x;
+    int bid = wg;
     {
         const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
@@ -984,6 +987,37 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_v3(const bf16_t* __restrict__ 
     V3_ST(4);
 }
 
+template <bool DUAL, bool AK, bool BK, class Epi, bool SPLIT = false, bool HM = false, int PIPE = v3_fold_pipe<Epi>::value>
+__global__ __launch_bounds__(512, 2) void gemm_nt_v3(const bf16_t* __restrict__ A, const bf16_t* __restrict__ A2, int64_t lda,
+                                                     const bf16_t* __restrict__ B, const bf16_t* __restrict__ B2, int64_t ldb,
+                                                     int M, int N, int nk, int tiles_m, int tiles_n, Epi epi_in) {
+    gemm_nt_v3_body<DUAL, AK, BK, Epi, SPLIT, HM, PIPE>(blockIdx.x, A, A2, lda, B, B2, ldb, M, N, nk, tiles_m, tiles_n, epi_in);
+}
+
+// ---- two INDEPENDENT two-pass GEMMs in one launch (updateGradInput and accGradParameters of one layer: both read g, gv, neither
+// reads what the other writes). Workgroup t runs the first GEMM's tile t, issues that tile's epilogue stores and goes straight into
+// the fill and the passes of the second GEMM's tile t: the first tile's last stores drain under the second tile's MFMA passes, as a
+// fold's stores drain under pass 2, instead of every CU of the chip draining at a launch boundary with the matrix pipe idle. No
+// workgroup waits for another: each body keeps its own tile mapping, MFMA order, fold and epilogue -- the bits of its own launch.
+// The grid is the larger tile count; a workgroup past a GEMM's count skips that body (workgroup-uniform).
+// Between the bodies: the first body's epilogue staging tiles lie where the second body's fill lands, so every wave's LDS reads
+// are retired and the workgroup meets once (stores stay in flight: they are OLDER than the fill on the vmcnt counter, and the counted
+// waits of run_pass only get stricter -- the same argument as for the fold's stores in front of pass 2).
+struct v3_gemm_args {
+    const bf16_t* A; const bf16_t* A2; int64_t lda;
+    const bf16_t* B; const bf16_t* B2; int64_t ldb;
+    int M, N, nk, tiles_m, tiles_n;
+};
+template <bool AK1, bool BK1, class Epi1, bool AK2, bool BK2, class Epi2>
+__global__ __launch_bounds__(512, 2) void gemm_nt_v3_chain(v3_gemm_args g1, Epi1 e1, v3_gemm_args g2, Epi2 e2) {
+    const int wg = blockIdx.x;
+    if (wg < g1.tiles_m * g1.tiles_n)
+        gemm_nt_v3_body<true, AK1, BK1, Epi1>(wg, g1.A, g1.A2, g1.lda, g1.B, g1.B2, g1.ldb, g1.M, g1.N, g1.nk, g1.tiles_m, g1.tiles_n, e1);
+    v2_lds_barrier();
+    if (wg < g2.tiles_m * g2.tiles_n)
+        gemm_nt_v3_body<true, AK2, BK2, Epi2>(wg, g2.A, g2.A2, g2.lda, g2.B, g2.B2, g2.ldb, g2.M, g2.N, g2.nk, g2.tiles_m, g2.tiles_n, e2);
+}
+
 // The kernel has no ragged-edge or general-output path: whole 256 x 256 tiles, 32-bit element offsets, the functor's
 // fast protocol and 16-byte rows of the transposed outputs. Everything else stays with gemm_v2.h.
 // (K-major operands: lda / ldb are the pitches of the K rows; K must be whole 64-row steps -- there is no padding row to
@@ -1061,6 +1095,47 @@ static int launch_gemm_v3(vbnn_ctx* ctx, const T* A, const T* A2, int64_t lda, c
         hipError_t e = hipLaunchKernel(kern, dim3(tiles_m * tiles_n), dim3(512), args, V3_LDS, ctx->stream);
         if (e != hipSuccess) { vbnn_set_error("launch of gemm_nt_v3 failed: %s", hipGetErrorString(e)); return VBNN_ERR_HIP; }
         return vbnn_check_launch("gemm_nt_v3");
+    }
+}
+
+// ---- the chained launch of two dual GEMMs (gemm_nt_v3_chain). The caller has established that EACH would take launch_gemm_v3 on its
+// own (operands present, gemm_v3_possible, the shape selection); what is checked here is what launch_gemm_v3 checks. The forms are
+// noted in launch order, so the last-form query reads what the two separate launches would leave.
+inline int g_v3_chain_off = 0;      // 1: vbnn_backward_chain always issues its two calls (vbnn_debug_set key 16)
+inline int g_v3_last_chained = 0;   // did the last vbnn_backward_chain call go out as one launch? (vbnn_debug_get key 15)
+template <typename T, bool AK1, bool BK1, class Epi1, bool AK2, bool BK2, class Epi2>
+static int launch_gemm_v3_chain(vbnn_ctx* ctx, const T* A, const T* A2, int64_t lda, const T* B, const T* B2, int64_t ldb, int M, int N, int K,
+                                const Epi1& epi1, const T* C, const T* C2, int64_t ldc, const T* D, const T* D2, int64_t ldd, int P, int Q,
+                                int R, const Epi2& epi2) {
+    if constexpr (sizeof(T) != 2) {
+        return VBNN_ERR_UNSUPPORTED;
+    } else {
+        if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)A2 | (uintptr_t)B2 | (uintptr_t)C | (uintptr_t)D | (uintptr_t)C2 | (uintptr_t)D2) & 15u) != 0)
+            return VBNN_ERR_UNSUPPORTED;
+        const int nk1 = (K + V2_BK - 1) / V2_BK, nk2 = (R + V2_BK - 1) / V2_BK;
+        if ((!AK1 && lda < (int64_t)nk1 * V2_BK) || (!BK1 && ldb < (int64_t)nk1 * V2_BK) || (!AK2 && ldc < (int64_t)nk2 * V2_BK) ||
+            (!BK2 && ldd < (int64_t)nk2 * V2_BK))
+            return VBNN_ERR_UNSUPPORTED;
+        if (!gemm_v3_possible(M, N, K, lda, ldb, AK1, BK1, epi1) || !gemm_v3_possible(P, Q, R, ldc, ldd, AK2, BK2, epi2)) return VBNN_ERR_UNSUPPORTED;
+        const void* kern = (const void*)gemm_nt_v3_chain<AK1, BK1, Epi1, AK2, BK2, Epi2>;
+        static vbnn_per_device_flag configured_on;           // per instantiation and device
+        bool& configured = configured_on[ctx->device];
+        if (!configured) {
+            hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS);
+            if (e != hipSuccess) { vbnn_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return VBNN_ERR_HIP; }
+            configured = true;
+        }
+        v3_gemm_args g1 = {(const bf16_t*)A, (const bf16_t*)A2, lda, (const bf16_t*)B, (const bf16_t*)B2, ldb, M, N, nk1, M / V3_BM, N / V3_BN};
+        v3_gemm_args g2 = {(const bf16_t*)C, (const bf16_t*)C2, ldc, (const bf16_t*)D, (const bf16_t*)D2, ldd, P, Q, nk2, P / V3_BM, Q / V3_BN};
+        Epi1 e1 = epi1;
+        Epi2 e2 = epi2;
+        void* args[] = {&g1, &e1, &g2, &e2};
+        const int n1 = g1.tiles_m * g1.tiles_n, n2 = g2.tiles_m * g2.tiles_n;
+        vbnn_note_gemm_form<T>(VBNN_GEMM_KERNEL_V3, 0, 0, true, false, AK1, BK1, 0, false, false, epi1);
+        vbnn_note_gemm_form<T>(VBNN_GEMM_KERNEL_V3, 0, 0, true, false, AK2, BK2, 0, false, false, epi2);
+        hipError_t e = hipLaunchKernel(kern, dim3(n1 > n2 ? n1 : n2), dim3(512), args, V3_LDS, ctx->stream);
+        if (e != hipSuccess) { vbnn_set_error("launch of gemm_nt_v3_chain failed: %s", hipGetErrorString(e)); return VBNN_ERR_HIP; }
+        return vbnn_check_launch("gemm_nt_v3_chain");
     }
 }
 

@@ -128,6 +128,15 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
         self._params_stale = False            # sharded: the fp32 means / lvars of OTHER ranks' rows are stale after an update
         self._dx_first_opt = opt.get("dx_first", None)      # None: decided from the layer sizes once they are known (below)
         self.fuse_kl = bool(opt.get("fuse_kl", True))
+        # opt.chain_backward (or VBNN_CHAIN_BACKWARD): "dx" / "dw" -- updateGradInput and accGradParameters of every layer but the
+        # first as ONE chained launch (vbnn_backward_chain), updateGradInput's / accGradParameters' tile first; False / "" / "0": off.
+        # bf16 without an exchange only (run). None: "dx" where dx_first holds (decided below, once the layer sizes are known), else
+        # off -- LAB_NOTES.md section 16 has the measurement: it wins where a lighter launch follows the chained pair (the wide
+        # net, -1.6 %) and loses where seven chained pairs run back to back (the deep stack, +0.5 %).
+        cb = opt.get("chain_backward", os.environ.get("VBNN_CHAIN_BACKWARD"))
+        cb = "dx" if cb is True else ("" if cb in (False, "0", 0, "") else cb)
+        assert cb in (None, "", "dx", "dw"), "chain_backward: 'dx', 'dw' or off"
+        self._chain_opt = cb
         # "nll": LogSoftMax + ClassNLLCriterion (mlp.lua:30-32); "mse": nn.MSECriterion on the final Linear's outputs
         # (BASELINE.json configs[4], a regression target of n_classes dimensions -- not in the reference); "gauss": the
         # heteroscedastic Gaussian likelihood (vbnn_gauss_nll_forward) -- the final Linear's n_classes = 2 D outputs are D means
@@ -176,6 +185,8 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
         self.sizes = sizes
         weights = [sizes[i] * sizes[i + 1] for i in range(len(sizes) - 1)]
         self.dx_first = bool(self._dx_first_opt) if self._dx_first_opt is not None else (2 * min(weights) <= max(weights))
+        self.chain_backward = "" if self.dtype != "bf16" else (self._chain_opt if self._chain_opt is not None else
+                                                                ("dx" if self.dx_first and self._dx_first_opt is None else ""))
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         # ---- gradient arena: [gradWeight | gradSum | gradBias] per VB layer, then the final Linear (partition.arena_layout)
@@ -487,6 +498,18 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
         if self.probe is None or self.probe[0] != "all" or not self._early(self.vb[li], self._lrt()):
             return _NULL_CM
         return self._probed(name, li)
+
+    def _chain_as_two_probed(self, li, N, d, order):
+        """A probed layer's chained pair (opt.chain_backward) as its two launches, in the chain's order: the measurement hook
+        brackets each family's launch on its own. The same bits; only the probed block of bench.py runs this."""
+        lib, ctx, code = L.lib(), self.ctx.h, self.code
+        fams = ("updateGradInput", "accGradParameters") if order == L.CHAIN_DX_FIRST else ("accGradParameters", "updateGradInput")
+        for fam in fams:
+            with self._probed(fam, li):
+                if fam == "updateGradInput":
+                    L.check(lib.vbnn_grad_input(ctx, code, C.byref(self._dx_args(li, N))))
+                else:
+                    L.check(lib.vbnn_acc_grad_parameters(ctx, code, C.byref(d)))
 
     # ---- VBLinear:clamp_to_map on every VB layer (mlp.lua:88-91): the forward uses the means as weights.
     @_ordered
@@ -800,6 +823,28 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
                         L.check(lib.vbnn_acc_grad_parameters(ctx, code, C.byref(d)))
                 if not (fused_head and li == nl - 1) and not v.bias_from_dw:
                     L.check(lib.vbnn_acc_grad_bias(ctx, code, v.g_s.ptr, v.g_s.ld, N, v.O, 1.0, accumulate, _p(v.gradBias)))
+        elif self.chain_backward and not self.reduce and not self.overlap:
+            # opt.chain_backward (bf16, no exchange; in place of either order below): updateGradInput and accGradParameters of a
+            # layer are independent (both consume g_li) and go out as ONE launch where both run on the two-pass 256 x 256 kernel
+            # (vbnn_backward_chain: a workgroup computes its tile of the first, then its tile of the second, so the first tile's
+            # stores drain under the second's matrix passes; elsewhere the call is the two launches) -- each tile bitwise what its
+            # own launch computes. The first layer has no updateGradInput: its accGradParameters is a launch of its own, last.
+            order = L.CHAIN_DW_FIRST if self.chain_backward == "dw" else L.CHAIN_DX_FIRST
+            for li in range(nl - 1, 0, -1):
+                v = self.vb[li]
+                d = self._dw_args(li, N, accumulate)
+                if self.probe is not None and self.probe[0] in (li, "all"):
+                    self._chain_as_two_probed(li, N, d, order)
+                else:
+                    L.check(lib.vbnn_backward_chain(ctx, code, C.byref(self._dx_args(li, N)), C.byref(d), order))
+                if not (fused_head and li == nl - 1) and not v.bias_from_dw:
+                    L.check(lib.vbnn_acc_grad_bias(ctx, code, v.g_s.ptr, v.g_s.ld, N, v.O, 1.0, accumulate, _p(v.gradBias)))
+            v = self.vb[0]
+            d = self._dw_args(0, N, accumulate)
+            with self._probed("accGradParameters", 0):
+                L.check(lib.vbnn_acc_grad_parameters(ctx, code, C.byref(d)))
+            if not (fused_head and nl == 1) and not v.bias_from_dw:
+                L.check(lib.vbnn_acc_grad_bias(ctx, code, v.g_s.ptr, v.g_s.ld, N, v.O, 1.0, accumulate, _p(v.gradBias)))
         elif self.dx_first and not self.reduce and not self.overlap:
             # every updateGradInput first, then the accGradParameters from the first layer up: in the wide net the two 4096^3
             # launches are then separated by the lighter 784-wide gradient. The chip is power-bound in these launches
