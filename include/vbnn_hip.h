@@ -1210,7 +1210,15 @@ int vbnn_logit_draws(vbnn_ctx* ctx, const vbnn_logit_draws_args* a);
  * vbnn_forward / vbnn_head_predict evaluate the pruned network ---------------------------------------------------------------
  * The key of a weight is snr = |means / sqrt(exp(lvars))| in fp32, operation for operation as mainviz.lua:20 forms
  * torch.abs(torch.cdiv(means, torch.sqrt(vars))); all three calls below compute it with ONE device function, so a weight has
- * the same key bits in each. A NaN key (a NaN parameter) orders above every number and is never pruned. */
+ * the same key bits in each. A NaN key (a NaN parameter, or 0 / 0: a zero mean under a variance that underflows to 0) orders
+ * above every number and is never pruned. Denormals are not flushed: the key of a denormal mean at lvars = 0 is that denormal,
+ * bit for bit, and a key that underflows is the correctly rounded denormal. A quiet NaN mean keeps its payload in the key
+ * (fabsf clears the sign), a signalling one comes out quiet with the rest of its payload; the selection orders NaN keys by
+ * their bit patterns, all of them above +inf.
+ * Held by tests/test_prune_forms_gpu.py against tests/_prune_np.py: with v = the device's own fp32 expf(lvars) the key is bit
+ * for bit fabsf(means / sqrtf(v)) (divide and square root correctly rounded), and within 2.25 ulp of |means| exp(-lvars / 2).
+ * ALIGNMENT. None is required of any pointer or pitch below beyond the natural alignment of its element type; 16-byte
+ * accesses are taken where the arguments allow them and the scalar paths leave the same bits. */
 typedef struct vbnn_prune_desc {
     const float* means; const float* lvars; int64_t O, I;     /* the layer's fp32 parameters, O x I */
     /* vbnn_prune_pack only (vbnn_prune_select and vbnn_prune_workspace_bytes read the four fields above): */
@@ -1218,7 +1226,8 @@ typedef struct vbnn_prune_desc {
     double* stats;                             /* 4 doubles, below */
     uint8_t* mask;                             /* optional O x I bytes, 1 = pruned (the `pruned` tensor of mainviz.lua:21); NULL to skip */
 } vbnn_prune_desc;
-/* mainviz.lua:20: snr_out[i] = the key of weight i (W floats): what nn.VBLinear exposes as :snr(). */
+/* mainviz.lua:20: snr_out[i] = the key of weight i (W floats): what nn.VBLinear exposes as :snr(). 16-byte loads and stores
+ * when means, lvars and snr_out are all 16-byte aligned (the last W % 4 elements singly), 4-byte ones otherwise. */
 int vbnn_snr(vbnn_ctx* ctx, const float* means, const float* lvars, int64_t W, float* snr_out);
 /* mainviz.lua:20-21 turned round: tau_dev[0] = the EXACT k-th smallest key (0-based) over the union of the listed layers'
  * weights (n_layers <= 8; one layer = per-layer pruning, all of them = global), so that `key < tau` prunes at most k weights
@@ -1227,7 +1236,9 @@ int vbnn_snr(vbnn_ctx* ctx, const float* means, const float* lvars, int64_t W, f
  * hands prefix and remaining rank to the next pass in device words. No host synchronisation, no allocation: the caller
  * passes `workspace` of at least vbnn_prune_workspace_bytes(...) bytes (4-byte aligned; contents irrelevant). Every pass
  * re-forms the keys from means / lvars (8 B per weight read, nothing per weight written). 0 <= k < W_total, else
- * VBNN_ERR_INVALID (to prune everything pass tau = +inf to vbnn_prune_pack). Fewer than 2^32 weights in all. */
+ * VBNN_ERR_INVALID (to prune everything pass tau = +inf to vbnn_prune_pack). Fewer than 2^32 weights in all. A layer is read
+ * with 16-byte loads when its means and lvars are both 16-byte aligned (whatever O and I: the layer is one run of O I
+ * floats), with 4-byte loads otherwise. tau_dev[0] is the key's bit pattern, a NaN's payload included. */
 int vbnn_prune_workspace_bytes(int n_layers, const vbnn_prune_desc* layers, size_t* bytes);
 int vbnn_prune_select(vbnn_ctx* ctx, int n_layers, const vbnn_prune_desc* layers, int64_t k, float* tau_dev,
                       void* workspace, size_t workspace_bytes);
@@ -1237,7 +1248,11 @@ int vbnn_prune_select(vbnn_ctx* ctx, int n_layers, const vbnn_prune_desc* layers
  * vbnn_prepare writes to mu_s / var_s, a pruned weight's are +0 in both (no mean, no variance); stats[0..3] = { number
  * pruned, sum of exp(lvars) over the pruned weights, sum of exp(lvars) over all weights, W } -- pruned:sum(),
  * prunedvars:mean() W and vars:mean() W of mainviz.lua:22-27 -- from per-workgroup partials added in a fixed order (two
- * runs give the same bits); and optionally the byte mask. No transposed shadows: the predictive path is forward-only. */
+ * runs give the same bits); and optionally the byte mask. No transposed shadows: the predictive path is forward-only.
+ * A NaN tau prunes nothing, tau = +inf everything but the NaN keys. ALIGNMENT, per layer: means / lvars take 16-byte loads
+ * when I % 4 == 0 and both are 16-byte aligned; mu_p / var_p take 4-element stores when ld_w % 4 == 0 and both are 16-byte
+ * aligned; the mask takes 4-byte stores when I % 4 == 0 and it is 4-byte aligned; element accesses otherwise, the same bits
+ * either way. Pad elements (c >= I of a shadow row) are never written. */
 int vbnn_prune_pack(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prune_desc* layers, const float* tau_dev, float tau_host);
 
 /* ---- compressed pruned weights and the forward that multiplies by them (additive, ABI 6) ------------------------------------
@@ -1265,7 +1280,8 @@ typedef struct vbnn_sparse_desc {
  * an ordered fill sweep (a wave walks its row in column order; an entry's place is its rank among the row's kept weights, from
  * a wave ballot): no atomics, no order dependence, two runs give the same bytes. No host synchronisation: the capacity is known
  * to a host that has read a vbnn_prune_pack's stats[0] for the same tau (nnz = W - pruned); with a smaller nnz_cap the entries
- * past it are dropped (row_ptr and nnz_dev still tell the true count, so the host can check). n_layers <= 8. */
+ * past it are dropped (row_ptr and nnz_dev still tell the true count, so the host can check). n_layers <= 8. Every access is
+ * an element access: no alignment beyond the element types' is asked of any array. */
 int vbnn_prune_compress(vbnn_ctx* ctx, int dtype, int n_layers, const vbnn_prune_desc* layers, const vbnn_sparse_desc* sparse,
                         const float* tau_dev, float tau_host);
 
@@ -1308,7 +1324,12 @@ typedef struct vbnn_unit_desc {
  * weight key's (vbnn_snr); both sums run in double in one fixed order (a wave per row, or a workgroup per row when the rows are
  * few and long: wave shuffles, then the waves in order), square roots and quotient in double, ONE rounding to fp32: two runs give
  * the same bits. A NaN key (a NaN parameter, 0 / 0) is stored as the positive quiet NaN 0x7fc00000, so that keys order as their
- * bit patterns with NaN above every number; such a unit is never pruned. 8 B read per weight. n_layers <= 8. */
+ * bit patterns with NaN above every number; such a unit is never pruned. 8 B read per weight. n_layers <= 8.
+ * A row is read with 16-byte loads when I % 4 == 0 and means and lvars are both 16-byte aligned, with 4-byte loads
+ * otherwise; a thread adds the same elements in the same order either way, so the key does not depend on the alignment.
+ * Held by tests/test_prune_forms_gpu.py: the key is float32(sqrt(sum m^2) / sqrt(sum v)) evaluated in double from the device's
+ * own v = expf(lvars), exactly, wherever the order of the double additions cannot move the quotient across a rounding
+ * midpoint. */
 int vbnn_unit_snr(vbnn_ctx* ctx, int n_layers, const vbnn_unit_desc* layers);
 /* mainviz.lua:20-21 turned round, per unit: tau = the EXACT k-th smallest key (0-based) over the union of the listed layers'
  * units, read from the key arrays vbnn_unit_snr wrote, so that `key < tau` prunes at most k units (fewer when keys tie at tau)
@@ -1329,7 +1350,10 @@ int vbnn_unit_index(vbnn_ctx* ctx, int n_layers, const vbnn_unit_desc* layers, c
  * fp32 bit copies into dense n_rows x n_cols arrays. rows == NULL: every row (n_rows = O); cols == NULL: every column
  * (n_cols = I). lvars / dst_lvars and bias / dst_bias are optional, in pairs: a VB layer passes all three (rows = its own kept
  * list, cols = the previous layer's), the final Linear its weight alone with cols = the last VB layer's list. The list LENGTHS
- * are host values (read back from n_keep). Index words are clamped to the source shape. Any O, I, n_rows, n_cols >= 1. */
+ * are host values (read back from n_keep). Index words are clamped to the source shape (a word >= O reads row O - 1, a word
+ * >= I column I - 1). Any O, I, n_rows, n_cols >= 1. dst_means / dst_lvars take 16-byte stores when n_cols % 4 == 0 and both
+ * are 16-byte aligned; without a column list the source takes 16-byte loads when I % 4 == 0 and means / lvars are 16-byte
+ * aligned; element accesses otherwise. Nothing behind n_rows x n_cols (or n_rows) elements is written. */
 typedef struct vbnn_unit_gather_args {
     const float* means; const float* lvars; const float* bias; int64_t O, I;      /* source: O x I (and O) */
     const uint32_t* rows; int64_t n_rows;

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import _prune_np as PN
+
 pytestmark = pytest.mark.gpu
 
 SEED = 3
@@ -95,7 +97,9 @@ def test_key_matches_float64(oracle, net):
         got, want = keys32(eng, li).astype(np.float64), snr64(eng, li)
         rel = np.abs(got - want) / want
         print(f"{net} layer {li}: key max rel err {np.nanmax(rel):.3e}, range {want.min():.3e} .. {want.max():.3e}")
-        assert np.all(np.abs(got - want) <= 1e-5 * want)
+        bound = PN.key_bound(host(eng.vb[li].means), host(eng.vb[li].lvars))      # derived in tests/_prune_np.py: 2.25 ulp
+        print(f"{net} layer {li}: fraction of the bound used {np.max(np.abs(got - want) / bound):.3f}")
+        assert np.all(np.abs(got - want) <= bound)
 
 
 # ---- 2. selection is exact on its own keys
@@ -211,7 +215,8 @@ def test_shadows_stats_and_reproducibility(oracle, net, dtype):
             st = r.stats[li]
             var64 = np.exp(host(v.lvars).astype(np.float64))
             assert st[0] == m.sum() and st[3] == v.O * v.I
-            assert abs(st[1] - var64[m].sum()) <= 1e-5 * var64[m].sum() and abs(st[2] - var64.sum()) <= 1e-5 * var64.sum()
+            rel = PN.pack_sum_rel(v.O, v.I)                                     # expf's allowance and the additions: _prune_np.py
+            assert abs(st[1] - var64[m].sum()) <= rel * var64[m].sum() and abs(st[2] - var64.sum()) <= rel * var64.sum()
             assert r.layers[li]["n_pruned"] == int(m.sum())
             npruned += int(m.sum())
         assert r.n_pruned == npruned and r.W == sum(v.O * v.I for v in eng.vb)

@@ -37,10 +37,12 @@ __device__ __forceinline__ vbnn_f32x4 vbnn_normal4_hw(uint64_t seed, uint32_t st
 
 // THE pruning key (mainviz.lua:20: torch.abs(torch.cdiv(means, torch.sqrt(vars))), vars = exp(lvars) as k_prep_layer forms var_s),
 // op for op in fp32. One definition for prune.hip and sparse.hip (both compiled without fp contraction): every kernel that
-// decides kept / pruned must give one weight the same bits.
+// decides kept / pruned must give one weight the same bits. sqrtf and the divide are hipcc's correctly rounded ones, as
+// torch's are -- NOT __fsqrt_rn, which this toolchain maps to the hardware's approximate v_sqrt_f32 (1 ulp) despite its name:
+// with it one key in seven was an ulp above fabsf(mean / sqrtf(v)) (tests/test_prune_forms_gpu.py::test_snr).
 #if defined(__HIPCC__)
 __device__ __forceinline__ float vbnn_snr_key(float mean, float lvar) {
-    return fabsf(__fdiv_rn(mean, __fsqrt_rn(expf(lvar))));
+    return fabsf(mean / sqrtf(expf(lvar)));
 }
 #endif
 
