@@ -1153,6 +1153,59 @@ typedef struct vbnn_selective_args {
 } vbnn_selective_args;
 int vbnn_selective(vbnn_ctx* ctx, const vbnn_selective_args* a);
 
+/* ---- pool acquisition for active learning (additive, ABI 6; vbnn_amd/csrc/acquire.hip; not in the reference) ----------------
+ * vbnn_top_rows: the exact top-k of R fp32 scores WITH their row indices -- which rows of an unlabelled pool to label next.
+ * ORDER. A key orders by its bits under vbnn_selective's monotone map (sign clear -> b ^ 0x80000000, sign set -> ~b, compared
+ * as unsigned integers): -0 ranks below +0, +-inf are ordinary values. A row whose SCORE is a NaN (any pattern) is never a
+ * candidate and is counted in n_nan; a row with exclude[r] != 0 is never a candidate and is counted in n_excluded ONLY (its score
+ * is not looked at). Among equal keys the LOWER row index wins and comes first. The output is fully ordered -- by key (largest = 1:
+ * descending, largest = 0: ascending), then by ascending row index -- and is bit for bit the same whatever the grid and the
+ * order in which the atomics arrive. With fewer than k candidates n_selected is their number; the remaining index entries are -1
+ * and their value / key entries the quiet NaN 0x7fc00000.
+ * KEY. stochastic = 0: key = score. stochastic = 1 (sampling k rows without replacement with probability proportional to
+ * score^beta: Gumbel top-k in its exponential-race form), evaluated op for op from vbnn_philox.h, for global row g = row0 + r:
+ *   x   = word (g & 3) of vbnn_philox4x32_10(g >> 2, 0, draw, VBNN_STREAM_ACQUIRE, (uint32_t)seed, (uint32_t)(seed >> 32))
+ *   u   = (float)min((x >> 8) + 1, 2^24 - 1) * 2^-24                       (0 < u < 1, exact)
+ *   E   = -vbnn_det_logf(u)                                                (> 0: a unit exponential)
+ *   L   = vbnn_det_logf(s) for a positive normal finite score s;  +inf for s = +inf;  -inf for every other non-NaN s (zero,
+ *         negative, subnormal: still candidates, chosen last);  0 when score is NULL (every candidate has weight 1)
+ *   key = fmaf(beta, L, -vbnn_det_logf(E))
+ * and the top k by key with largest = 1 (largest = 0 is refused). The noise depends on (seed, draw, g) alone: a pool scored in
+ * pieces, each with its row0, gets the keys of the whole. vbnn_det_logf is used beyond the [2^-24, 1] its comment states (E up to
+ * 16.7, scores over the normal range); the relative error measured there is in DESIGN.md section 8.
+ * OUTPUTS, all WRITTEN: index[j] the selected rows; value[j] = score[index[j]] as given (a bit copy; 1.0f when score is NULL);
+ * key[j] (optional) the key the row was ranked by (stochastic = 0: the score's bits); counts = { n_selected, n_candidates,
+ * n_nan, n_excluded }.
+ * SHAPE: three digit passes (11 + 11 + 10 bits, an LDS histogram per workgroup, one integer atomic per non-empty bin) find the
+ * k-th key and how many of its tied rows are wanted; a count pass per workgroup (skipped on the device unless the tie must be
+ * split) and one take pass collect the rows, ties by a prefix in index order over contiguous row ranges; one workgroup sorts the
+ * <= 4096 (key, row) pairs in LDS. stochastic = 0: keys are re-formed in every pass, 4 B (+ 1 B of exclude) read per row and
+ * pass, nothing per row written. stochastic = 1: the first pass stores every row's key in the workspace (4 B per row) and the
+ * later passes read it. A 16-byte aligned score (with exclude NULL or 4-byte aligned) takes 16-byte loads, any other 4-byte
+ * aligned score the 4-byte path; the stored keys likewise by the workspace's alignment. Integer atomics only, no allocation, no
+ * host synchronisation; the workspace (a fixed part and 4 B per row; vbnn_top_rows_workspace_bytes) needs no preparation.
+ * VBNN_ERR_INVALID, nothing written: R outside 1 .. 2^31 - 1; k outside 1 .. VBNN_TOP_ROWS_MAX_K; score NULL with
+ * stochastic = 0; largest = 0 with stochastic = 1; beta not in (0, FLT_MAX]; row0 < 0 or row0 + R > 2^32; a NULL output or
+ * workspace; workspace_bytes below vbnn_top_rows_workspace_bytes; a misaligned pointer (4 bytes; counts 8). */
+#define VBNN_TOP_ROWS_MAX_K 4096       /* most rows selected in one call */
+typedef struct vbnn_top_rows_args {
+    const float*   score;               /* R, or NULL with stochastic = 1: every candidate has weight 1 ("random") */
+    const uint8_t* exclude;             /* R or NULL; non-zero = not a candidate */
+    int64_t R;                          /* 1 <= R < 2^31 */
+    int32_t k;                          /* 1 .. VBNN_TOP_ROWS_MAX_K */
+    int32_t largest;                    /* 1: the k largest keys; 0: the k smallest */
+    int32_t stochastic;                 /* 0: key = score; 1: the perturbed key above */
+    float   beta;                       /* stochastic: > 0, finite */
+    uint64_t seed; uint32_t draw; int64_t row0;   /* stochastic: noise address; row0 + R <= 2^32 */
+    int32_t* index;                     /* k: selected rows, ordered by (key, then LOWER index first) */
+    float*   value;                     /* k: score[index[j]] as given (bit copies) */
+    float*   key;                       /* k or NULL: the key each row was ranked by */
+    int64_t* counts;                    /* 4: n_selected, n_candidates, n_nan, n_excluded (WRITTEN) */
+    void* workspace; size_t workspace_bytes;
+} vbnn_top_rows_args;
+int vbnn_top_rows_workspace_bytes(int64_t R, int32_t k, size_t* bytes);
+int vbnn_top_rows(vbnn_ctx* ctx, const vbnn_top_rows_args* a);
+
 /* ---- the sampling-free predictive by moment propagation (additive, ABI 6; vbnn_amd/csrc/propagate.hip; not in the reference) --
  * A factorised-Gaussian posterior needs no draws to predict: one pass carries (mean a, second moment q, variance c) of every
  * activation through the network. A hidden layer is three SINGLE products of vbnn_forward (w2 = NULL, y out, no ReLU):

@@ -45,6 +45,7 @@
 #define VBNN_STREAM_INIT  3u /* means ~ N(0, sqrt(var_init)) (VBLinear.lua:26-28)     */
 #define VBNN_STREAM_DATA  4u /* synthetic inputs for bench/tests                      */
 #define VBNN_STREAM_HEINIT 5u /* He init of `weight` (mlp.lua:52-53)                  */
+#define VBNN_STREAM_ACQUIRE 6u /* pool acquisition noise, one word per row (vbnn_top_rows) */
 
 typedef struct { uint32_t v[4]; } vbnn_u32x4;
 typedef struct { float v[4]; } vbnn_f32x4;

@@ -368,6 +368,23 @@ typedef struct vbnn_selective_args {
     uint64_t* counts;
 } vbnn_selective_args;
 int vbnn_selective(vbnn_ctx* ctx, const vbnn_selective_args* a);
+typedef struct vbnn_top_rows_args {
+    const float*   score;
+    const uint8_t* exclude;
+    int64_t R;
+    int32_t k;
+    int32_t largest;
+    int32_t stochastic;
+    float   beta;
+    uint64_t seed; uint32_t draw; int64_t row0;
+    int32_t* index;
+    float*   value;
+    float*   key;
+    int64_t* counts;
+    void* workspace; size_t workspace_bytes;
+} vbnn_top_rows_args;
+int vbnn_top_rows_workspace_bytes(int64_t R, int32_t k, size_t* bytes);
+int vbnn_top_rows(vbnn_ctx* ctx, const vbnn_top_rows_args* a);
 typedef struct vbnn_relu_moments_args {
     const float* m; int64_t ld_m;
     const float* v1; const float* v2; int64_t ld_v;

@@ -18,7 +18,7 @@ CHAIN_DX_FIRST, CHAIN_DW_FIRST = 0, 1      # VBNN_CHAIN_DX_FIRST, VBNN_CHAIN_DW_
 DEBUG_LAST_CHAINED, DEBUG_CHAIN_OFF = 15, 16   # VBNN_DEBUG_LAST_CHAINED (vbnn_debug_get), VBNN_DEBUG_CHAIN_OFF (vbnn_debug_set)
 PACK_COPY, PACK_EXP, PACK_SQUARE, PACK_MUL, PACK_RELU, PACK_RELU_SQUARE = range(6)
 KPAD = 64
-STREAM_EPS, STREAM_ZETA, STREAM_INIT, STREAM_DATA, STREAM_HEINIT = 1, 2, 3, 4, 5
+STREAM_EPS, STREAM_ZETA, STREAM_INIT, STREAM_DATA, STREAM_HEINIT, STREAM_ACQUIRE = 1, 2, 3, 4, 5, 6
 
 _vp, _i64, _u64, _u32, _f, _i = C.c_void_p, C.c_int64, C.c_uint64, C.c_uint32, C.c_float, C.c_int
 
@@ -169,6 +169,15 @@ class SelectiveArgs(C.Structure):     # vbnn_selective_args
 SELECTIVE_MAX_Q = 32                  # VBNN_SELECTIVE_MAX_Q
 
 
+class TopRowsArgs(C.Structure):       # vbnn_top_rows_args
+    _fields_ = [("score", _vp), ("exclude", _vp), ("R", _i64), ("k", C.c_int32), ("largest", C.c_int32),
+                ("stochastic", C.c_int32), ("beta", _f), ("seed", _u64), ("draw", _u32), ("row0", _i64),
+                ("index", _vp), ("value", _vp), ("key", _vp), ("counts", _vp), ("workspace", _vp), ("workspace_bytes", C.c_size_t)]
+
+
+TOP_ROWS_MAX_K = 4096                 # VBNN_TOP_ROWS_MAX_K
+
+
 class ReluMomentsArgs(C.Structure):   # vbnn_relu_moments_args
     _fields_ = [("m", _vp), ("ld_m", _i64), ("v1", _vp), ("v2", _vp), ("ld_v", _i64), ("N", _i64), ("O", _i64),
                 ("a", _vp), ("q", _vp), ("c", _vp), ("ld_out", _i64)]
@@ -304,6 +313,8 @@ _SIGS = {
     "vbnn_predict_quantiles": ([_vp, C.POINTER(QuantilesArgs)], _i),
     "vbnn_predict_calibration": ([_vp, C.POINTER(CalibrationArgs)], _i),
     "vbnn_selective": ([_vp, C.POINTER(SelectiveArgs)], _i),
+    "vbnn_top_rows_workspace_bytes": ([_i64, C.c_int32, C.POINTER(C.c_size_t)], _i),
+    "vbnn_top_rows": ([_vp, C.POINTER(TopRowsArgs)], _i),
     "vbnn_relu_moments": ([_vp, _i, C.POINTER(ReluMomentsArgs)], _i),
     "vbnn_square_shadow": ([_vp, _i, _vp, _i64, _i64, _i64, _vp, _i64], _i),
     "vbnn_logit_draws": ([_vp, C.POINTER(LogitDrawsArgs)], _i),

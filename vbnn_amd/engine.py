@@ -27,6 +27,7 @@ from .predictive import (LabelPredictResult, PredictResult, QuantilePredictResul
 from .calibration import CalibrationResult, SelectiveResult, _Calibration      # noqa: F401
 from .pruning import PruneResult, SparsePruneResult, UnitPruneResult, _Pruning      # noqa: F401
 from .checkpoint import CheckpointError, _Checkpoint, digest      # noqa: F401
+from .acquisition import AcquireResult, _Acquisition      # noqa: F401
 
 
 _NULL_CM = contextlib.nullcontext()
@@ -66,7 +67,7 @@ class _StepGraph:
             self.h = None
 
 
-class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint):
+class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint, _Acquisition):
     def __init__(self, opt, device=None, world_size=1, rank=0, process_group=None, force_reduce=False, stream=None):
         """stream: a torch.cuda.Stream for this engine's launches (a library context of its own, hence its own reduction
         scratch and tickets): two engines on two streams may compute on one device at the same time. Default: the
