@@ -1206,6 +1206,70 @@ typedef struct vbnn_top_rows_args {
 int vbnn_top_rows_workspace_bytes(int64_t R, int32_t k, size_t* bytes);
 int vbnn_top_rows(vbnn_ctx* ctx, const vbnn_top_rows_args* a);
 
+/* ---- diverse pool acquisition: greedy k-centre selection (additive, ABI 6; vbnn_amd/csrc/kcentre.hip; not in the reference) --
+ * vbnn_kcentre: core-set selection (Sener & Savarese) over R rows of D fp32 features. Each of k steps takes the candidate
+ * farthest from every centre so far -- the given `centres` and the rows picked before it -- optionally weighted by a per-row
+ * score. All arithmetic is fp32, operation by operation as written here (compiled without floating-point contraction: no
+ * multiply-add is fused); the output is bit for bit the same whatever the grid and the order in which the atomics arrive.
+ * DISTANCE. d(r, c) = sum_j (f[r,j] - f[c,j])^2. The row is shared by T threads, T = 64 for D <= 1024 and T = 256 above. With the
+ * row cut into quads of four columns (the last one short), thread i owns quads i, i + T, i + 2T, ... and walks its columns in
+ * ascending order from acc = +0:  t = f[r,j] - f[c,j];  p = t * t;  acc = acc + p  (three roundings per column). The T partials
+ * are added by the moments family's row-sum rule: inside each wave of 64 lanes the xor butterfly v[i] = v[i] + v[i ^ off] for
+ * off = 32, 16, 8, 4, 2, 1; for T = 256 the four waves then as ((w0 + w1) + w2) + w3. The order depends on D alone. d(r, r) is
+ * exactly +0. The squared NORM of a row is the same sum with f[c,j] = 0 and no subtraction (p = f * f).
+ * VOID. A row whose squared norm is not finite (a NaN, an infinity, an overflow) is void: never a candidate, ignored as a
+ * centre, counted in n_void, min_dist = the quiet NaN 0x7fc00000. With resume = 1 no norm is taken: a row is void exactly when
+ * the min_dist given for it is a NaN (it is rewritten as 0x7fc00000).
+ * MINIMUM. m[r] = min over the centres so far of d(r, c) (m = d < m ? d : m), from +inf, or from the given min_dist with
+ * resume = 1. The given centres are applied first, in blocks (the result does not depend on the blocks: a minimum). A centre
+ * index outside [0, R) is ignored; how many were is left as an int64 in the first 8 bytes of the workspace on return.
+ * CANDIDATES are the rows that are not excluded (exclude[r] == 0), not void and not picked in this call. A candidate whose
+ * weight is a NaN or below zero (-0 is not) is no candidate either and is counted in n_void, but its min_dist is kept and it
+ * serves as a centre when given as one. An excluded row is counted in n_excluded only. n_candidates counts the candidates
+ * before the first step. A given centre that is not excluded stays a candidate (with m = 0).
+ * KEY of a candidate: m (weight NULL) or m * w (one multiplication) while m is finite; w, or +inf with weight NULL, while
+ * m = +inf (no centre yet, or every distance overflowed). The one NaN product, 0 * inf, counts as +0. Each step takes the
+ * candidate with the LARGEST key, keys ordered as vbnn_top_rows orders them (the monotone map of their bits, -0 below +0),
+ * ties to the LOWER row; it records index[t], key[t] and dist[t] = the pick's m before it was picked; the pick becomes a
+ * centre. When the candidates run out n_selected < k, the rest of index is -1 and the rest of key / dist is 0x7fc00000.
+ * min_dist on return is m after the last pick (picked rows hold +0). A call with k = a + b gives the bits of a call with
+ * k = a followed by one with resume = 1, the a picks added to exclude, and k = b.
+ * OUTPUTS, all WRITTEN: index, key, dist (k each), min_dist (R), counts = { n_selected, n_candidates, n_void, n_excluded }.
+ * SHAPE: initial centres in blocks of min(8, 32768 / (4 * ceil(D / 4))) rows staged in LDS, one pass over feat per block;
+ * then k + 1 launches, each staging the previous pick's row (read from a device word), lowering m, and settling its own pick
+ * with one 64-bit integer atomic max of (order word << 32 | ~row) per workgroup; a one-workgroup finish. The first launch also
+ * takes the norms and writes one byte per row of workspace (candidate or not). feat with a 16-byte aligned base and ld % 4 == 0
+ * takes 16-byte loads, an 8-byte aligned base with ld % 2 == 0 8-byte loads, anything else 4-byte loads; a short last quad
+ * is read element by element, so nothing past column D - 1 is read. No allocation, no host synchronisation, no workgroup waits
+ * for another; the workspace (vbnn_kcentre_workspace_bytes: a fixed part and 1 B per row) needs no preparation.
+ * VBNN_ERR_INVALID, nothing written: R outside 1 .. 2^31 - 1; D outside 1 .. VBNN_KCENTRE_MAX_D; k outside 1 ..
+ * VBNN_KCENTRE_MAX_K; ld < D; n_centres < 0, or centres NULL with n_centres > 0; resume not 0 / 1; a NULL feat, index, min_dist,
+ * counts or workspace (key and dist are optional); workspace_bytes below vbnn_kcentre_workspace_bytes; a misaligned pointer
+ * (4 bytes; counts and the workspace 8). */
+#define VBNN_KCENTRE_MAX_K 4096        /* most rows selected in one call */
+#define VBNN_KCENTRE_MAX_D 8192        /* widest feature row */
+typedef struct vbnn_kcentre_args {
+    const float*   feat;                /* R x D, row stride ld */
+    int64_t ld;                         /* >= D */
+    const float*   weight;              /* R or NULL */
+    const uint8_t* exclude;             /* R or NULL; non-zero = never taken */
+    const int32_t* centres;             /* n_centres rows already labelled (duplicates, excluded and void rows allowed) or NULL */
+    int64_t R;                          /* 1 <= R < 2^31 */
+    int64_t D;                          /* 1 .. VBNN_KCENTRE_MAX_D */
+    int32_t n_centres;                  /* >= 0 */
+    int32_t k;                          /* 1 .. VBNN_KCENTRE_MAX_K */
+    int32_t resume;                     /* 1: m starts from min_dist as given */
+    int32_t reserved;                   /* 0 */
+    int32_t* index;                     /* k: the picks in pick order */
+    float*   key;                       /* k or NULL */
+    float*   dist;                      /* k or NULL */
+    float*   min_dist;                  /* R: read with resume = 1, WRITTEN */
+    int64_t* counts;                    /* 4: n_selected, n_candidates, n_void, n_excluded (WRITTEN) */
+    void* workspace; size_t workspace_bytes;
+} vbnn_kcentre_args;
+int vbnn_kcentre_workspace_bytes(int64_t R, int64_t D, int32_t k, size_t* bytes);
+int vbnn_kcentre(vbnn_ctx* ctx, const vbnn_kcentre_args* a);
+
 /* ---- the sampling-free predictive by moment propagation (additive, ABI 6; vbnn_amd/csrc/propagate.hip; not in the reference) --
  * A factorised-Gaussian posterior needs no draws to predict: one pass carries (mean a, second moment q, variance c) of every
  * activation through the network. A hidden layer is three SINGLE products of vbnn_forward (w2 = NULL, y out, no ReLU):

@@ -385,6 +385,27 @@ typedef struct vbnn_top_rows_args {
 } vbnn_top_rows_args;
 int vbnn_top_rows_workspace_bytes(int64_t R, int32_t k, size_t* bytes);
 int vbnn_top_rows(vbnn_ctx* ctx, const vbnn_top_rows_args* a);
+typedef struct vbnn_kcentre_args {
+    const float*   feat;
+    int64_t ld;
+    const float*   weight;
+    const uint8_t* exclude;
+    const int32_t* centres;
+    int64_t R;
+    int64_t D;
+    int32_t n_centres;
+    int32_t k;
+    int32_t resume;
+    int32_t reserved;
+    int32_t* index;
+    float*   key;
+    float*   dist;
+    float*   min_dist;
+    int64_t* counts;
+    void* workspace; size_t workspace_bytes;
+} vbnn_kcentre_args;
+int vbnn_kcentre_workspace_bytes(int64_t R, int64_t D, int32_t k, size_t* bytes);
+int vbnn_kcentre(vbnn_ctx* ctx, const vbnn_kcentre_args* a);
 typedef struct vbnn_relu_moments_args {
     const float* m; int64_t ld_m;
     const float* v1; const float* v2; int64_t ld_v;

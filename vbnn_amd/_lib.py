@@ -178,6 +178,17 @@ class TopRowsArgs(C.Structure):       # vbnn_top_rows_args
 TOP_ROWS_MAX_K = 4096                 # VBNN_TOP_ROWS_MAX_K
 
 
+class KcentreArgs(C.Structure):       # vbnn_kcentre_args
+    _fields_ = [("feat", _vp), ("ld", _i64), ("weight", _vp), ("exclude", _vp), ("centres", _vp), ("R", _i64), ("D", _i64),
+                ("n_centres", C.c_int32), ("k", C.c_int32), ("resume", C.c_int32), ("reserved", C.c_int32),
+                ("index", _vp), ("key", _vp), ("dist", _vp), ("min_dist", _vp), ("counts", _vp), ("workspace", _vp),
+                ("workspace_bytes", C.c_size_t)]
+
+
+KCENTRE_MAX_K = 4096                  # VBNN_KCENTRE_MAX_K
+KCENTRE_MAX_D = 8192                  # VBNN_KCENTRE_MAX_D
+
+
 class ReluMomentsArgs(C.Structure):   # vbnn_relu_moments_args
     _fields_ = [("m", _vp), ("ld_m", _i64), ("v1", _vp), ("v2", _vp), ("ld_v", _i64), ("N", _i64), ("O", _i64),
                 ("a", _vp), ("q", _vp), ("c", _vp), ("ld_out", _i64)]
@@ -315,6 +326,8 @@ _SIGS = {
     "vbnn_selective": ([_vp, C.POINTER(SelectiveArgs)], _i),
     "vbnn_top_rows_workspace_bytes": ([_i64, C.c_int32, C.POINTER(C.c_size_t)], _i),
     "vbnn_top_rows": ([_vp, C.POINTER(TopRowsArgs)], _i),
+    "vbnn_kcentre_workspace_bytes": ([_i64, _i64, C.c_int32, C.POINTER(C.c_size_t)], _i),
+    "vbnn_kcentre": ([_vp, C.POINTER(KcentreArgs)], _i),
     "vbnn_relu_moments": ([_vp, _i, C.POINTER(ReluMomentsArgs)], _i),
     "vbnn_square_shadow": ([_vp, _i, _vp, _i64, _i64, _i64, _vp, _i64], _i),
     "vbnn_logit_draws": ([_vp, C.POINTER(LogitDrawsArgs)], _i),

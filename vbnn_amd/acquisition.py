@@ -30,6 +30,28 @@ class AcquireResult:
         self.score_name = self.S = self.chunks = self.predictive = None
 
 
+class SpreadResult:
+    """FusedMLP.spread_rows' / acquire_diverse's outcome (vbnn_kcentre). Device tensors: indices (k, int32: the rows in pick
+    order; -1 past n_selected), keys (k: what each pick was ranked by -- its distance to the nearest centre, times its weight),
+    dists (k: that distance alone; NaN past n_selected), min_dist (R: every row's squared distance to the nearest centre after the
+    last pick; NaN for a void row) -- pass the result as state= to continue. Python integers: n_selected, n_candidates, n_void
+    (rows whose features or weight are not usable: never selected), n_excluded, n_ignored_centres (centre indices outside the
+    matrix). acquire_diverse also sets score_name, S, chunks and predictive (None with weighted=False)."""
+
+    def __init__(self, indices, keys, dists, min_dist, counts, n_ignored_centres=0, exclude=None):
+        self.indices, self.keys, self.dists, self.min_dist = indices, keys, dists, min_dist
+        self.n_selected, self.n_candidates, self.n_void, self.n_excluded = (int(c) for c in counts)
+        self.n_ignored_centres = int(n_ignored_centres)
+        self.exclude = exclude                     # uint8, R: what the call excluded plus its own picks (what state= carries on)
+        self.score_name = self.S = self.chunks = self.predictive = None
+
+
+def _check_spread_k(what, k):
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= L.KCENTRE_MAX_K:
+        raise ValueError(f"{what}: k = {k} (an integer in 1 .. {L.KCENTRE_MAX_K}: for more rows continue with state=)")
+    return int(k)
+
+
 def _check_k(what, k):
     if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= L.TOP_ROWS_MAX_K:
         raise ValueError(f"{what}: k = {k} (an integer in 1 .. {L.TOP_ROWS_MAX_K}: for more rows select in several calls, "
@@ -106,6 +128,42 @@ class _Acquisition:
             self._consume_draws(1, False)
         return res
 
+    def _score_refusals(self, what, name, S, map, analytic):
+        """What acquire and acquire_diverse refuse of a scored selection before any predictive runs."""
+        if analytic and map:
+            raise ValueError(f"{what}: analytic=True propagates moments through the posterior: map=True does not apply to it")
+        one_pass = not analytic and (map or self.opt.get("quicktest"))
+        draws = 1 if one_pass else int(self.opt["testSamples"] if S is None else S)
+        if name == "mutual_info" and draws == 1:
+            raise ValueError(f"{what}: score = 'mutual_info' is identically zero for one draw (map=True, quicktest or S = 1): "
+                             "give S >= 2 without map, or rank by 'entropy'")
+
+    def _score_pool(self, pool, name, S, map, analytic, row0):
+        """The scoring half of acquire and acquire_diverse: the criterion's predictive over the pool (its draws consumed as it
+        consumes them) and the score `name` of every row. Returns (vec, pred)."""
+        if analytic:                               # ("bce" / "gauss": refused there, as predict_analytic refuses them)
+            pred = (self.predict_analytic(pool, S=S, row0=row0, topk=2, keep_probs=False) if self.criterion == "nll"
+                    else self.predict_analytic(pool))
+        elif self.criterion == "nll":
+            pred = self.predict_classes(pool, S=S, map=map, row0=row0, topk=2, keep_probs=False)
+        elif self.criterion == "bce":
+            pred = self.predict_labels(pool, S=S, map=map, row0=row0)
+        else:
+            pred = self.predict_regression(pool, S=S, map=map, row0=row0)
+        if name == "least_confidence":
+            vec = 1.0 - pred.topk_prob[:, 0]
+        elif name == "margin":
+            vec = pred.topk_prob[:, 1] - pred.topk_prob[:, 0]
+        elif name == "total_variance":
+            vec = pred.row_var + pred.row_noise_var
+        elif self.criterion == "bce":
+            vec = pred.row_mutual_info if name == "mutual_info" else pred.row_entropy
+        elif name == "variance":
+            vec = pred.row_var
+        else:
+            vec = pred.mutual_info if name == "mutual_info" else pred.entropy
+        return vec, pred
+
     @_ordered
     def acquire(self, pool, k, score=None, S=None, map=False, analytic=False, exclude=None, beta=None, row0=None):
         """Choose the next k rows of the device-resident `pool` (R x input_size fp32) to label: score every row with the
@@ -149,36 +207,170 @@ class _Acquisition:
             self._consume_draws(1, False)
             res.score_name, res.S, res.chunks = name, 0, 0
             return res
-        if analytic and map:
-            raise ValueError(f"{what}: analytic=True propagates moments through the posterior: map=True does not apply to it")
-        one_pass = not analytic and (map or self.opt.get("quicktest"))
-        draws = 1 if one_pass else int(self.opt["testSamples"] if S is None else S)
-        if name == "mutual_info" and draws == 1:
-            raise ValueError(f"{what}: score = 'mutual_info' is identically zero for one draw (map=True, quicktest or S = 1): "
-                             "give S >= 2 without map, or rank by 'entropy'")
-        if analytic:                               # ("bce" / "gauss": refused there, as predict_analytic refuses them)
-            pred = (self.predict_analytic(pool, S=S, row0=row0, topk=2, keep_probs=False) if self.criterion == "nll"
-                    else self.predict_analytic(pool))
-        elif self.criterion == "nll":
-            pred = self.predict_classes(pool, S=S, map=map, row0=row0, topk=2, keep_probs=False)
-        elif self.criterion == "bce":
-            pred = self.predict_labels(pool, S=S, map=map, row0=row0)
-        else:
-            pred = self.predict_regression(pool, S=S, map=map, row0=row0)
-        if name == "least_confidence":
-            vec = 1.0 - pred.topk_prob[:, 0]
-        elif name == "margin":
-            vec = pred.topk_prob[:, 1] - pred.topk_prob[:, 0]
-        elif name == "total_variance":
-            vec = pred.row_var + pred.row_noise_var
-        elif self.criterion == "bce":
-            vec = pred.row_mutual_info if name == "mutual_info" else pred.row_entropy
-        elif name == "variance":
-            vec = pred.row_var
-        else:
-            vec = pred.mutual_info if name == "mutual_info" else pred.entropy
+        self._score_refusals(what, name, S, map, analytic)
+        vec, pred = self._score_pool(pool, name, S, map, analytic, row0)
         res = self._top_rows(what, vec.contiguous(), R, k, True, exclude, beta, self.draw + 1 if beta is not None else 0, sel_row0)
         if beta is not None:
             self._consume_draws(1, False)
         res.score_name, res.S, res.chunks, res.predictive = name, pred.S, pred.chunks, pred
+        return res
+
+    # ---- diverse acquisition: greedy k-centre over the network's own representation (vbnn_kcentre, csrc/kcentre.hip)
+    @_ordered
+    def features(self, inputs, layer=-1):
+        """The MAP activations of hidden layer `layer` (default: the last, which the final Linear reads) for R input rows: an
+        R x H fp32 device tensor. One forward on the means through the predictives' own route (chunked by opt.predict_rows,
+        which cannot change a bit; pruned, compact and held-mask networks as the predictives honour them; under a compressed
+        view only the last layer is kept row-major); bf16 activations are widened exactly. No draw is consumed and nothing of
+        the training step is written."""
+        what = "features"
+        nl = len(self.vb)
+        if isinstance(layer, bool) or int(layer) != layer or not -nl <= int(layer) < nl:
+            raise ValueError(f"{what}: layer = {layer} (one of the {nl} hidden layers: -{nl} .. {nl - 1})")
+        li = int(layer) % nl
+        from .pruning import SparsePruneResult
+        if li != nl - 1 and isinstance(self._pruned, SparsePruneResult):
+            raise ValueError(f"{what}: a compressed pruned view keeps only the last hidden layer row-major (layer = -1)")
+        p = self._predictive_plan(what, inputs, None, True, None)
+        H = self.vb[li].O
+        out = torch.empty(p.R, H, dtype=torch.float32, device=self.device)
+        for _, c0, rows, xc in self._chunks(p):
+            self._draw_forward(p, xc, rows, c0)
+            out[c0:c0 + rows].copy_(p.bufs[li + 1].x.t[:rows, :H])
+        return out
+
+    def _kcentre(self, what, feat, k, weight, exclude, centres, min_dist):
+        """The one caller of vbnn_kcentre: every argument checked already. min_dist given = resume."""
+        lib, dev = L.lib(), self.device
+        R, D = feat.shape
+        nbytes = C.c_size_t()
+        L.check(lib.vbnn_kcentre_workspace_bytes(R, D, k, C.byref(nbytes)))
+        ws = getattr(self, "_kcentre_ws", None)
+        if ws is None or ws.numel() * 8 < nbytes.value:
+            ws = self._kcentre_ws = torch.empty((nbytes.value + 7) // 8, dtype=torch.int64, device=dev)
+        index = torch.empty(k, dtype=torch.int32, device=dev)
+        key = torch.empty(k, dtype=torch.float32, device=dev)
+        dist = torch.empty(k, dtype=torch.float32, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        resume = min_dist is not None
+        md = min_dist.clone() if resume else torch.empty(R, dtype=torch.float32, device=dev)
+        a = L.KcentreArgs(feat=_p(feat), ld=feat.stride(0), weight=_p(weight), exclude=_p(exclude), centres=_p(centres), R=R, D=D,
+                          n_centres=0 if centres is None else centres.numel(), k=k, resume=int(resume), reserved=0,
+                          index=_p(index), key=_p(key), dist=_p(dist), min_dist=_p(md), counts=_p(counts), workspace=_p(ws),
+                          workspace_bytes=ws.numel() * 8)
+        L.check(lib.vbnn_kcentre(self.ctx.h, C.byref(a)))
+        both = torch.cat([counts, ws[:1]]).cpu().tolist()          # (one copy: synchronises)
+        res = SpreadResult(index, key, dist, md, both[:4], both[4])
+        taken = torch.zeros(R, dtype=torch.uint8, device=dev) if exclude is None else exclude.clone()
+        taken[index[:res.n_selected].long()] = 1
+        res.exclude = taken
+        return res
+
+    def _check_features(self, what, features, R=None):
+        if (not torch.is_tensor(features) or features.dtype != torch.float32 or not features.is_cuda
+                or features.device != self.device or features.dim() != 2 or not 1 <= features.shape[0] < 1 << 31
+                or not 1 <= features.shape[1] <= L.KCENTRE_MAX_D or (R is not None and features.shape[0] != R)):
+            raise ValueError(f"{what}: features is an fp32 device matrix of " + ("R" if R is None else f"{R}")
+                             + f" rows (1 <= R < 2^31) by 1 .. {L.KCENTRE_MAX_D} columns on the engine's device")
+        if features.stride(1) != 1 or features.stride(0) < features.shape[1]:
+            features = features.contiguous()
+        return features
+
+    @_ordered
+    def spread_rows(self, features, k, weight=None, exclude=None, centres=None, state=None):
+        """Greedy k-centre selection on any fp32 device matrix `features` (R x D, D <= 8192; a row pitch is honoured): k times
+        the candidate row farthest -- in squared Euclidean distance, weighted by weight[r] >= 0 when given -- from every row in
+        `centres` (int32 / int64 row indices, or a uint8 / bool mask of R entries: the rows already labelled) and every row
+        picked before it. Exact and deterministic: ties go to the lower row, rows with exclude[r] != 0 are never taken, rows
+        with a non-finite norm or a NaN / negative weight neither. state: a previous SpreadResult on the same features to
+        continue from (its distances are resumed, its picks and its exclude stay excluded); a + b picks in two calls are the
+        a + b picks of one. One call of vbnn_kcentre, no host synchronisation inside. Returns a SpreadResult (the counts
+        synchronise; the tensors stay on the device)."""
+        what = "spread_rows"
+        features = self._check_features(what, features)
+        R = features.shape[0]
+        k = _check_spread_k(what, k)
+        if weight is not None:
+            if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.device != self.device or weight.dim() != 1
+                    or weight.numel() != R):
+                raise ValueError(f"{what}: weight is an fp32 device vector of R = {R} entries")
+            weight = weight.contiguous()
+        exclude = _check_exclude(what, exclude, R, self.device)
+        if centres is not None:
+            if not torch.is_tensor(centres) or centres.device != self.device or centres.dim() != 1:
+                raise ValueError(f"{what}: centres is a device vector (int32 / int64 row indices, or a uint8 / bool mask of R entries)")
+            if centres.dtype in (torch.uint8, torch.bool):
+                if centres.numel() != R:
+                    raise ValueError(f"{what}: a centres mask has R = {R} entries")
+                centres = torch.nonzero(centres, as_tuple=False).flatten().to(torch.int32)
+            elif centres.dtype in (torch.int32, torch.int64):
+                centres = centres.clamp(-1, (1 << 31) - 1).to(torch.int32).contiguous()  # (an index out of range stays out of range)
+            else:
+                raise ValueError(f"{what}: centres is int32 / int64 row indices or a uint8 / bool mask")
+            if centres.numel() == 0:
+                centres = None
+        min_dist = None
+        if state is not None:
+            if (not isinstance(state, SpreadResult) or state.min_dist is None or state.min_dist.numel() != R
+                    or state.min_dist.device != self.device):
+                raise ValueError(f"{what}: state is a SpreadResult of a selection on the same R = {R} rows")
+            min_dist = state.min_dist
+            exclude = state.exclude if exclude is None else torch.maximum(exclude, state.exclude)
+        return self._kcentre(what, features, k, weight, exclude, centres, min_dist)
+
+    @_ordered
+    def acquire_diverse(self, pool, k, score=None, S=None, map=False, analytic=False, exclude=None, weighted=True,
+                        cover_labelled=True, features=None, row0=None):
+        """acquire's diverse sibling (core-set selection): choose k rows of the device-resident `pool` that are far from the
+        labelled rows and from each other in the network's own last hidden representation, each distance weighted by the
+        row's uncertainty. weighted=True scores the pool exactly as acquire does (score, S, map, analytic, row0 and the draws
+        consumed as there) and runs spread_rows on features (default: self.features(pool)) with weight = the score;
+        weighted=False is plain k-centre: no predictive runs, no draw is consumed, score must be None. exclude: the rows
+        already labelled, never taken; with cover_labelled they are also the initial centres, so the picks stay away from
+        what is labelled. Refused with the draw counter untouched: "random" (no predictive vector) and "margin" (never
+        positive) with weighted=True; what acquire refuses of "mutual_info" and analytic; features of the wrong shape, dtype
+        or device; k outside 1 .. 4096. Returns a SpreadResult."""
+        what = "acquire_diverse"
+        name = None
+        if weighted:
+            names = SCORES[self.criterion]
+            name = names[0] if score is None else score
+            if name not in names:
+                raise ValueError(f"{what}: score = {score!r} is not one of criterion = '{self.criterion}''s scores {names}")
+            if name == "random":
+                raise ValueError(f"{what}: score = 'random' has no predictive vector to weight the distances by: weighted=False "
+                                 "is plain k-centre, acquire(score='random') is uniform sampling")
+            if name == "margin":
+                raise ValueError(f"{what}: score = 'margin' (the second probability minus the top one) is never positive and a "
+                                 "weight is not negative: weight by 'least_confidence' or 'entropy'")
+        elif score is not None:
+            raise ValueError(f"{what}: weighted=False runs no predictive: score must be None (got {score!r})")
+        k = _check_spread_k(what, k)
+        if (not torch.is_tensor(pool) or pool.dim() < 1 or pool.shape[0] < 1 or pool.dtype != torch.float32 or not pool.is_cuda
+                or pool.numel() != pool.shape[0] * self.sizes[0]):
+            raise ValueError(f"{what}: pool is an fp32 device tensor of R x {self.sizes[0]} (R >= 1): a host-resident pool is "
+                             "not supported, move it to the device")
+        R = pool.shape[0]
+        if R >= 1 << 31:
+            raise ValueError(f"{what}: a pool of R = {R} rows (R < 2^31)")
+        exclude = _check_exclude(what, exclude, R, self.device)
+        if features is not None:
+            features = self._check_features(what, features, R)
+        vec = pred = None
+        if weighted:
+            self._score_refusals(what, name, S, map, analytic)
+            vec, pred = self._score_pool(pool, name, S, map, analytic, row0)
+            vec = vec.contiguous()
+        if features is None:
+            features = self._check_features(what, self.features(pool), R)
+        centres = None
+        if cover_labelled and exclude is not None:
+            centres = torch.nonzero(exclude, as_tuple=False).flatten().to(torch.int32)
+            centres = centres if centres.numel() else None
+        res = self._kcentre(what, features, k, vec, exclude, centres, None)
+        res.score_name = name
+        if pred is not None:
+            res.S, res.chunks, res.predictive = pred.S, pred.chunks, pred
+        else:
+            res.S, res.chunks = 0, 0
         return res

@@ -27,13 +27,14 @@ def _train_epoch(net, opt, x, t, order, S):
         net.update(opt)
 
 
-def active_learning(opt, x_pool, y_pool, x_test, y_test, n_init, k, rounds, score=None, beta=None, epochs=5, device=None):
+def active_learning(opt, x_pool, y_pool, x_test, y_test, n_init, k, rounds, score=None, beta=None, epochs=5, device=None, diverse=False):
     """Pool-based active learning with the NLL criterion. x_pool (R x input_size fp32) / y_pool (R int32 class indices) are the
     pool and the labels an annotator would give, x_test / y_test the held-out rows; all device tensors. The first n_init pool
     rows start labelled. Each of `rounds` rounds trains ONE engine (built once from opt; training continues from round to
     round) for `epochs` passes over the labelled rows in their order of acquisition, evaluates it on the test rows
     (predict_classes: opt.testSamples draws), then acquires k rows of the unlabelled rest by `score` (FusedMLP.acquire with
-    exclude = the labelled rows; beta as there) and labels them. Returns one dict per round: labels (the labelled rows the
+    exclude = the labelled rows; beta as there; diverse=True: FusedMLP.acquire_diverse instead -- k rows spread over the
+    network's last hidden representation, away from the labelled rows, weighted by `score`; beta must be None) and labels them. Returns one dict per round: labels (the labelled rows the
     round trained on), accuracy (percent), nll, acquired (the k rows chosen after it, best first). Deterministic for a given
     opt.seed: a second run gives the same curve."""
     if opt.get("criterion", "nll") != "nll":
@@ -44,6 +45,8 @@ def active_learning(opt, x_pool, y_pool, x_test, y_test, n_init, k, rounds, scor
         raise ValueError(f"active_learning: n_init = {n_init} (opt.batchSize = {bs} .. R = {R})")
     if int(n_init) + int(k) * int(rounds) > R:
         raise ValueError(f"active_learning: n_init + k * rounds = {int(n_init) + int(k) * int(rounds)} exceeds the pool's {R} rows")
+    if diverse and beta is not None:
+        raise ValueError("active_learning: diverse=True selects deterministically (beta must be None)")
     net = FusedMLP(opt, device=device)
     opt = dict(opt, kl_in_update=bool(getattr(net, "kl_in_update", False)))
     S = int(opt["S"]) if opt.get("type", "vb") == "vb" else 1
@@ -57,7 +60,10 @@ def active_learning(opt, x_pool, y_pool, x_test, y_test, n_init, k, rounds, scor
         for _e in range(int(epochs)):
             _train_epoch(net, opt, x, y_pool, order, S)
         ev = net.predict_classes(x_test, targets=y_test, keep_probs=False)
-        got = net.acquire(x, int(k), score=score, exclude=labelled, beta=beta)
+        if diverse:
+            got = net.acquire_diverse(x, int(k), score=score, exclude=labelled)
+        else:
+            got = net.acquire(x, int(k), score=score, exclude=labelled, beta=beta)
         new = got.indices[:got.n_selected].long()
         curve.append(dict(labels=int(order.numel()), accuracy=ev.accuracy, nll=ev.nll, acquired=new.cpu().tolist()))
         labelled[new] = 1

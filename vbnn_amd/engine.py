@@ -27,7 +27,7 @@ from .predictive import (LabelPredictResult, PredictResult, QuantilePredictResul
 from .calibration import CalibrationResult, SelectiveResult, _Calibration      # noqa: F401
 from .pruning import PruneResult, SparsePruneResult, UnitPruneResult, _Pruning      # noqa: F401
 from .checkpoint import CheckpointError, _Checkpoint, digest      # noqa: F401
-from .acquisition import AcquireResult, _Acquisition      # noqa: F401
+from .acquisition import AcquireResult, SpreadResult, _Acquisition      # noqa: F401
 
 
 _NULL_CM = contextlib.nullcontext()
