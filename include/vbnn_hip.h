@@ -1270,6 +1270,62 @@ typedef struct vbnn_kcentre_args {
 int vbnn_kcentre_workspace_bytes(int64_t R, int64_t D, int32_t k, size_t* bytes);
 int vbnn_kcentre(vbnn_ctx* ctx, const vbnn_kcentre_args* a);
 
+/* ---- rank metrics: exact AUROC and average precision per label (additive, ABI 6; vbnn_amd/csrc/ranking.hip; not in the
+ * reference) -- vbnn_rank_metrics: per column j of an R x D fp32 score matrix (row pitch ld >= D; pad columns are never read),
+ * the integers that AUROC, average precision and the hit counts at Q thresholds are ratios of.
+ * LABELS. Exactly one of two sources: `target` (R x D fp32, pitch ld_t >= D): element (r, j) is positive iff t > 0.5f, the
+ * Bernoulli criterion's own hit rule; or `target_class` (R int32): column j is positive on row r iff
+ * min(max(t, 0), D - 1) == j, the moments family's target rule, one-vs-rest.
+ * COUNTED. An element is counted unless its score is a NaN or, with `target`, its target is a NaN. An element that is not
+ * counted adds 1 to n_nan and changes nothing else.
+ * ORDER. That of the fp32 values: -0 equals +0 (the score is canonicalised as s + 0.0f -- in the kernel the bit pattern
+ * 0x80000000 becomes 0, which is that sum for every non-NaN s without depending on a denormal mode -- before vbnn_selective's
+ * monotone map: sign clear -> b ^ 0x80000000, sign set -> ~b, compared as unsigned integers); +-inf are ordinary values;
+ * subnormals order as they are. A threshold compares the same way (s >= tau[q] as fp32 values; a NaN tau[q] is met by nothing).
+ * OUTPUTS, all WRITTEN (rank metrics are not additive over rows): out holds D x (6 + 2 Q) uint64 words, column j at
+ * out + j (6 + 2 Q):
+ *   [0] n_pos, [1] n_neg, [2] n_nan;
+ *   [3] u2 = sum over the positives i of (2 #{negatives k : s_k < s_i} + #{negatives k : s_k == s_i}); AUROC = u2 / (2 n_pos
+ *       n_neg), ties counted half; u2 <= 2^61 for R < 2^31;
+ *   [4] ap_fix = sum over the positives i of floor(TP_i 2^32 / (TP_i + FP_i)), TP_i = #{positives : s >= s_i}, FP_i =
+ *       #{negatives : s >= s_i}; average precision = ap_fix / (2^32 n_pos): the step-wise sum_n (R_n - R_{n-1}) P_n over the
+ *       distinct thresholds. Each term is below its exact value by less than 1, so the host value is within 2^-32 below the
+ *       exact rational; TP 2^32 <= 2^63 and ap_fix <= 2^63: no overflow;
+ *   [5] reserved (written 0);
+ *   [6 + 2 q] tp_q = #{positives : s >= tau[q]}, [7 + 2 q] fp_q = #{negatives : s >= tau[q]} for q < Q (any floats, any order).
+ * Everything is an integer: out is bit for bit the same whatever the grid, the order in which the atomics arrive, and the
+ * arrangement of the sort.
+ * SHAPE. out is cleared; a pack pass (tiles of 4096 elements through LDS; 4 B of score and 4 B of target read with 4-byte
+ * loads, whatever the alignment) writes one 8-byte record (order word << 1 | positive; all ones for an element that is not
+ * counted, which sorts last) per element, column-major, into the first half of the workspace, and adds n_pos / n_neg / n_nan /
+ * tp_q / fp_q -- kept in registers over a workgroup's tiles, then one LDS add per thread and one 64-bit integer atomic per
+ * nonzero word and workgroup. Then ONE workgroup of 1024 threads per column: one read for the four 8-bit digit histograms of
+ * the order word, a stable least-significant-digit radix pass per digit through the two halves of the workspace (the rank inside
+ * a wave from ballots on the digit's bits, the waves' digit counts prefixed in wave order in LDS, tiles in row order; a digit
+ * on which the whole column agrees is skipped), and a walk over the sorted column that carries the running positive and
+ * negative counts across tiles and closes each run of equal order words with its share of u2 and ap_fix (a 64-bit division per
+ * run). Passes over the 8-byte records: 1 written by the pack, 1 read for the histograms, up to 4 read and written by the
+ * sort, 1 read by the walk. There is no parallelism inside a column.
+ * Integer atomics only, no allocation, no host synchronisation. The workspace needs no preparation;
+ * vbnn_rank_metrics_workspace_bytes gives 16 R D bytes (two 8-byte records per element, nothing else).
+ * VBNN_ERR_INVALID, nothing written: R < 1, D < 1, R D > 2^31 - 1; Q outside 0 .. VBNN_RANK_MAX_Q; ld < D, or ld_t < D with
+ * target; both or neither of target / target_class; a NULL score, out or workspace; workspace_bytes below
+ * vbnn_rank_metrics_workspace_bytes; a misaligned pointer (4 bytes; out and the workspace 8). */
+#define VBNN_RANK_MAX_Q 16             /* most thresholds */
+typedef struct vbnn_rank_metrics_args {
+    const float* score; int64_t ld;     /* R x D scores, ld >= D */
+    const float* target; int64_t ld_t;  /* R x D fp32 labels (positive iff > 0.5f), ld_t >= D; or NULL */
+    const int32_t* target_class;        /* R class indices (one-vs-rest); or NULL */
+    int64_t R, D;                       /* rows, columns: R D <= 2^31 - 1 */
+    int32_t Q;                          /* thresholds in tau: 0 .. VBNN_RANK_MAX_Q */
+    int32_t reserved;
+    float tau[16];                      /* VBNN_RANK_MAX_Q entries; the first Q are read */
+    uint64_t* out;                      /* D x (6 + 2 Q) words, WRITTEN (8-byte aligned) */
+    void* workspace; size_t workspace_bytes;
+} vbnn_rank_metrics_args;
+int vbnn_rank_metrics_workspace_bytes(int64_t R, int64_t D, size_t* bytes);
+int vbnn_rank_metrics(vbnn_ctx* ctx, const vbnn_rank_metrics_args* a);
+
 /* ---- the sampling-free predictive by moment propagation (additive, ABI 6; vbnn_amd/csrc/propagate.hip; not in the reference) --
  * A factorised-Gaussian posterior needs no draws to predict: one pass carries (mean a, second moment q, variance c) of every
  * activation through the network. A hidden layer is three SINGLE products of vbnn_forward (w2 = NULL, y out, no ReLU):

@@ -406,6 +406,19 @@ typedef struct vbnn_kcentre_args {
 } vbnn_kcentre_args;
 int vbnn_kcentre_workspace_bytes(int64_t R, int64_t D, int32_t k, size_t* bytes);
 int vbnn_kcentre(vbnn_ctx* ctx, const vbnn_kcentre_args* a);
+typedef struct vbnn_rank_metrics_args {
+    const float* score; int64_t ld;
+    const float* target; int64_t ld_t;
+    const int32_t* target_class;
+    int64_t R, D;
+    int32_t Q;
+    int32_t reserved;
+    float tau[16];
+    uint64_t* out;
+    void* workspace; size_t workspace_bytes;
+} vbnn_rank_metrics_args;
+int vbnn_rank_metrics_workspace_bytes(int64_t R, int64_t D, size_t* bytes);
+int vbnn_rank_metrics(vbnn_ctx* ctx, const vbnn_rank_metrics_args* a);
 typedef struct vbnn_relu_moments_args {
     const float* m; int64_t ld_m;
     const float* v1; const float* v2; int64_t ld_v;

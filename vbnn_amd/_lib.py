@@ -189,6 +189,15 @@ KCENTRE_MAX_K = 4096                  # VBNN_KCENTRE_MAX_K
 KCENTRE_MAX_D = 8192                  # VBNN_KCENTRE_MAX_D
 
 
+class RankMetricsArgs(C.Structure):   # vbnn_rank_metrics_args
+    _fields_ = [("score", _vp), ("ld", _i64), ("target", _vp), ("ld_t", _i64), ("target_class", _vp), ("R", _i64), ("D", _i64),
+                ("Q", C.c_int32), ("reserved", C.c_int32), ("tau", _f * 16), ("out", _vp), ("workspace", _vp),
+                ("workspace_bytes", C.c_size_t)]
+
+
+RANK_MAX_Q = 16                       # VBNN_RANK_MAX_Q
+
+
 class ReluMomentsArgs(C.Structure):   # vbnn_relu_moments_args
     _fields_ = [("m", _vp), ("ld_m", _i64), ("v1", _vp), ("v2", _vp), ("ld_v", _i64), ("N", _i64), ("O", _i64),
                 ("a", _vp), ("q", _vp), ("c", _vp), ("ld_out", _i64)]
@@ -328,6 +337,8 @@ _SIGS = {
     "vbnn_top_rows": ([_vp, C.POINTER(TopRowsArgs)], _i),
     "vbnn_kcentre_workspace_bytes": ([_i64, _i64, C.c_int32, C.POINTER(C.c_size_t)], _i),
     "vbnn_kcentre": ([_vp, C.POINTER(KcentreArgs)], _i),
+    "vbnn_rank_metrics_workspace_bytes": ([_i64, _i64, C.POINTER(C.c_size_t)], _i),
+    "vbnn_rank_metrics": ([_vp, C.POINTER(RankMetricsArgs)], _i),
     "vbnn_relu_moments": ([_vp, _i, C.POINTER(ReluMomentsArgs)], _i),
     "vbnn_square_shadow": ([_vp, _i, _vp, _i64, _i64, _i64, _vp, _i64], _i),
     "vbnn_logit_draws": ([_vp, C.POINTER(LogitDrawsArgs)], _i),

@@ -27,6 +27,11 @@ CalibrationResult over its minibatches (FusedMLP.calibration, into=) and logs `d
 opt.selective_coverages = [c, ...] adds `dev_acc@cov<c>`, the accuracy over the fraction c of the dev rows the predictive entropy
 ranks most certain (FusedMLP.selective).
 
+opt.ranking = True (off by default) with opt.predictive and the "bce" or "nll" criterion: the dev pass keeps each minibatch's
+probs and targets on the device (R_dev x D x 4 bytes of probabilities, and as much again for fp32 targets), calls
+FusedMLP.ranking ONCE over all of them at the end -- rank metrics are not additive over minibatches -- and logs `dev_auroc` and
+`dev_avg_precision`, the macro means of the per-label AUROC and average precision ("nll": each class against the rest).
+
 opt.criterion = "bce" (the Bernoulli likelihood: multi-label classification, binary with one label): targets are R x D fp32
 labels, the accuracy is the label accuracy 100 correct / (rows S D), and with opt.predictive the dev pass calls
 FusedMLP.predict_labels and logs `devll_pred` (the joint log-likelihood of a row's label vector), `dev_label_acc`,
@@ -173,6 +178,10 @@ class Main:
         # (FusedMLP.selective). Both need the R x C probabilities, which the predictive then keeps.
         cal_bins = int(opt.get("calibration_bins") or 0) if (opt.get("predictive") and not regression and criterion != "bce") else 0
         cal = None
+        # opt.ranking (off by default) with a "bce" or "nll" predictive: every minibatch's probs and targets are kept on the device
+        # (R_dev x D x 4 bytes of probabilities) and ranked ONCE after the pass (FusedMLP.ranking): `dev_auroc`, `dev_avg_precision`
+        ranking = bool(opt.get("ranking")) and bool(opt.get("predictive")) and not regression
+        rank_probs, rank_targets = [], []
         for t0 in starts:
             inputs, targets = dataset.create_minibatch(t0, bs, n, opt.get("geometry"))
             x, t = self._to_device(inputs, targets)
@@ -188,6 +197,9 @@ class Main:
                 pred["dev_label_acc"] += r.label_accuracy
                 pred["dev_exact_match"] += r.exact_match
                 pred["dev_label_mi"] += float(r.mutual_info.double().mean())
+                if ranking:
+                    rank_probs.append(r.probs)
+                    rank_targets.append(t)
             elif opt.get("predictive") and regression:
                 if analytic:
                     r = net.predict_analytic(x, targets=t, noise_var=tau2)
@@ -205,9 +217,9 @@ class Main:
                     pred["dev_noise_var"] += r.mean_noise_var
             elif opt.get("predictive"):    # the S-draw model average on the same minibatch (its own draws, after test()'s)
                 if analytic:
-                    r = net.predict_analytic(x, targets=t, keep_probs=bool(cal_bins))
+                    r = net.predict_analytic(x, targets=t, keep_probs=bool(cal_bins) or ranking)
                 elif getattr(net, "n_classes", 0) > 16:      # predict's head holds a row's classes in one 16-wide tile
-                    r = net.predict_classes(x, targets=t, keep_probs=bool(cal_bins))
+                    r = net.predict_classes(x, targets=t, keep_probs=bool(cal_bins) or ranking)
                 else:
                     r = net.predict(x, targets=t)
                 if cal_bins:
@@ -215,6 +227,9 @@ class Main:
                 pred["devacc_pred"] += r.accuracy
                 pred["devnll_pred"] += r.nll
                 pred["dev_mi"] += float(r.mutual_info.double().mean())
+                if ranking:
+                    rank_probs.append(r.probs)
+                    rank_targets.append(t)
         self.predictive = {k: v / len(starts) for k, v in pred.items()} if opt.get("predictive") else None
         if cal is not None:                                  # (sums over the whole dev set, not means of minibatch values)
             self.predictive.update(dev_ece=cal.ece, dev_mce=cal.mce, dev_brier=cal.brier)
@@ -222,6 +237,9 @@ class Main:
             if covs:
                 sel = net.selective(cal.entropy, cal.hit, covs)
                 self.predictive.update({f"dev_acc@cov{c:g}": a for c, a in zip(covs, sel.accuracy)})
+        if ranking and rank_probs:                           # (one call over the whole dev set: ranks do not add)
+            rk = net.ranking(rank_probs, rank_targets)
+            self.predictive.update(dev_auroc=rk.macro_auroc, dev_avg_precision=rk.macro_average_precision)
         return accuracy / len(starts), error / len(starts)
 
     def _prune_series(self, testSet):
@@ -292,7 +310,7 @@ class Main:
             rec.update(self._prune_series(testSet))       # opt.prune_report / opt.prune_eval (both off by default)
             if self.log:
                 for k in ("devacc", "trainacc", "deverr", "trainerr", "lc", "devacc_pred", "devnll_pred", "dev_mi", "devll_pred", "dev_epi_var",
-                          "dev_noise_var", "dev_ece", "dev_mce", "dev_brier"):   # main.lua:169-177 (+ opt.predictive, opt.calibration_bins)
+                          "dev_noise_var", "dev_ece", "dev_mce", "dev_brier", "dev_auroc", "dev_avg_precision"):   # main.lua:169-177 (+ opt.predictive, opt.calibration_bins, opt.ranking)
                     if k in rec:
                         self.log.add(k, rec[k])
                 for k in rec:
