@@ -3,9 +3,9 @@
 // is its shape. Many workgroups, integer atomics only, no allocation, no host synchronisation; compiled without fp
 // contraction (Makefile) so that the stochastic key is vbnn_philox.h evaluated as written.
 //
-// Shape (prune.hip's radix select, taken one step further to the rows themselves):
-//   1. three digit passes (11 + 11 + 10 bits) over the ORDER WORD of every candidate -- a 2048-bin LDS histogram per
-//      workgroup, one integer atomic per non-empty bin, a one-workgroup pick that hands prefix and rank on in device words.
+// Shape (device_prims.h's radix select, taken one step further to the rows themselves):
+//   1. the three digit passes of that plan over the ORDER WORD of every candidate, each followed by a one-workgroup pick
+//      that hands prefix and rank on in device words.
 //      They end with T (the order word of the k-th candidate), the size of its tie and `need`, the tied rows wanted.
 //   2. when the tie has to be split (more rows equal T than are needed) one count pass writes each workgroup's number of
 //      tied rows; otherwise that launch returns at once. Workgroups own CONTIGUOUS row ranges, so a prefix over those
@@ -13,12 +13,12 @@
 //   3. one take pass copies (order word, row) of every row before T and of the `need` tied rows with the lowest indices to
 //      the candidate list. Which slot a row lands in depends on the arrival order; WHICH rows land does not, and
 //   4. a one-workgroup bitonic sort of the <= 4096 (order word, row) pairs in LDS fixes the order, then writes the outputs.
-// Deterministic: the order word is re-formed from score / exclude in every pass (prune.hip re-forms its key the same way):
+// Deterministic: the order word is re-formed from score / exclude in every pass:
 // nothing per row is kept and a pass reads 4 B (+ 1 B of exclude) per row -- what reading a stored key would cost, without
 // the pass that stores it. Stochastic: a key is one Philox block per four rows and three vbnn_det_logf per row, about 50 us
 // of arithmetic a pass at R = 10^7 against 8 us of bytes, so the FIRST pass stores the keys (4 B per row of workspace) and
 // the later passes walk over them as over scores; a row whose score is a NaN keeps a NaN key there.
-#include "common.h"
+#include "device_prims.h"
 
 typedef uint32_t acq_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -55,18 +55,6 @@ struct AcqSrc {
     uint32_t k0, k1, draw;
     uint64_t row0;
 };
-struct AcqPass { int shift, bits; uint32_t prefix_mask; };
-static inline AcqPass acq_pass(int p) {
-    switch (p) {
-        case 0: return {21, 11, 0u};
-        case 1: return {10, 11, 0xffe00000u};
-        default: return {0, 10, 0xfffffc00u};
-    }
-}
-
-// the monotone map of the header (vbnn_selective's) and its inverse
-__device__ __forceinline__ uint32_t acq_order(uint32_t b) { return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u); }
-__device__ __forceinline__ uint32_t acq_unorder(uint32_t m) { return (m & 0x80000000u) ? (m ^ 0x80000000u) : ~m; }
 
 // the stochastic key of the header, op for op: x the row's Philox word, sb the score's bits (not a NaN)
 __device__ __forceinline__ float acq_race_key(uint32_t x, uint32_t sb, bool has_score, float beta) {
@@ -120,7 +108,7 @@ __device__ __forceinline__ void acq_classify(const AcqSrc& s, int64_t r, int64_t
     for (int j = 0; j < 4; ++j) {
         if (r + j >= end) { ok[j] = 0u; what[j] = ROW_NONE; continue; }
         const uint32_t sb = w.sb[j];
-        const bool nan = s.score && ((sb & 0x7fffffffu) > 0x7f800000u);
+        const bool nan = s.score && vbnn_bits_nan(sb);
         what[j] = ((w.ex >> (8 * j)) & 0xffu) ? ROW_EXCLUDED : (nan ? ROW_NAN : ROW_CANDIDATE);
         uint32_t kb = sb;
         if (s.stochastic) {
@@ -133,7 +121,7 @@ __device__ __forceinline__ void acq_classify(const AcqSrc& s, int64_t r, int64_t
             const uint32_t x = wd == 0u ? blk.v[0] : (wd == 1u ? blk.v[1] : (wd == 2u ? blk.v[2] : blk.v[3]));
             kb = __float_as_uint(acq_race_key(x, sb, s.score != nullptr, s.beta));
         }
-        const uint32_t m = acq_order(kb);
+        const uint32_t m = vbnn_order_word(kb);
         ok[j] = s.largest ? ~m : m;
     }
 }
@@ -160,7 +148,7 @@ __device__ __forceinline__ void acq_walk(const AcqSrc& s, F step) {
 }
 
 // ---------------------------------------------------------------------------------- the digit passes
-__global__ __launch_bounds__(ACQ_THREADS) void k_acq_hist(AcqSrc s, AcqPass ps, int first, const uint32_t* state,
+__global__ __launch_bounds__(ACQ_THREADS) void k_acq_hist(AcqSrc s, RadixPass ps, int first, const uint32_t* state,
                                                           uint32_t* __restrict__ ghist, uint32_t* counts_out,
                                                           uint32_t* __restrict__ keys_out) {
     __shared__ uint32_t hist[ACQ_BINS];
@@ -170,12 +158,12 @@ __global__ __launch_bounds__(ACQ_THREADS) void k_acq_hist(AcqSrc s, AcqPass ps, 
     const uint32_t prefix = ps.prefix_mask ? state[ST_PREFIX] : 0u;
     __syncthreads();
     uint32_t n_cand = 0u, n_nan = 0u, n_excl = 0u;
-    const bool vec_out = (((uintptr_t)keys_out) & 15u) == 0;
+    const bool vec_out = vbnn_al16(keys_out);
     acq_walk(s, [&](int64_t r, const uint32_t ok[4], const uint32_t what[4]) {
         if (keys_out) {                                            // the stochastic key, formed ONCE: the later passes read it as a score
             acq_u32x4 kb;                                          // (a NaN score's row keeps a NaN there: no candidate later either)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) kb[j] = what[j] == ROW_NAN ? 0x7fc00000u : acq_unorder(~ok[j]);
+            for (int j = 0; j < 4; ++j) kb[j] = what[j] == ROW_NAN ? 0x7fc00000u : vbnn_unorder_word(~ok[j]);
             if (vec_out && what[3] != ROW_NONE) {
                 reinterpret_cast<acq_u32x4*>(keys_out)[r >> 2] = kb;
             } else {
@@ -199,47 +187,26 @@ __global__ __launch_bounds__(ACQ_THREADS) void k_acq_hist(AcqSrc s, AcqPass ps, 
         if (n_excl) atomicAdd(&kinds[2], n_excl);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < (1 << ps.bits); i += ACQ_THREADS) {
-        const uint32_t c = hist[i];
-        if (c) atomicAdd(&ghist[i], c);
-    }
+    radix_flush<ACQ_THREADS>(hist, ghist, ps.bits);
     if (first && threadIdx.x < 3 && kinds[threadIdx.x]) atomicAdd(&counts_out[threadIdx.x], kinds[threadIdx.x]);
 }
 
 // one workgroup: the bin of digit `ps` that holds the rem-th smallest of the rows matching the prefix (rem is 1-based;
 // pass 0: min(k, candidates)). Writes the longer prefix and the rank inside the bin; the last pass
 // leaves T = state[ST_PREFIX], need = state[ST_NEED] and the size of T's tie in state[ST_TIED].
-__global__ __launch_bounds__(256) void k_acq_pick(const uint32_t* __restrict__ ghist, AcqPass ps, int first, uint32_t k,
+__global__ __launch_bounds__(256) void k_acq_pick(const uint32_t* __restrict__ ghist, RadixPass ps, int first, uint32_t k,
                                                   uint32_t* state) {
     __shared__ uint32_t part[256];
-    const int nbins = 1 << ps.bits, per = nbins / 256;            // 8 or 4 consecutive bins per thread
-    uint32_t c[8];
-    uint32_t own = 0u;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { c[j] = (j < per) ? ghist[threadIdx.x * per + j] : 0u; own += c[j]; }
-    part[threadIdx.x] = own;
     const uint32_t n_cand = state[ST_CAND];
     const uint32_t rem = first ? (k < n_cand ? k : n_cand) : state[ST_REM];
     const uint32_t prefix = first ? 0u : state[ST_PREFIX];
-    __syncthreads();
     if (first && threadIdx.x == 0) state[ST_KEFF] = rem;
     if (rem == 0u) return;                                         // no candidate at all: the take pass does nothing
-    uint32_t before = 0u;
-    for (int i = 0; i < (int)threadIdx.x; ++i) before += part[i];
-    if (rem > before && rem - before <= own) {                     // exactly one thread: the bins hold at least rem rows
-        uint32_t r = rem - before;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j < per) {
-                if (r <= c[j]) {
-                    state[ST_PREFIX] = prefix | ((uint32_t)(threadIdx.x * per + j) << ps.shift);
-                    state[ST_REM] = r;
-                    if (ps.shift == 0) { state[ST_NEED] = r; state[ST_TIED] = c[j]; }
-                    break;
-                }
-                r -= c[j];
-            }
-        }
+    uint32_t bin, r, tied;
+    if (radix_pick(ghist, ps, rem - 1u, part, bin, r, tied)) {     // exactly one thread: the bins hold at least rem rows
+        state[ST_PREFIX] = prefix | (bin << ps.shift);
+        state[ST_REM] = r + 1u;
+        if (ps.shift == 0) { state[ST_NEED] = r + 1u; state[ST_TIED] = tied; }
     }
 }
 
@@ -264,14 +231,9 @@ __global__ __launch_bounds__(ACQ_THREADS) void k_acq_ties(AcqSrc s, const uint32
 // ---------------------------------------------------------------------------------- the take pass
 // exclusive prefix of v over the threads of the block in thread order, and the block's total
 __device__ __forceinline__ uint32_t acq_block_scan(uint32_t v, uint32_t* sh /* ACQ_THREADS / 64 words */, uint32_t* total) {
-    uint32_t inc = v;
+    const uint32_t inc = vbnn_wave_scan_incl(v);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    __syncthreads();                                               // the previous step's readers of sh are done
+    __syncthreads();                                              // the previous step's readers of sh are done
     if (lane == 63) sh[wave] = inc;
     __syncthreads();
     uint32_t wave_base = 0u, all = 0u;
@@ -372,7 +334,7 @@ __global__ __launch_bounds__(ACQ_SORT_THREADS) void k_acq_sort(AcqSrc s, int32_t
             const uint32_t ok = (uint32_t)(e[j] >> 32), row = (uint32_t)e[j];
             index[j] = (int32_t)row;
             value[j] = s.score ? s.score[(int64_t)row < s.R ? row : 0u] : 0x3f800000u;       // no scores: the weight every candidate has, 1
-            if (key) key[j] = acq_unorder(s.largest ? ~ok : ok);
+            if (key) key[j] = vbnn_unorder_word(s.largest ? ~ok : ok);
         } else {
             index[j] = -1;
             value[j] = 0x7fc00000u;
@@ -433,7 +395,7 @@ extern "C" int vbnn_top_rows(vbnn_ctx* ctx, const vbnn_top_rows_args* a) {
     n_wg = (a->R + s.chunk - 1) / s.chunk;
     s.largest = a->largest;
     s.stochastic = a->stochastic;
-    s.vec = (((uintptr_t)a->score & 15u) == 0 && ((uintptr_t)a->exclude & 3u) == 0) ? 1 : 0;
+    s.vec = (vbnn_al16(a->score) && ((uintptr_t)a->exclude & 3u) == 0) ? 1 : 0;
     s.beta = a->beta;
     s.k0 = (uint32_t)a->seed;
     s.k1 = (uint32_t)(a->seed >> 32);
@@ -448,12 +410,12 @@ extern "C" int vbnn_top_rows(vbnn_ctx* ctx, const vbnn_top_rows_args* a) {
     if (keys) {
         later.score = keys;
         later.stochastic = 0;
-        later.vec = (((uintptr_t)keys & 15u) == 0 && ((uintptr_t)a->exclude & 3u) == 0) ? 1 : 0;
+        later.vec = (vbnn_al16(keys) && ((uintptr_t)a->exclude & 3u) == 0) ? 1 : 0;
     }
     VBNN_CHECK_HIP(hipMemsetAsync(ws, 0, ACQ_OFF_TIES * sizeof(uint32_t), ctx->stream));
     const dim3 grid((unsigned)n_wg), block(ACQ_THREADS);
     for (int p = 0; p < ACQ_PASSES; ++p) {
-        const AcqPass ps = acq_pass(p);
+        const RadixPass ps = radix_pass(p);
         uint32_t* gh = ws + (size_t)p * ACQ_BINS;
         hipLaunchKernelGGL(k_acq_hist, grid, block, 0, ctx->stream, p == 0 ? s : later, ps, p == 0 ? 1 : 0, state, gh,
                            state + ST_CAND, p == 0 ? keys : nullptr);

@@ -21,8 +21,9 @@
 // its high half (both below 2^31, so neither carries) -- then one wave per rank scans its prefix's 256 bins, finds the bin that
 // holds the rank, and adds what lies below it to the rank's `below` pair. After the last pass the prefix is the k-th key, the
 // bin's word is the tied pair. No float atomics, no allocation, no host synchronisation.
-#include "moments_common.h"
+#include "device_prims.h"
 #include <math.h>
+#include <algorithm>
 
 constexpr int CAL_MAXB = VBNN_CALIBRATION_MAX_BINS;
 constexpr int CAL_T = 1024;                    // threads of a workgroup of k_calibration: 16 waves, each with rows of its own
@@ -180,7 +181,7 @@ extern "C" int vbnn_predict_calibration(vbnn_ctx* ctx, const vbnn_calibration_ar
     CalArgs m;
     m.probs = a->probs; m.ld = a->ld; m.pred = a->pred; m.target = a->target; m.R = a->R; m.C = (int)a->C; m.M = a->bins;
     m.conf = a->conf; m.hit = a->hit; m.brier = a->brier; m.bin = a->bin; m.acc = reinterpret_cast<u64*>(a->acc);
-    m.vec = (a->ld & 3) == 0 && mom_al16(a->probs) && a->C >= 4;
+    m.vec = (a->ld & 3) == 0 && vbnn_al16(a->probs) && a->C >= 4;
     const int64_t nq = (a->C + 3) >> 2;
     int G = 64;                                            // lanes per row: the row's quads, rounded up to a power of two
     if (a->C <= 256) { G = 1; while (G < nq) G <<= 1; }
@@ -201,15 +202,6 @@ extern "C" int vbnn_predict_calibration(vbnn_ctx* ctx, const vbnn_calibration_ar
 struct SelArgs {
     const float* score; const int32_t* hit; int64_t R; int Q; int64_t k[SEL_MAXQ]; float* tau; u64* counts;
 };
-
-// the floats in ascending order as unsigned integers (-0 right below +0); every NaN is the positive quiet NaN, above +inf
-__device__ __forceinline__ unsigned sel_key(float f) {
-    const unsigned u = (f != f) ? 0x7fc00000u : __float_as_uint(f);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float sel_unkey(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
 
 __global__ __launch_bounds__(SEL_T) void k_selective(const SelArgs a) {
     __shared__ u64 hist[SEL_U][256];           // low half: keys in the bin; high half: hits among them
@@ -248,7 +240,8 @@ __global__ __launch_bounds__(SEL_T) void k_selective(const SelArgs a) {
             for (int i = tid; i < nb * 256; i += SEL_T) hist[i >> 8][i & 255] = 0ull;
             __syncthreads();
             for (int64_t i = tid; i < a.R; i += SEL_T) {
-                const unsigned key = sel_key(a.score[i]);
+                const float f = a.score[i];                // the key: every NaN is the positive quiet NaN, above +inf
+                const unsigned key = vbnn_order_word((f != f) ? 0x7fc00000u : __float_as_uint(f));
                 const u64 inc = 1ull | (a.hit[i] != 0 ? (1ull << 32) : 0ull);
                 const int digit = (int)((key >> shift) & 255u);
                 for (int u = 0; u < nb; ++u)
@@ -267,12 +260,7 @@ __global__ __launch_bounds__(SEL_T) void k_selective(const SelArgs a) {
                     c[b] = (unsigned)w; h[b] = (unsigned)(w >> 32);
                 }
                 const unsigned cs = (c[0] + c[1]) + (c[2] + c[3]), hs = (h[0] + h[1]) + (h[2] + h[3]);
-                unsigned ci = cs, hh = hs;                 // the inclusive scan over the lanes
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const unsigned oc = __shfl_up(ci, off, 64), oh = __shfl_up(hh, off, 64);
-                    if (lane >= off) { ci += oc; hh += oh; }
-                }
+                const unsigned ci = vbnn_wave_scan_incl(cs), hh = vbnn_wave_scan_incl(hs);
                 unsigned ce = ci - cs, he = hh - hs;       // below this lane's first bin
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
@@ -289,7 +277,7 @@ __global__ __launch_bounds__(SEL_T) void k_selective(const SelArgs a) {
         }
     }
     if (tid < Q) {
-        a.tau[tid] = sel_unkey(pref[tid]);
+        a.tau[tid] = __uint_as_float(vbnn_unorder_word(pref[tid]));
         a.counts[4 * tid + 0] = below[tid] & 0xffffffffull;
         a.counts[4 * tid + 1] = below[tid] >> 32;
         a.counts[4 * tid + 2] = tied[tid] & 0xffffffffull;

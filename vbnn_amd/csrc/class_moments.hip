@@ -403,9 +403,9 @@ extern "C" int vbnn_predict_class_moments(vbnn_ctx* ctx, const vbnn_class_moment
     m.probs = a->probs; m.log_probs = a->log_probs; m.ld_out = a->ld_out; m.entropy = a->entropy;
     m.expected_entropy = a->expected_entropy; m.mutual_info = a->mutual_info; m.pred = a->pred; m.topk_idx = a->topk_idx;
     m.topk_prob = a->topk_prob;
-    m.y_vec = (a->ld_y & 3) == 0 && mom_al16(a->y);
-    m.o_vec = (a->ld_out & 3) == 0 && mom_al16(a->probs) && mom_al16(a->log_probs);
-    m.s_vec = !stacked && (a->ld_state & 3) == 0 && mom_al16(a->state);
+    m.y_vec = (a->ld_y & 3) == 0 && vbnn_al16(a->y);
+    m.o_vec = (a->ld_out & 3) == 0 && vbnn_al16(a->probs) && vbnn_al16(a->log_probs);
+    m.s_vec = !stacked && (a->ld_state & 3) == 0 && vbnn_al16(a->state);
     const MomPlan<CLS_NT> plan(ctx, a->C, a->R, (stacked || a->draw == a->S - 1) && a->totals);
     VBNN_REQUIRE(plan.fits, "reduction scratch");
     m.part = plan.part;

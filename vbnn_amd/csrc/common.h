@@ -62,6 +62,9 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// THE test for 16-byte accesses at p
+__host__ __device__ static inline bool vbnn_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
 struct vbnn_ctx {
     int device;
     hipStream_t stream;

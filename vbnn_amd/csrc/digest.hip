@@ -7,7 +7,7 @@
 // change a bit of it.
 //
 // Traffic: 4 B read per word, nothing written but the one atomic per workgroup. Arithmetic: two 64-bit multiplies per word.
-#include "common.h"
+#include "device_prims.h"
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(DIGEST_THREADS) void k_digest(const uint32_t* __res
     if (gid < head) acc += digest_term(index0 + gid + 1, buf[gid]);
     if (gid < n - tail0) acc += digest_term(index0 + tail0 + gid + 1, buf[tail0 + gid]);
     // wave, then workgroup: integer sums, any order gives the same bits
-    for (int off = 32; off > 0; off >>= 1) acc += (uint64_t)__shfl_down((unsigned long long)acc, off, 64);
+    acc = vbnn_wave_sum(acc);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -3,7 +3,7 @@
 // All of them are streaming kernels: coalesced 16-byte accesses, grid capped at 2048 blocks
 // with grid-stride loops (cdna_hip_programming.md Guideline 11), reductions as per-block
 // partials in double + a deterministic single-block finish (no float atomics).
-#include "common.h"
+#include "device_prims.h"
 
 static inline int grid_for(int64_t work_items, int per_block) {
     int64_t b = (work_items + per_block - 1) / per_block;
@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void k_fill_normal(float* out, int64_t rows, i
                                 : vbnn_normal4(seed, stream, layer, draw, (uint32_t)(row0 + r), (uint32_t)q);
         float* p = out + r * ld + q * 4;
         const int valid = (int)min((int64_t)4, cols - q * 4);
-        const bool vec = ((ld & 3) == 0) && (((uintptr_t)out & 15u) == 0);
+        const bool vec = ((ld & 3) == 0) && vbnn_al16(out);
         store4<float>(p, z.v[0] * scale, z.v[1] * scale, z.v[2] * scale, z.v[3] * scale, valid, vec);
     }
 }
@@ -74,22 +74,6 @@ extern "C" int vbnn_box_muller_forms(vbnn_ctx* ctx, const uint32_t* x0, const ui
     VBNN_API_END
 }
 
-// ---------------------------------------------------------------------------------- block reduce
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-// sums `v` over the 256 threads of a block; result valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* sh /* >= 4 doubles */) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // ---------------------------------------------------------------------------------- compute_prior
 // VBLinear.lua:77-88, one sweep: 8 B read per weight (+ 12 B written when the caches are asked for).
 __global__ __launch_bounds__(256) void k_prior_partial(const float* __restrict__ means, const float* __restrict__ lvars,
@@ -122,16 +106,16 @@ __global__ __launch_bounds__(256) void k_prior_partial(const float* __restrict__
         if (stdv) stdv[t] = sd;
         if (mu_sqe) mu_sqe[t] = q;
     }
-    const double r1 = block_sum(s1, sh);
-    const double r2 = block_sum(s2, sh);
+    const double r1 = vbnn_block_sum256(s1, sh);
+    const double r2 = vbnn_block_sum256(s2, sh);
     if (threadIdx.x == 0) { partial[blockIdx.x * 2] = r1; partial[blockIdx.x * 2 + 1] = r2; }
 }
 // the deterministic finish of the prior sums: one block adds the block partials in a fixed order
 __device__ __forceinline__ void prior_finish(const double* partial, int nblocks, int64_t W, double* stats, double* sh) {
     double s1 = 0.0, s2 = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += 256) { s1 += partial[b * 2]; s2 += partial[b * 2 + 1]; }
-    const double r1 = block_sum(s1, sh);
-    const double r2 = block_sum(s2, sh);
+    const double r1 = vbnn_block_sum256(s1, sh);
+    const double r2 = vbnn_block_sum256(s2, sh);
     if (threadIdx.x == 0) { stats[0] = r1; stats[1] = r2; stats[2] = (1.0 / (double)W) * r1; stats[3] = (double)W; }
 }
 // ---- a held pruning mask in the parameter sweeps (vbnn_prepare_masked / vbnn_update_masked): O x I bytes, non-zero = pruned.
@@ -180,9 +164,9 @@ __device__ __forceinline__ void masked_stats(double r1, double r2, double n, int
 __device__ __forceinline__ void prior_finish_masked(const double* partial, const double* cnt, int nblocks, int64_t W, double* stats, double* sh) {
     double s1 = 0.0, s2 = 0.0, c = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += 256) { s1 += partial[b * 2]; s2 += partial[b * 2 + 1]; c += cnt[b]; }
-    const double r1 = block_sum(s1, sh);
-    const double r2 = block_sum(s2, sh);
-    const double n = block_sum(c, sh);
+    const double r1 = vbnn_block_sum256(s1, sh);
+    const double r2 = vbnn_block_sum256(s2, sh);
+    const double n = vbnn_block_sum256(c, sh);
     if (threadIdx.x == 0) masked_stats(r1, r2, n, W, stats);
 }
 __global__ __launch_bounds__(256) void k_prior_finish(const double* partial, int nblocks, int64_t W, double* stats) {
@@ -396,14 +380,14 @@ __global__ __launch_bounds__(256) void k_lc_partial(const float* __restrict__ me
         if (lc_elem) lc_elem[t] = lc;
         s += (double)lc;
     }
-    const double r = block_sum(s, sh);
+    const double r = vbnn_block_sum256(s, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
 __global__ __launch_bounds__(256) void k_sum_finish(const double* partial, int nblocks, double* out) {
     __shared__ double sh[4];
     double s = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += 256) s += partial[b];
-    const double r = block_sum(s, sh);
+    const double r = vbnn_block_sum256(s, sh);
     if (threadIdx.x == 0) out[0] = r;
 }
 
@@ -605,7 +589,7 @@ __global__ __launch_bounds__(256) void k_mse(const float* __restrict__ y, int64_
         if (g) store4<float>(g + n * ld_g + d, gv[0], gv[1], gv[2], gv[3], valid, vec);
     }
     if (partial) {
-        const double r = block_sum(acc, sh);
+        const double r = vbnn_block_sum256(acc, sh);
         if (threadIdx.x == 0) partial[blockIdx.x] = r;
     }
 }
@@ -613,7 +597,7 @@ __global__ __launch_bounds__(256) void k_mse_finish(const double* partial, int n
     __shared__ double sh[4];
     double a = 0.0;
     for (int b = threadIdx.x; b < nb; b += 256) a += partial[b];
-    const double r = block_sum(a, sh);
+    const double r = vbnn_block_sum256(a, sh);
     if (threadIdx.x == 0) loss[0] = (accumulate ? loss[0] : 0.0) + scale * r;
 }
 static int mse_launch(vbnn_ctx* ctx, const float* y, int64_t ld_y, const float* t, int64_t ld_t, int64_t N, int64_t D, float inv_nd,
@@ -656,10 +640,10 @@ __global__ __launch_bounds__(256) void k_gauss_nll(const float* __restrict__ y, 
     __shared__ double sh[4];
     double acc = 0.0;
     const bool d4 = (D & 3) == 0;
-    const bool m_vec = d4 && ((ld_y & 3) == 0) && (((uintptr_t)y & 15u) == 0);
+    const bool m_vec = d4 && ((ld_y & 3) == 0) && vbnn_al16(y);
     const bool s_vec = d4 && ((ld_y & 3) == 0) && ((((uintptr_t)y + 4 * (uintptr_t)D) & 15u) == 0);
-    const bool t_vec = d4 && ((ld_t & 3) == 0) && (((uintptr_t)t & 15u) == 0);
-    const bool gm_vec = d4 && ((ld_g & 3) == 0) && (((uintptr_t)g & 15u) == 0);
+    const bool t_vec = d4 && ((ld_t & 3) == 0) && vbnn_al16(t);
+    const bool gm_vec = d4 && ((ld_g & 3) == 0) && vbnn_al16(g);
     const bool gs_vec = d4 && ((ld_g & 3) == 0) && ((((uintptr_t)g + 4 * (uintptr_t)D) & 15u) == 0);
     const float half_inv = 0.5f * inv_nd;
     const int64_t D4 = (D + 3) >> 2;
@@ -689,7 +673,7 @@ __global__ __launch_bounds__(256) void k_gauss_nll(const float* __restrict__ y, 
         }
     }
     if (partial) {
-        const double r = block_sum(acc, sh);
+        const double r = vbnn_block_sum256(acc, sh);
         if (threadIdx.x == 0) partial[blockIdx.x] = r;
     }
 }
@@ -739,9 +723,9 @@ __global__ __launch_bounds__(256) void k_bce(const float* __restrict__ y, int64_
     __shared__ double sh[4];
     double acc = 0.0;
     int hits = 0;
-    const bool y_vec = ((ld_y & 3) == 0) && (((uintptr_t)y & 15u) == 0);
-    const bool t_vec = ((ld_t & 3) == 0) && (((uintptr_t)t & 15u) == 0);
-    const bool g_vec = ((ld_g & 3) == 0) && (((uintptr_t)g & 15u) == 0);
+    const bool y_vec = ((ld_y & 3) == 0) && vbnn_al16(y);
+    const bool t_vec = ((ld_t & 3) == 0) && vbnn_al16(t);
+    const bool g_vec = ((ld_g & 3) == 0) && vbnn_al16(g);
     const int64_t D4 = (D + 3) >> 2;
     const bool small = N * D4 < (1ll << 31);                // the quad's row by a 32-bit division (a 64-bit one costs several times that)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N * D4; i += (int64_t)gridDim.x * 256) {
@@ -767,10 +751,10 @@ __global__ __launch_bounds__(256) void k_bce(const float* __restrict__ y, int64_
         if (g) store4<float>(g + n * ld_g + d, gv[0], gv[1], gv[2], gv[3], valid, g_vec);
     }
     if (partial) {                                         // (block-uniform) the block's sum, and behind the sums its hit count
-        const double r = block_sum(acc, sh);
+        const double r = vbnn_block_sum256(acc, sh);
         if (threadIdx.x == 0) partial[blockIdx.x] = r;
         if (count) {
-            const double c = block_sum((double)hits, sh);  // (integers below 2^53: exact)
+            const double c = vbnn_block_sum256((double)hits, sh);  // (integers below 2^53: exact)
             if (threadIdx.x == 0) partial[gridDim.x + blockIdx.x] = c;
         }
     }
@@ -785,8 +769,8 @@ __global__ __launch_bounds__(256) void k_bce_finish(const double* partial, int n
         a += partial[b];
         if (correct) c += partial[nb + b];
     }
-    const double r = block_sum(a, sh);
-    const double h = block_sum(c, sh);
+    const double r = vbnn_block_sum256(a, sh);
+    const double h = vbnn_block_sum256(c, sh);
     if (threadIdx.x == 0) {
         loss[0] = (accumulate ? loss[0] : 0.0) + scale * r;
         if (correct && h != 0.0) atomicAdd(correct, (int)h);
@@ -836,7 +820,7 @@ __global__ __launch_bounds__(256) void k_nll_forward(const float* __restrict__ o
             corr += (best == t) ? 1 : 0;
         }
     }
-    const double r = block_sum(acc, sh);
+    const double r = vbnn_block_sum256(acc, sh);
     if (threadIdx.x == 0 && loss_sum) atomicAdd(loss_sum, r);
     if (correct && corr) atomicAdd(correct, corr);
 }
@@ -934,11 +918,11 @@ __global__ __launch_bounds__(256) void k_prep_layer(const float* __restrict__ me
             store4<T>(mu_s + r * ld_w + c, m[0], m[1], m[2], m[3], 4, true);
             store4<T>(var_s + r * ld_w + c, v[0], v[1], v[2], v[3], 4, true);
         }
-        const double r1 = block_sum(s1, sh);
-        const double r2 = block_sum(s2, sh);
+        const double r1 = vbnn_block_sum256(s1, sh);
+        const double r2 = vbnn_block_sum256(s2, sh);
         if (threadIdx.x == 0) { partial[blockIdx.x * 2] = r1; partial[blockIdx.x * 2 + 1] = r2; }
         if constexpr (MASKED) {
-            const double rn = block_sum(nk, sh);
+            const double rn = vbnn_block_sum256(nk, sh);
             if (threadIdx.x == 0) cnt_partial[blockIdx.x] = rn;
         }
         return;
@@ -991,11 +975,11 @@ __global__ __launch_bounds__(256) void k_prep_layer(const float* __restrict__ me
             __syncthreads();
         }
     }
-    const double r1 = block_sum(s1, sh);
-    const double r2 = block_sum(s2, sh);
+    const double r1 = vbnn_block_sum256(s1, sh);
+    const double r2 = vbnn_block_sum256(s2, sh);
     if (threadIdx.x == 0) { partial[blockIdx.x * 2] = r1; partial[blockIdx.x * 2 + 1] = r2; }
     if constexpr (MASKED) {
-        const double rn = block_sum(nk, sh);
+        const double rn = vbnn_block_sum256(nk, sh);
         if (threadIdx.x == 0) cnt_partial[blockIdx.x] = rn;
     }
 }
@@ -1154,7 +1138,7 @@ __device__ __forceinline__ void upd_block_reduce(double (&a)[UPD_NSUM], double* 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < UPD_NSUM; ++k) {
-        const double r = (k < 12) ? wave_sum(a[k]) : ((k & 1) ? wave_max(a[k]) : wave_min(a[k]));
+        const double r = (k < 12) ? vbnn_wave_sum(a[k]) : ((k & 1) ? wave_max(a[k]) : wave_min(a[k]));
         if (lane == 0) sh[k][wave] = r;
     }
     __syncthreads();
@@ -1279,7 +1263,7 @@ __global__ __launch_bounds__(256) void k_vb_update(UpdLayer a) {
         }
         upd_block_reduce(acc, a.partial + (size_t)blockIdx.x * UPD_NSUM, sh);
         if constexpr (MASKED) {
-            const double rn = block_sum(nk, sh[0]);
+            const double rn = vbnn_block_sum256(nk, sh[0]);
             if (threadIdx.x == 0) a.cnt_partial[blockIdx.x] = rn;
         }
         return;
@@ -1317,7 +1301,7 @@ __global__ __launch_bounds__(256) void k_vb_update(UpdLayer a) {
     }
     upd_block_reduce(acc, a.partial + (size_t)blockIdx.x * UPD_NSUM, sh);
     if constexpr (MASKED) {
-        const double rn = block_sum(nk, sh[0]);
+        const double rn = vbnn_block_sum256(nk, sh[0]);
         if (threadIdx.x == 0) a.cnt_partial[blockIdx.x] = rn;
     }
 }
@@ -1370,7 +1354,7 @@ __global__ __launch_bounds__(256) void k_update_finish(UpdFinishArgs a) {
             if (a.cnt[l]) {
                 double c = 0.0;
                 for (int b = threadIdx.x; b < nb; b += 256) c += a.cnt[l][b];
-                n_w = block_sum(c, sh[0]);
+                n_w = vbnn_block_sum256(c, sh[0]);
                 masked = true;
             }
         }
@@ -1510,7 +1494,7 @@ __global__ __launch_bounds__(256) void k_pack_input(const float* __restrict__ sr
     __shared__ float tb[64][65];
     const int64_t tiles_c = (I + 63) / 64, tiles_r = (N + 63) / 64;
     const int64_t ntiles = tiles_c * tiles_r;
-    const bool vec_in = ((ld_src & 3) == 0) && (((uintptr_t)src & 15u) == 0);
+    const bool vec_in = ((ld_src & 3) == 0) && vbnn_al16(src);
     const bool vec_t = (ld_xT & 3) == 0;
     for (int64_t tI = blockIdx.x; tI < ntiles; tI += gridDim.x) {
         const int64_t r0 = (tI / tiles_c) * 64, c0 = (tI % tiles_c) * 64;

@@ -8,8 +8,6 @@
 #include "gemm_v2.h"
 #include "gemm_v3.h"
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // 0 = choose by shape, 1 = always the general kernel (gemm_v1.h), 2 = the pipelined bf16 kernel
 // (gemm_v2.h) whenever the operands allow it, 3 = its 256 x 256 two-pass variant (gemm_v3.h) whenever they do.
 // Test / A-B hook: vbnn_debug_set(VBNN_DEBUG_GEMM_KERNEL, ..).
@@ -106,11 +104,11 @@ static EpiDx<T> make_dx_epi(const vbnn_dx_args* a) {
     EpiDx<T> e;
     e.dual = a->gv != nullptr;
     e.x = (const T*)a->x; e.ld_x = a->ld_x;
-    e.gx = a->gx; e.ld_gx = a->ld_gx; e.gx_vec = a->gx && aligned16(a->gx) && (a->ld_gx % 4 == 0);
+    e.gx = a->gx; e.ld_gx = a->ld_gx; e.gx_vec = a->gx && vbnn_al16(a->gx) && (a->ld_gx % 4 == 0);
     e.relu_mask = a->relu_mask;
     e.r_prev = a->r_prev_packed ? nullptr : (const float*)a->r_prev;
     e.r_prev_t = a->r_prev_packed ? (const T*)a->r_prev : nullptr;
-    e.ld_r_prev = a->ld_r_prev; e.r_vec = a->r_prev && aligned16(a->r_prev) && (a->ld_r_prev % 4 == 0);
+    e.ld_r_prev = a->ld_r_prev; e.r_vec = a->r_prev && vbnn_al16(a->r_prev) && (a->ld_r_prev % 4 == 0);
     e.g_prev = (T*)a->g_prev; e.gv_prev = (T*)a->gv_prev; e.ld_gp = a->ld_gp;
     e.gT_prev = (T*)a->gT_prev; e.gvT_prev = (T*)a->gvT_prev; e.ld_gpT = a->ld_gpT;
     e.I = (int)a->I; e.N = (int)a->N;
@@ -123,9 +121,9 @@ static EpiDw make_dw_epi(const vbnn_dw_args* a) {
     e.lrt = (a->x2T != nullptr) || (a->x2 != nullptr) || (a->gvT != nullptr) || (a->gv != nullptr);
     e.scale = a->scale; e.accumulate = a->accumulate;
     e.gradWeight = a->gradWeight; e.gradSum = a->gradSum;
-    e.vec = (a->I % 4 == 0) && (!a->lvars || aligned16(a->lvars)) && (!a->means || aligned16(a->means)) &&
-            (!a->gradWeight || aligned16(a->gradWeight)) && (!a->gradSum || aligned16(a->gradSum)) &&
-            (!a->grad_mu || aligned16(a->grad_mu)) && (!a->grad_lv || aligned16(a->grad_lv));
+    e.vec = (a->I % 4 == 0) && (!a->lvars || vbnn_al16(a->lvars)) && (!a->means || vbnn_al16(a->means)) &&
+            (!a->gradWeight || vbnn_al16(a->gradWeight)) && (!a->gradSum || vbnn_al16(a->gradSum)) &&
+            (!a->grad_mu || vbnn_al16(a->grad_mu)) && (!a->grad_lv || vbnn_al16(a->grad_lv));
     e.seed = a->seed; e.layer = a->layer; e.draw = a->draw; e.draw_dev = a->draw_dev;
     e.lvars = a->lvars;
     e.grad_mu = a->grad_mu; e.grad_lv = a->grad_lv;

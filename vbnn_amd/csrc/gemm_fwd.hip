@@ -8,10 +8,10 @@ static int forward_t(vbnn_ctx* ctx, const vbnn_fwd_args* a) {
     e.noise = a->w2 != nullptr ? 1 : 0;
     e.seed = a->seed; e.layer = a->layer; e.draw = a->draw; e.row0 = a->row0; e.draw_dev = a->draw_dev;
     e.rpd = (int)a->rows_per_draw;
-    e.y = a->y; e.ld_y = a->ld_y; e.y_vec = a->y && aligned16(a->y) && (a->ld_y % 4 == 0);
+    e.y = a->y; e.ld_y = a->ld_y; e.y_vec = a->y && vbnn_al16(a->y) && (a->ld_y % 4 == 0);
     e.r = a->r_packed ? nullptr : (float*)a->r;
     e.r_t = a->r_packed ? (T*)a->r : nullptr;
-    e.ld_r = a->ld_r; e.r_vec = a->r && aligned16(a->r) && (a->ld_r % 4 == 0);
+    e.ld_r = a->ld_r; e.r_vec = a->r && vbnn_al16(a->r) && (a->ld_r % 4 == 0);
     e.relu = a->relu;
     e.h = (T*)a->h; e.h2 = (T*)a->h2; e.ld_h = a->ld_h;
     e.hT = (T*)a->hT; e.h2T = (T*)a->h2T; e.ld_hT = a->ld_hT;
@@ -20,7 +20,7 @@ static int forward_t(vbnn_ctx* ctx, const vbnn_fwd_args* a) {
         // the classifier head's logits from the forward's own tiles (vbnn_fwd_args.head_slots): the two-pass 256 x 256 kernel only
         if constexpr (sizeof(T) == 2) {
             if (!head_slots_selected(a->N, a->I, a->O, a->head_C) || a->rows_per_draw != 0 || a->draw_dev || !a->head_w3 || a->hT ||
-                a->head_ld_w < a->O || a->head_ld_w % 4 != 0 || !aligned16(a->head_w3) || !aligned16(a->head_slots)) {
+                a->head_ld_w < a->O || a->head_ld_w % 4 != 0 || !vbnn_al16(a->head_w3) || !vbnn_al16(a->head_slots)) {
                 vbnn_set_error("head_slots: this forward does not take the fused form (ask vbnn_forward_head_slots; no stacked draws, "
                                "no device draw counter, no transposed output, packed 16-byte-aligned head_w3)");
                 return VBNN_ERR_INVALID;

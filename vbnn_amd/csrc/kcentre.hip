@@ -16,6 +16,7 @@
 // launches (the per-row streams of a launch are 9 B a row). min_dist, weight and the standing are read once per launch, but a
 // 4-byte scalar per row per wave has no vector form to hint.
 #include "moments_common.h"
+#include "device_prims.h"
 
 constexpr int KC_THREADS = 256;
 constexpr int KC_WAVE_MAX_D = 1024;                              // a wave per row up to here (four quads a lane), the workgroup above
@@ -41,11 +42,6 @@ struct KcPass {
     uint32_t* cnt;                                               // first launch: candidates, void, excluded
     int32_t first, resume;
 };
-
-__device__ __forceinline__ uint32_t kc_order(uint32_t b) { return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u); }
-__device__ __forceinline__ uint32_t kc_unorder(uint32_t m) { return (m & 0x80000000u) ? (m ^ 0x80000000u) : ~m; }
-__device__ __forceinline__ bool kc_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ bool kc_nan(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
 
 // columns col .. col + 3 of a row (`valid` of them inside the row; the rest read as 0 and are never loaded: a pad is not read)
 __device__ __forceinline__ void kc_load4(const float* p, float (&v)[4], int valid, int mode) {
@@ -116,8 +112,8 @@ __global__ __launch_bounds__(KC_THREADS) void k_kc_pass(KcPass a) {
 #pragma unroll
             for (int j = 0; j < NC; ++j) if (j == tid) nj = n[j];
             const int c = c_row[tid];
-            bool ok = c >= 0 && kc_finite(nj);
-            if (ok && (!a.first || a.resume)) ok = !kc_nan(a.min_dist[c]);     // a NaN stays a NaN: no race with its owner
+            bool ok = c >= 0 && vbnn_bits_finite(__float_as_uint(nj));
+            if (ok && (!a.first || a.resume)) ok = !vbnn_bits_nan(__float_as_uint(a.min_dist[c]));     // a NaN stays one: no race with its owner
             if (!ok) c_row[tid] = -1;
         }
         __syncthreads();
@@ -174,7 +170,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_kc_pass(KcPass a) {
         mom_row_sum<WPR, NC + 1>(d, red, wave);
         if (!live) continue;
         // the row's own arithmetic, the same in every thread of the row; thread 0 of the row writes
-        const bool is_void = (a.first && !a.resume) ? !kc_finite(d[NC]) : kc_nan(m_old);
+        const bool is_void = (a.first && !a.resume) ? !vbnn_bits_finite(__float_as_uint(d[NC])) : vbnn_bits_nan(__float_as_uint(m_old));
         float m = is_void ? qnan : m_old;
         bool picked = false;
         if (!is_void) {
@@ -190,7 +186,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_kc_pass(KcPass a) {
             }
         }
         if (a.first) {
-            const bool w_void = a.weight && (kc_nan(w) || w < 0.f);
+            const bool w_void = a.weight && (vbnn_bits_nan(__float_as_uint(w)) || w < 0.f);
             fl = (ex || is_void || w_void) ? 1u : 0u;
             if (tr == 0) {
                 if (ex) n_excl += 1u; else if (is_void || w_void) n_void += 1u; else n_cand += 1u;
@@ -205,8 +201,8 @@ __global__ __launch_bounds__(KC_THREADS) void k_kc_pass(KcPass a) {
                 float key;
                 if (m == inf) key = a.weight ? w : inf;
                 else key = a.weight ? m * w : m;
-                if (kc_nan(key)) key = 0.f;                       // 0 * inf
-                const unsigned long long p = ((unsigned long long)kc_order(__float_as_uint(key)) << 32) | (unsigned long long)~(uint32_t)r;
+                if (vbnn_bits_nan(__float_as_uint(key))) key = 0.f;        // 0 * inf
+                const unsigned long long p = ((unsigned long long)vbnn_order_word(__float_as_uint(key)) << 32) | (unsigned long long)~(uint32_t)r;
                 if (p > mine) mine = p;
             }
         }
@@ -241,7 +237,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_kc_finish(const unsigned long lo
         const unsigned long long b = best[j];
         if (b) {
             index[j] = (int32_t)~(uint32_t)b;
-            if (key) key[j] = kc_unorder((uint32_t)(b >> 32));
+            if (key) key[j] = vbnn_unorder_word((uint32_t)(b >> 32));
             sel += 1u;
         } else {
             index[j] = -1;
@@ -328,7 +324,7 @@ extern "C" int vbnn_kcentre(vbnn_ctx* ctx, const vbnn_kcentre_args* a) {
 
     KcPass p;
     p.feat = a->feat; p.ld = a->ld; p.R = a->R; p.D = (int32_t)a->D;
-    p.mode = (mom_al16(a->feat) && a->ld % 4 == 0) ? 2 : ((((uintptr_t)a->feat & 7u) == 0 && a->ld % 2 == 0) ? 1 : 0);
+    p.mode = (vbnn_al16(a->feat) && a->ld % 4 == 0) ? 2 : ((((uintptr_t)a->feat & 7u) == 0 && a->ld % 2 == 0) ? 1 : 0);
     p.weight = a->weight; p.exclude = a->exclude;
     p.min_dist = a->min_dist; p.flag = reinterpret_cast<uint8_t*>(ws + KC_OFF_FLAG);
     p.cnt = reinterpret_cast<uint32_t*>(ws + KC_OFF_CNT);

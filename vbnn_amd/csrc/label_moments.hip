@@ -247,10 +247,10 @@ extern "C" int vbnn_predict_label_moments(vbnn_ctx* ctx, const vbnn_label_moment
     m.probs = a->probs; m.entropy = a->entropy; m.mutual_info = a->mutual_info; m.ld_out = a->ld_out;
     m.row_entropy = a->row_entropy; m.row_mutual_info = a->row_mutual_info; m.row_log_lik = a->row_log_lik;
     m.row_marg_log_lik = a->row_marg_log_lik; m.row_hits = a->row_hits;
-    m.y_vec = d4 && (a->ld_y & 3) == 0 && mom_al16(a->y);
-    m.t_vec = a->target && d4 && (a->ld_t & 3) == 0 && mom_al16(a->target);
-    m.o_vec = d4 && (a->ld_out & 3) == 0 && mom_al16(a->probs) && mom_al16(a->entropy) && mom_al16(a->mutual_info);
-    m.s_vec = !stacked && d4 && mom_al16(a->state);
+    m.y_vec = d4 && (a->ld_y & 3) == 0 && vbnn_al16(a->y);
+    m.t_vec = a->target && d4 && (a->ld_t & 3) == 0 && vbnn_al16(a->target);
+    m.o_vec = d4 && (a->ld_out & 3) == 0 && vbnn_al16(a->probs) && vbnn_al16(a->entropy) && vbnn_al16(a->mutual_info);
+    m.s_vec = !stacked && d4 && vbnn_al16(a->state);
     const MomPlan<LAB_NT> plan(ctx, a->D, a->R, (stacked || a->draw == a->S - 1) && a->totals);
     VBNN_REQUIRE(plan.fits, "reduction scratch");
     m.part = plan.part;

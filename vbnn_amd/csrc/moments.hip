@@ -172,7 +172,7 @@ struct GaussFamily {
     static int own(const Api& a, bool d4, MomArgs& m) {
         VBNN_REQUIRE(a.s_min <= a.s_max, "the clamp: s_min <= s_max");
         m.s_min = a.s_min; m.s_max = a.s_max; m.nvar = a.noise_var; m.row_nvar = a.row_noise_var;
-        m.sh_vec = d4 && (a.ld_y & 3) == 0 && mom_al16(a.y + a.D);      // the s half starts at column D
+        m.sh_vec = d4 && (a.ld_y & 3) == 0 && vbnn_al16(a.y + a.D);      // the s half starts at column D
         return VBNN_OK;
     }
 };
@@ -346,10 +346,10 @@ static int mom_predict(vbnn_ctx* ctx, const typename F::Api* a) {
     m.draw = stacked ? 0 : a->draw; m.state = stacked ? nullptr : a->state;
     m.mean = a->mean; m.var = a->var; m.ld_out = a->ld_out; m.row_var = a->row_var; m.row_sq_err = a->row_sq_err;
     m.row_log_lik = a->row_log_lik;
-    m.y_vec = d4 && (a->ld_y & 3) == 0 && mom_al16(a->y);
-    m.t_vec = a->target && d4 && (a->ld_t & 3) == 0 && mom_al16(a->target);
-    m.o_vec = d4 && (a->ld_out & 3) == 0 && mom_al16(a->mean) && mom_al16(a->var) && mom_al16(m.nvar);
-    m.s_vec = !stacked && d4 && mom_al16(a->state);
+    m.y_vec = d4 && (a->ld_y & 3) == 0 && vbnn_al16(a->y);
+    m.t_vec = a->target && d4 && (a->ld_t & 3) == 0 && vbnn_al16(a->target);
+    m.o_vec = d4 && (a->ld_out & 3) == 0 && vbnn_al16(a->mean) && vbnn_al16(a->var) && vbnn_al16(m.nvar);
+    m.s_vec = !stacked && d4 && vbnn_al16(a->state);
     const MomPlan<F::NT> plan(ctx, a->D, a->R, (stacked || a->draw == a->S - 1) && a->totals);
     VBNN_REQUIRE(plan.fits, "reduction scratch");
     m.part = plan.part;

@@ -1,6 +1,6 @@
-// moments_common.h -- what the kernels of the moments family (moments.hip, class_moments.hip) share: the quad access paths,
-// a thread's tile of a row, the row sum whose order depends on the row width alone, the workgroup partials of the double
-// totals with the kernel that adds them, and the host's launch plan.
+// moments_common.h -- what the kernels of the moments family (moments.hip, class_moments.hip, label_moments.hip) share: the quad
+// access paths, a thread's tile of a row, the row sum whose order depends on the row width alone, the workgroup partials of the
+// double totals with the kernel that adds them, and the host's launch plan. kcentre.hip takes the quad loads and the row sum.
 #pragma once
 #include "common.h"
 #include <algorithm>
@@ -115,8 +115,6 @@ __global__ __launch_bounds__(256) void k_moments_finish(const double* __restrict
 }
 
 // ---- host side
-static inline bool mom_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // the launch plan of a family's kernels over R rows of `width` columns; `totals`: this launch finishes and the caller wants the
 // NT totals. The caller requires `fits` ("reduction scratch"), launches nb workgroups of 256 with `part`, then calls finish().
 template <int NT>

@@ -8,13 +8,7 @@
 // with the early variant's `lambda` decay of b1 (config.lua:52,56,61 hint at it) available as b1_t = b1 lambda^(t-1);
 // and plain optim.sgd:  x -= lr g  (no momentum / decay: config.lua:51-54 sets only learningRate).
 // One streaming pass per parameter tensor: 16 B read + 12 B written per element (HBM-bound).
-#include "common.h"
-
-__device__ __forceinline__ double opt_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
+#include "device_prims.h"
 
 // grad = g1 (+ g2): the reference adds the likelihood and KL parts with torch.add right before optim.adam
 // (VBLinear.lua:131-134). norms (optional): partial[block][2] = { |update|^2, |x_new|^2 } for the norm ratios.
@@ -52,7 +46,7 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ x, const float
         su += (double)up * up; sx += (double)xn * xn;
     }
     if (partial) {
-        su = opt_wave_sum(su); sx = opt_wave_sum(sx);
+        su = vbnn_wave_sum(su); sx = vbnn_wave_sum(sx);
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         if (lane == 0) { sh[0][wave] = su; sh[1][wave] = sx; }
         __syncthreads();
@@ -66,7 +60,7 @@ __global__ __launch_bounds__(256) void k_norm_finish(const double* partial, int 
     __shared__ double sh[2][4];
     double a = 0.0, b = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += 256) { a += partial[i * 2]; b += partial[i * 2 + 1]; }
-    a = opt_wave_sum(a); b = opt_wave_sum(b);
+    a = vbnn_wave_sum(a); b = vbnn_wave_sum(b);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { sh[0][wave] = a; sh[1][wave] = b; }
     __syncthreads();

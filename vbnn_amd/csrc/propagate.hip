@@ -12,7 +12,6 @@ static inline int prop_grid(int64_t items) {                   // ~8 workgroups 
     const int64_t b = std::max<int64_t>(1, (items + 255) / 256);
     return (int)std::min<int64_t>(b, (int64_t)vbnn_cu_count() * 8);
 }
-static inline bool prop_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // G consecutive floats of a row: 16-byte loads (vec) or element by element (`valid` of them; the rest read as 0)
 template <int G>
@@ -103,8 +102,8 @@ static int relu_moments_t(vbnn_ctx* ctx, const vbnn_relu_moments_args* a) {
     RmArgs p;
     p.m = a->m; p.ld_m = a->ld_m; p.v1 = a->v1; p.v2 = a->v2; p.ld_v = a->ld_v; p.N = a->N; p.O = a->O;
     p.a = a->a; p.q = a->q; p.c = a->c; p.ld_out = a->ld_out;
-    p.in_vec = prop_al16(a->m) && prop_al16(a->v1) && prop_al16(a->v2) && (a->ld_m & 3) == 0 && (a->ld_v & 3) == 0;
-    p.out_vec = prop_al16(a->a) && prop_al16(a->q) && prop_al16(a->c) && (a->ld_out % G) == 0;
+    p.in_vec = vbnn_al16(a->m) && vbnn_al16(a->v1) && vbnn_al16(a->v2) && (a->ld_m & 3) == 0 && (a->ld_v & 3) == 0;
+    p.out_vec = vbnn_al16(a->a) && vbnn_al16(a->q) && vbnn_al16(a->c) && (a->ld_out % G) == 0;
     vbnn_cu_scope scope(ctx);
     const int nb = prop_grid(a->N * ((a->O + G - 1) / G));
     if (a->v2) hipLaunchKernelGGL((k_relu_moments<T, true>), dim3(nb), dim3(256), 0, ctx->stream, p);
@@ -176,7 +175,7 @@ extern "C" int vbnn_square_shadow(vbnn_ctx* ctx, int dtype, const void* src, int
     VBNN_REQUIRE(dtype == VBNN_F32 || dtype == VBNN_BF16, "dtype");
     const int es = dtype == VBNN_F32 ? 4 : 2, G = 16 / es;
     VBNN_REQUIRE(((uintptr_t)src % es) == 0 && ((uintptr_t)dst % es) == 0, "src, dst: aligned to the element");
-    const int vec = prop_al16(src) && prop_al16(dst) && (ld_src % G) == 0 && (ld_dst % G) == 0;
+    const int vec = vbnn_al16(src) && vbnn_al16(dst) && (ld_src % G) == 0 && (ld_dst % G) == 0;
     vbnn_cu_scope scope(ctx);
     const int nb = prop_grid(rows * ((cols + G - 1) / G));
     if (dtype == VBNN_F32)
@@ -221,7 +220,7 @@ extern "C" int vbnn_logit_draws(vbnn_ctx* ctx, const vbnn_logit_draws_args* a) {
     VBNN_REQUIRE(a->ld_m < (1ll << 31) && a->ld_v < (1ll << 31), "ld_m, ld_v: too large");
     VBNN_REQUIRE(a->ld_y <= (1ll << 60) / a->R && a->draw_stride <= (1ll << 60) / a->S, "ld_y, draw_stride: too large");
     VBNN_REQUIRE(a->draw_stride >= a->R * a->ld_y, "draw_stride is at least R ld_y");
-    const int vec = prop_al16(a->y) && (a->ld_y & 3) == 0 && (a->draw_stride & 3) == 0;
+    const int vec = vbnn_al16(a->y) && (a->ld_y & 3) == 0 && (a->draw_stride & 3) == 0;
     vbnn_cu_scope scope(ctx);
     const int nb = prop_grid(a->S * a->R * ((a->C + 3) / 4));
     hipLaunchKernelGGL(k_logit_draws, dim3(nb), dim3(256), 0, ctx->stream, *a, vec);

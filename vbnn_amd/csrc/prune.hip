@@ -1,5 +1,5 @@
 // prune.hip -- signal-to-noise pruning of the VB layers (mainviz.lua:20-27): the key |mu| / sigma per weight, the exact
-// k-th smallest key over one or several layers (a radix select on the key's bits), and the pruned operand shadows the
+// k-th smallest key over one or several layers (device_prims.h's radix select on the key's bits), and the pruned operand shadows the
 // predictive path multiplies by. Streaming kernels like the sweeps of elementwise.hip: 16-byte loads, grid-stride loops,
 // integer histograms (order-independent) and double partials summed in a fixed order -- no float atomics anywhere, so
 // every output is bitwise reproducible. Compiled without fp contraction (Makefile), as the other sweeps.
@@ -7,7 +7,7 @@
 // Traffic of the chosen design: every pass re-forms the key from means / lvars (8 B per weight) -- three histogram passes
 // and the pack, 32 B read + 2 x sizeof(T) written per weight. Nothing per weight is kept between the passes: the
 // workspace is three histograms and two words of state.
-#include "common.h"
+#include "device_prims.h"
 
 // THE key: vbnn_snr_key (common.h), one definition -- the kernels below and sparse.hip's must give one weight the same bits.
 
@@ -46,31 +46,20 @@ extern "C" int vbnn_snr(vbnn_ctx* ctx, const float* means, const float* lvars, i
 
 // ---------------------------------------------------------------------------------- vbnn_prune_select
 // Non-negative floats (and the NaNs above them, sign cleared by fabsf) order as their bit patterns: the k-th smallest key
-// is found digit by digit, 11 + 11 + 10 bits. Pass p counts, over the keys that match the prefix chosen so far, the
-// values of digit p (a 2048-bin LDS histogram per workgroup, flushed with one integer atomic per non-empty bin); a
-// one-workgroup kernel then walks the histogram to the bin that holds the remaining rank and writes the longer prefix and
-// the rank within that bin to the state words the next pass reads. Counts are integers: the result does not depend on
-// the order of the atomics.
+// is found digit by digit by the plan of device_prims.h (RadixPass, radix_flush, radix_pick): a histogram pass over the keys
+// that match the prefix chosen so far, then a one-workgroup pick that writes the longer prefix and the rank within the bin
+// to the state words the next pass reads.
 constexpr int PRUNE_BINS = 2048;
 constexpr int PRUNE_PASSES = 3;
 constexpr size_t PRUNE_WS_WORDS = (size_t)PRUNE_PASSES * PRUNE_BINS + 16;       // histograms, then state { prefix, rank }
 
-struct PrunePass { int shift, bits; uint32_t prefix_mask; };
-static inline PrunePass prune_pass(int p) {
-    switch (p) {
-        case 0: return {21, 11, 0u};
-        case 1: return {10, 11, 0xffe00000u};
-        default: return {0, 10, 0xfffffc00u};
-    }
-}
-
-__device__ __forceinline__ void prune_count(uint32_t* hist, float mean, float lvar, uint32_t prefix, PrunePass ps) {
+__device__ __forceinline__ void prune_count(uint32_t* hist, float mean, float lvar, uint32_t prefix, RadixPass ps) {
     const uint32_t b = __float_as_uint(vbnn_snr_key(mean, lvar));
     if ((b & ps.prefix_mask) == prefix) atomicAdd(&hist[(b >> ps.shift) & ((1u << ps.bits) - 1u)], 1u);
 }
 
 __global__ __launch_bounds__(256) void k_prune_hist(const float* __restrict__ means, const float* __restrict__ lvars, int64_t W,
-                                                    PrunePass ps, const uint32_t* __restrict__ state, uint32_t* __restrict__ ghist) {
+                                                    RadixPass ps, const uint32_t* __restrict__ state, uint32_t* __restrict__ ghist) {
     __shared__ uint32_t hist[PRUNE_BINS];
     for (int i = threadIdx.x; i < PRUNE_BINS; i += 256) hist[i] = 0u;
     const uint32_t prefix = ps.prefix_mask ? state[0] : 0u;
@@ -86,41 +75,20 @@ __global__ __launch_bounds__(256) void k_prune_hist(const float* __restrict__ me
     for (int64_t t = (W4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; t < W; t += (int64_t)gridDim.x * 256)
         prune_count(hist, means[t], lvars[t], prefix, ps);
     __syncthreads();
-    for (int i = threadIdx.x; i < (1 << ps.bits); i += 256) {
-        const uint32_t c = hist[i];
-        if (c) atomicAdd(&ghist[i], c);
-    }
+    radix_flush<256>(hist, ghist, ps.bits);
 }
 
 // one workgroup: the bin of digit `ps` that holds rank state[1] (pass 0: k), the new prefix and the rank inside the bin
-__global__ __launch_bounds__(256) void k_prune_pick(const uint32_t* __restrict__ ghist, PrunePass ps, int first, uint32_t k,
+__global__ __launch_bounds__(256) void k_prune_pick(const uint32_t* __restrict__ ghist, RadixPass ps, int first, uint32_t k,
                                                     uint32_t* state, float* tau_dev) {
     __shared__ uint32_t part[256];
-    const int nbins = 1 << ps.bits, per = nbins / 256;            // 8 or 4 consecutive bins per thread
-    uint32_t c[8];
-    uint32_t own = 0u;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { c[j] = (j < per) ? ghist[threadIdx.x * per + j] : 0u; own += c[j]; }
-    part[threadIdx.x] = own;
     const uint32_t rank = first ? k : state[1];
     const uint32_t prefix = first ? 0u : state[0];
-    __syncthreads();
-    uint32_t before = 0u;
-    for (int i = 0; i < (int)threadIdx.x; ++i) before += part[i];
-    if (rank >= before && rank - before < own) {                   // exactly one thread: the counts sum to more than rank
-        uint32_t r = rank - before;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j < per) {
-                if (r < c[j]) {
-                    const uint32_t np = prefix | ((uint32_t)(threadIdx.x * per + j) << ps.shift);
-                    state[0] = np; state[1] = r;
-                    if (ps.shift == 0) tau_dev[0] = __uint_as_float(np);
-                    break;
-                }
-                r -= c[j];
-            }
-        }
+    uint32_t bin, r, n;
+    if (radix_pick(ghist, ps, rank, part, bin, r, n)) {            // exactly one thread: the counts sum to more than rank
+        const uint32_t np = prefix | (bin << ps.shift);
+        state[0] = np; state[1] = r;
+        if (ps.shift == 0) tau_dev[0] = __uint_as_float(np);
     }
 }
 
@@ -159,7 +127,7 @@ extern "C" int vbnn_prune_select(vbnn_ctx* ctx, int n_layers, const vbnn_prune_d
     uint32_t* state = ws + (size_t)PRUNE_PASSES * PRUNE_BINS;
     VBNN_CHECK_HIP(hipMemsetAsync(ws, 0, PRUNE_WS_WORDS * sizeof(uint32_t), ctx->stream));
     for (int p = 0; p < PRUNE_PASSES; ++p) {
-        const PrunePass ps = prune_pass(p);
+        const RadixPass ps = radix_pass(p);
         uint32_t* gh = ws + (size_t)p * PRUNE_BINS;
         for (int l = 0; l < n_layers; ++l) {
             const int64_t Wl = layers[l].O * layers[l].I;
@@ -173,14 +141,6 @@ extern "C" int vbnn_prune_select(vbnn_ctx* ctx, int n_layers, const vbnn_prune_d
 }
 
 // ---------------------------------------------------------------------------------- vbnn_prune_pack
-// sum of `v` over the 256 threads of a block in a fixed order (wave shuffles, then the four waves in order); valid in thread 0
-__device__ __forceinline__ double prune_block_sum(double v, double* sh /* 4 doubles */) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
 // One sweep per layer: a kept weight's shadows are what k_prep_layer stores (T(mean), T(expf(lvar))), a pruned weight's
 // are +0; per-workgroup partials of { pruned, sum of pruned vars, sum of vars }, added in a fixed order by the finish.
 template <typename T>
@@ -223,9 +183,9 @@ __global__ __launch_bounds__(256) void k_prune_pack(const float* __restrict__ me
                 for (int e = 0; e < valid; ++e) mp[e] = (uint8_t)((bits >> (8 * e)) & 1u);
         }
     }
-    const double r0 = prune_block_sum(n_pruned, sh);
-    const double r1 = prune_block_sum(s_pruned, sh);
-    const double r2 = prune_block_sum(s_all, sh);
+    const double r0 = vbnn_block_sum256(n_pruned, sh);
+    const double r1 = vbnn_block_sum256(s_pruned, sh);
+    const double r2 = vbnn_block_sum256(s_all, sh);
     if (threadIdx.x == 0) { partial[blockIdx.x * 3] = r0; partial[blockIdx.x * 3 + 1] = r1; partial[blockIdx.x * 3 + 2] = r2; }
 }
 
@@ -239,9 +199,9 @@ __global__ __launch_bounds__(256) void k_prune_finish(PruneFinishArgs a) {
     for (int b = threadIdx.x; b < a.nb[l]; b += 256)
 #pragma unroll
         for (int q = 0; q < 3; ++q) s[q] += a.partial[l][b * 3 + q];
-    const double r0 = prune_block_sum(s[0], sh);
-    const double r1 = prune_block_sum(s[1], sh);
-    const double r2 = prune_block_sum(s[2], sh);
+    const double r0 = vbnn_block_sum256(s[0], sh);
+    const double r1 = vbnn_block_sum256(s[1], sh);
+    const double r2 = vbnn_block_sum256(s[2], sh);
     if (threadIdx.x == 0) { a.stats[l][0] = r0; a.stats[l][1] = r1; a.stats[l][2] = r2; a.stats[l][3] = (double)a.W[l]; }
 }
 

@@ -13,7 +13,7 @@
 //     data-dependent branch), the sorted column goes back to LDS where the interpolation picks a_k, a_{k+1} by a run-time k.
 //   FIXED_NOISE, GAUSS: the column holds mu_s (and c_s = 1 / (sigma_s sqrt 2), formed in place from s); F is a running fp32
 //     sum of erfcf over the column; the root search is per lane (q_mixture).
-#include "moments_common.h"
+#include "device_prims.h"
 #include <math.h>
 #include <algorithm>
 
@@ -30,15 +30,6 @@ struct QArgs {
     float* q; int64_t ld_q, plane; float* pit; int64_t ld_pit; int* row_le; unsigned long long* count_le;
     int m_vec, s_vec;                          // 16-byte loads of the m (or y) half and of the s half
 };
-
-// the floats in ascending order as unsigned integers (adjacent floats are adjacent keys; -0 sits right below +0)
-__device__ __forceinline__ unsigned q_key(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float q_unkey(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // fills one plane of the tile: lds[s T + i] = draw s of element e0 + i. Elements at or past a.total are not read.
 __device__ __forceinline__ void q_fill(const QArgs& a, const float* base, bool vec, float* lds, int T, int64_t e0, bool act,
@@ -184,10 +175,11 @@ __device__ __forceinline__ void q_mixture(const QArgs& a, const QLane& w, const 
         float x = mean + sp[Q_MAXQ + j] * sd;
         if (!bad) {
             for (int it = 0; it < Q_MAX_ITERS; ++it) {
-                const unsigned kl = q_key(L), kh = q_key(H);
+                // the order words of the bracket's ends: adjacent floats are adjacent words
+                const unsigned kl = vbnn_order_word(__float_as_uint(L)), kh = vbnn_order_word(__float_as_uint(H));
                 if (kh - kl <= 1u) break;                  // adjacent floats: done (this lane; nobody else's result moves)
                 const bool newton = it < Q_NEWTON_ITERS && kh - kl > 16u;
-                if (!newton || !(x > L && x < H)) x = q_unkey(kl + ((kh - kl) >> 1));
+                if (!newton || !(x > L && x < H)) x = __uint_as_float(vbnn_unorder_word(kl + ((kh - kl) >> 1)));
                 const float acc = newton ? q_cdf_sum<GAUSS, true>(mu, cs, a.c_fixed, S, T, x, dacc)
                                          : q_cdf_sum<GAUSS, false>(mu, cs, a.c_fixed, S, T, x, dacc);
                 const bool below = __fdiv_rn(acc, twoS) < p;
@@ -198,7 +190,7 @@ __device__ __forceinline__ void q_mixture(const QArgs& a, const QLane& w, const 
                     // evaluation falls on the other side and the bracket closes from both ends
                     const float pad = (twoS * p * 2.4e-7f) / dacc;
                     float xn = (x + (twoS * p - acc) / dacc) + (below ? pad : -pad);
-                    xn = q_unkey(q_key(xn) + (below ? 2u : -2u));
+                    xn = __uint_as_float(vbnn_unorder_word(vbnn_order_word(__float_as_uint(xn)) + (below ? 2u : -2u)));
                     if (!(xn > L && xn < H)) xn = L + 0.5f * (H - L);
                     x = xn;                                // (still outside: the next turn takes the middle bit pattern)
                 }
@@ -291,7 +283,6 @@ extern "C" int vbnn_predict_quantiles(vbnn_ctx* ctx, const vbnn_quantiles_args* 
     VBNN_REQUIRE(!a->q || (a->ld_q >= a->D && a->ld_q <= (1ll << 60) / a->R && a->plane_stride <= (1ll << 60) / a->Q), "ld_q, plane_stride");
     VBNN_REQUIRE(!a->q || a->plane_stride >= (a->R - 1) * a->ld_q + a->D, "plane_stride holds a plane");
     VBNN_REQUIRE(!a->pit || (a->ld_pit >= a->D && a->ld_pit <= (1ll << 60) / a->R), "ld_pit");
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
     QArgs m;
     m.y = a->y; m.ld_y = a->ld_y; m.stride = a->draw_stride; m.t = a->target; m.ld_t = a->ld_t; m.R = a->R; m.D = a->D;
     m.total = a->R * a->D; m.S = (int)a->S; m.Q = a->Q;
@@ -305,8 +296,8 @@ extern "C" int vbnn_predict_quantiles(vbnn_ctx* ctx, const vbnn_quantiles_args* 
     m.q = a->q; m.ld_q = a->ld_q; m.plane = a->plane_stride; m.pit = a->pit; m.ld_pit = a->ld_pit; m.row_le = a->row_le;
     m.count_le = reinterpret_cast<unsigned long long*>(a->count_le);
     const bool quads = (a->D & 3) == 0 && (a->ld_y & 3) == 0 && (a->draw_stride & 3) == 0;
-    m.m_vec = quads && al16(a->y);
-    m.s_vec = gauss && quads && al16(a->y + a->D);
+    m.m_vec = quads && vbnn_al16(a->y);
+    m.s_vec = gauss && quads && vbnn_al16(a->y + a->D);
     // the tile: S draws (GAUSS: two planes) of T elements beside the kernel's few static words, in 64 KiB of LDS in all
     const int planes = gauss ? 2 : 1;
     int T = 256;                                           // (32: GAUSS at S = 128 alone -- half a wave idles)

@@ -14,7 +14,9 @@
 // running base of each digit moves on tile by tile. A workgroup reads in one pass what its own waves wrote in the pass before:
 // they share the CU's L1, and __syncthreads orders the accesses. The walk closes a run of equal order words at the START of the
 // next run (the last one after the loop), from the counts of positives and negatives before the run, carried across tiles.
-#include "moments_common.h"
+#include "device_prims.h"
+#include <string.h>
+#include <algorithm>
 
 constexpr int RK_MAXQ = VBNN_RANK_MAX_Q;
 constexpr int RK_WORDS = 3 + 2 * RK_MAXQ;      // the counts the pack pass takes for a column: n_pos, n_neg, n_nan, tp_q, fp_q
@@ -37,12 +39,6 @@ struct RankArgs {
     int ltc;                                   // log2 of the pack tile's columns
     int64_t ncol_t, nrow_t, nrg;               // column tiles, row tiles, workgroups that share a column tile's row tiles
 };
-
-// the floats in ascending order as unsigned integers, -0 as +0 (bits 0x80000000 -> 0: what s + 0.0f gives)
-__host__ __device__ __forceinline__ uint32_t rk_order(uint32_t u) {
-    if (u == 0x80000000u) u = 0u;
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
 
 __global__ __launch_bounds__(RK_PT) void k_rank_pack(const RankArgs a) {
     __shared__ u64 tile[RK_TILE + 64];         // [TC][TR + 1] records
@@ -67,8 +63,8 @@ __global__ __launch_bounds__(RK_PT) void k_rank_pack(const RankArgs a) {
             const int row = (tid + RK_PT * k) >> ltc;
             const int64_t r = r0 + row;
             if (cok && r < a.R) {
-                const uint32_t u = a.score[r * a.ld + c];
-                bool counted = (u & 0x7fffffffu) <= 0x7f800000u, pos;
+                uint32_t u = a.score[r * a.ld + c];
+                bool counted = !vbnn_bits_nan(u), pos;
                 if (a.target) {
                     const float t = a.target[r * a.ld_t + c];
                     counted = counted && t == t;
@@ -77,7 +73,8 @@ __global__ __launch_bounds__(RK_PT) void k_rank_pack(const RankArgs a) {
                     const int64_t t = a.tclass[r];
                     pos = (t < 0 ? 0 : (t > a.D - 1 ? a.D - 1 : t)) == c;
                 }
-                const uint32_t key = rk_order(u);
+                if (u == 0x80000000u) u = 0u;          // -0 as +0: what s + 0.0f gives
+                const uint32_t key = vbnn_order_word(u);
                 tile[col * (TR + 1) + row] = counted ? (((u64)key << 1) | (pos ? 1ull : 0ull)) : ~0ull;
                 if (!counted) ++n_nan;
                 else {
@@ -174,12 +171,7 @@ __global__ __launch_bounds__(RK_ST) void k_rank_column(const RankArgs a) {
         if (skip[p]) continue;                 // (workgroup-uniform)
         if (tid < 256) {                       // the exclusive prefix of the digit's histogram: one wave scan per 64 values
             const unsigned v = hist[p][tid];
-            unsigned inc = v;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned o = __shfl_up(inc, off, 64);
-                if (lane >= off) inc += o;
-            }
+            const unsigned inc = vbnn_wave_scan_incl(v);
             base[tid] = inc - v;
             if (lane == 63) wpos[wave] = inc;
         }
@@ -323,7 +315,8 @@ extern "C" int vbnn_rank_metrics(vbnn_ctx* ctx, const vbnn_rank_metrics_args* a)
     for (int q = 0; q < RK_MAXQ; ++q) {
         uint32_t u = 0x7fc00000u;
         if (q < a->Q) memcpy(&u, &a->tau[q], 4);
-        m.tauk[q] = (u & 0x7fffffffu) > 0x7f800000u ? 0xffffffffu : rk_order(u);
+        if (u == 0x80000000u) u = 0u;          // as the scores: -0 as +0
+        m.tauk[q] = vbnn_bits_nan(u) ? 0xffffffffu : vbnn_order_word(u);
     }
     m.out = reinterpret_cast<u64*>(a->out); m.ws = reinterpret_cast<u64*>(a->workspace);
     m.ltc = 0;

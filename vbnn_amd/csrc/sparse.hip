@@ -5,6 +5,7 @@
 // XCD's L2. The epilogue is EpiFwd (epilogues.h), the dense forward's own. No atomics, no hand-off between workgroups; every
 // sum has one fixed order. Compiled without fp contraction (Makefile): the key bits are prune.hip's.
 #include "epilogues.h"
+#include "device_prims.h"
 
 // ---------------------------------------------------------------------------------- vbnn_prune_compress
 static inline int sparse_row_grid(int64_t O) {
@@ -27,7 +28,7 @@ __global__ __launch_bounds__(256) void k_sparse_count(const float* __restrict__ 
         const float* l = lvars + o * I;
         uint32_t c = 0u;
         for (int64_t i = lane; i < I; i += 64) c += sparse_kept(m[i], l[i], tau) ? 1u : 0u;
-        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+        c = vbnn_wave_sum(c);
         if (lane == 0) row_ptr[o + 1] = c;
     }
 }
@@ -192,7 +193,7 @@ static int forward_sparse_t(vbnn_ctx* ctx, const vbnn_sparse_fwd_args* a) {
     e.noise = a->var_v != nullptr ? 1 : 0;
     e.seed = a->seed; e.layer = a->layer; e.draw = a->draw; e.row0 = a->row0; e.draw_dev = nullptr;
     e.rpd = (int)a->rows_per_draw;
-    e.y = a->y; e.ld_y = a->ld_y; e.y_vec = a->y && (((uintptr_t)a->y & 15u) == 0) && (a->ld_y % 4 == 0);
+    e.y = a->y; e.ld_y = a->ld_y; e.y_vec = a->y && vbnn_al16(a->y) && (a->ld_y % 4 == 0);
     e.r = nullptr; e.r_t = nullptr; e.ld_r = 0; e.r_vec = 0;
     e.relu = (int)a->relu;
     e.h = (T*)a->h; e.h2 = (T*)a->h2; e.ld_h = a->ld_h;

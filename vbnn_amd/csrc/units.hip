@@ -5,7 +5,7 @@
 // dense network those lists describe. Streaming kernels: 16-byte accesses, integer counts and double sums in one fixed order,
 // ordered lists from wave ballots (as k_sparse_fill) -- no float atomics, every output bitwise reproducible. Compiled without fp
 // contraction (Makefile), as the other sweeps: expf here gives the bits it gives in k_snr.
-#include "common.h"
+#include "device_prims.h"
 
 // ---------------------------------------------------------------------------------- vbnn_unit_snr
 // Quad q of a row (elements 4q .. 4q + 3) belongs to thread q % T of the row's T threads (T = 64: a wave per row; 256: a
@@ -46,17 +46,15 @@ __global__ __launch_bounds__(256) void k_unit_snr(const float* __restrict__ mean
         for (int64_t o = blockIdx.x; o < O; o += gridDim.x) {
             double sm = 0.0, sv = 0.0;
             unit_row_sums<256>(means + o * I, lvars + o * I, I, (int)threadIdx.x, vec, sm, sv);
-            for (int off = 32; off > 0; off >>= 1) { sm += __shfl_down(sm, off, 64); sv += __shfl_down(sv, off, 64); }
-            __syncthreads();                                       // (the previous row's reads of sh are over)
-            if (lane == 0) { sh[wave] = sm; sh[4 + wave] = sv; }
-            __syncthreads();
-            if (threadIdx.x == 0) key[o] = unit_key(sh[0] + sh[1] + sh[2] + sh[3], sh[4] + sh[5] + sh[6] + sh[7]);
+            sm = vbnn_block_sum256(sm, sh);                        // (its first barrier: the previous row's reads of sh are over)
+            sv = vbnn_block_sum256(sv, sh + 4);
+            if (threadIdx.x == 0) key[o] = unit_key(sm, sv);
         }
     } else {
         for (int64_t o = (int64_t)blockIdx.x * 4 + wave; o < O; o += (int64_t)gridDim.x * 4) {
             double sm = 0.0, sv = 0.0;
             unit_row_sums<64>(means + o * I, lvars + o * I, I, lane, vec, sm, sv);
-            for (int off = 32; off > 0; off >>= 1) { sm += __shfl_down(sm, off, 64); sv += __shfl_down(sv, off, 64); }
+            sm = vbnn_wave_sum(sm); sv = vbnn_wave_sum(sv);
             if (lane == 0) key[o] = unit_key(sm, sv);
         }
     }
@@ -169,7 +167,7 @@ __global__ __launch_bounds__(UNIT_THREADS) void k_unit_index(UnitKeys a, const f
     __syncthreads();
     uint32_t c = 0u;
     for (uint32_t i = threadIdx.x; i < O; i += UNIT_THREADS) c += !(key[i] < tau) ? 1u : 0u;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    c = vbnn_wave_sum(c);
     if (lane == 0 && c) atomicAdd(&st[0], c);
     __syncthreads();
     const uint32_t n0 = max(st[0], 1u);
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(UNIT_THREADS) void k_unit_index(UnitKeys a, const f
         const uint32_t u = unit_bits(key[i]);
         g += u > T ? 1u : 0u; e += u == T ? 1u : 0u;
     }
-    for (int off = 32; off > 0; off >>= 1) { g += __shfl_down(g, off, 64); e += __shfl_down(e, off, 64); }
+    g = vbnn_wave_sum(g); e = vbnn_wave_sum(e);
     if (lane == 0) { cnt[0][wave] = g; cnt[1][wave] = e; }
     __syncthreads();
     uint32_t g_all = 0u, g_run = 0u, e_run = 0u;
