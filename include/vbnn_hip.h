@@ -1153,6 +1153,68 @@ typedef struct vbnn_selective_args {
 } vbnn_selective_args;
 int vbnn_selective(vbnn_ctx* ctx, const vbnn_selective_args* a);
 
+/* Conformal prediction sets (additive, ABI 6; vbnn_amd/csrc/conformal.hip; not in the reference): split conformal prediction
+ * for a class predictive. From the class probabilities (R x C fp32) the call computes a per-row conformity score of the target
+ * and, for Q thresholds, the set of classes whose score is at or below the threshold. A threshold is one exact order statistic
+ * of the scores of a held-out calibration set (vbnn_selective on `score` gives it); the sets then hold the true class with at
+ * least the requested probability for exchangeable data, whatever the network. All arithmetic is fp32, operation by operation
+ * as written here (compiled without floating-point contraction).
+ * RANKING of a row. With w(x) = the order word of x's bits (vbnn_selective's map: sign clear -> b ^ 0x80000000, sign set -> ~b,
+ * compared as unsigned integers), class c ranks AT OR ABOVE class j iff w(p[c]) > w(p[j]), or w(p[c]) == w(p[j]) and c <= j:
+ * larger probabilities first, ties to the lower index (the project's rule everywhere), -0 below +0.
+ * SCORES. t = min(max(target[r], 0), C - 1) (the family's rule for targets).
+ *   VBNN_CONFORMAL_LAC: s(r, j) = 1 - p[j].
+ *   VBNN_CONFORMAL_APS (adaptive prediction sets, not randomised): s(r, j) = sum_c m_c with m_c = p[c] if c ranks at or above
+ *     j (j itself included), else +0 -- a MASKED row sum over all C columns by the family's row-sum rule as
+ *     vbnn_predict_calibration states it: T = 64 threads while C <= 256, 256 above; thread i adds to +0, in ascending order,
+ *     the columns 4 q .. 4 q + 3 of its quads q = i, i + T, ...; the xor butterfly 32, 16, .. 1 inside a wave; the four waves in
+ *     wave order. The order depends on C alone, not on the mask.
+ * SETS. set_q(r) = { j : s(r, j) <= qhat[q] }, an fp32 comparison; a NaN qhat[q] is taken as +inf (every class). What the
+ * method rests on: ALONG A ROW'S RANKING s IS NON-DECREASING IN FP32, SO THE SET IS A PREFIX OF THE RANKING. (LAC: p does not
+ * increase along the ranking and fl(1 - p) is monotone in p. APS: going down the ranking only turns terms of the sum from +0
+ * into a p[c] >= 0 at a fixed place of a fixed tree of additions, and a rounded addition is monotone in either argument, so
+ * no node of the tree decreases. Equal probabilities have equal LAC scores, and their APS scores follow the index.)
+ *   size[q, r] = the prefix length;  cut_index / cut_prob[q, r] = the index and the probability (a copy of its bits) of the
+ *   last admitted class, -1 and the quiet NaN 0x7fc00000 for an empty set;  member = the prefix as bits (class j is bit j & 31
+ *   of word j >> 5 of the row's ceil(C / 32) words; the unused high bits of the last word are zero);
+ *   covered[q, r] = [s(r, t) <= qhat[q]], which is the member bit of t;  score[r] = s(r, t).
+ * A row whose UNMASKED row sum (every m_c = p[c], the same rule) is NaN is SKIPPED: it adds 1 to n_nan and nothing else, its
+ * score and cut_prob are NaN, its size, cut_index and covered are -1, its member words 0, and no other row changes by a bit.
+ * Probabilities are finite values in [0, 1] (a few ulps above 1, -0 and subnormals included) or NaN; the results for other values
+ * are unspecified (no access leaves the buffers). Pad columns (ld > C) are never read; the row takes 16-byte loads where ld is a
+ * multiple of 4 and probs is 16-byte aligned, 4-byte loads otherwise (chosen per launch; a row's last, partial quad always goes
+ * element by element) -- the same bits either way.
+ * acc: 8 Q + 2 uint64 words that the call ADDS to and the caller zeroes. Per threshold q, words 8 q + 0 .. 8 q + 7:
+ *   0 rows counted (not the NaN ones);  1 covered;  2 sum of size;  3 empty sets;  4 singletons;  5 covered singletons;
+ *   6 full sets (size == C);  7 reserved (untouched).   acc[8 Q] = n_nan;  acc[8 Q + 1] reserved (untouched).
+ * Words 1 and 5 are untouched without target. Every accumulated value is an integer, so acc is bit for bit independent of the
+ * grid, the arrival order, the chunking, the number of calls and -- summed on the host -- the number of ranks. Each workgroup
+ * reduces its rows in LDS first and issues at most one global add per word (64-bit vector integer atomics). From the integers,
+ * in float64 on the host: coverage = covered / rows, mean size = sum of size / rows, and the fractions likewise.
+ * Refused with VBNN_ERR_INVALID and nothing written: an unknown kind; Q outside [0, VBNN_CONFORMAL_MAX_Q]; qhat NULL with Q > 0
+ * (it is not read with Q = 0); score or covered without target; R or C out of range; ld < C; a pointer that is not 4-byte aligned
+ * (acc: 8). The thresholds are read on the device: no host synchronisation, no allocation. */
+#define VBNN_CONFORMAL_MAX_Q 8         /* most thresholds */
+#define VBNN_CONFORMAL_LAC 0
+#define VBNN_CONFORMAL_APS 1
+typedef struct vbnn_conformal_args {
+    const float* probs; int64_t ld;     /* R x C class probabilities, ld >= C */
+    const int32_t* target;              /* R class indices, or NULL */
+    int64_t R, C;                       /* rows (1 .. 2^31 - 1), classes (>= 1) */
+    int32_t kind;                       /* VBNN_CONFORMAL_LAC | VBNN_CONFORMAL_APS */
+    int32_t Q;                          /* thresholds: 0 (scores only) .. VBNN_CONFORMAL_MAX_Q */
+    const float* qhat;                  /* Q thresholds ON THE DEVICE; NULL iff Q = 0 */
+    /* outputs, each optional (NULL to skip) */
+    float* score;                       /* R: s(r, t_r) (needs target) */
+    int32_t* size;                      /* Q x R */
+    int32_t* cut_index;                 /* Q x R */
+    float* cut_prob;                    /* Q x R */
+    int32_t* covered;                   /* Q x R (needs target) */
+    uint32_t* member;                   /* Q x R x ceil(C / 32) words */
+    uint64_t* acc;                      /* 8 Q + 2 words: the call ADDS, the caller zeroes (8-byte aligned) */
+} vbnn_conformal_args;
+int vbnn_conformal(vbnn_ctx* ctx, const vbnn_conformal_args* a);
+
 /* ---- pool acquisition for active learning (additive, ABI 6; vbnn_amd/csrc/acquire.hip; not in the reference) ----------------
  * vbnn_top_rows: the exact top-k of R fp32 scores WITH their row indices -- which rows of an unlabelled pool to label next.
  * ORDER. A key orders by its bits under vbnn_selective's monotone map (sign clear -> b ^ 0x80000000, sign set -> ~b, compared

@@ -368,6 +368,22 @@ typedef struct vbnn_selective_args {
     uint64_t* counts;
 } vbnn_selective_args;
 int vbnn_selective(vbnn_ctx* ctx, const vbnn_selective_args* a);
+typedef struct vbnn_conformal_args {
+    const float* probs; int64_t ld;
+    const int32_t* target;
+    int64_t R, C;
+    int32_t kind;
+    int32_t Q;
+    const float* qhat;
+    float* score;
+    int32_t* size;
+    int32_t* cut_index;
+    float* cut_prob;
+    int32_t* covered;
+    uint32_t* member;
+    uint64_t* acc;
+} vbnn_conformal_args;
+int vbnn_conformal(vbnn_ctx* ctx, const vbnn_conformal_args* a);
 typedef struct vbnn_top_rows_args {
     const float*   score;
     const uint8_t* exclude;

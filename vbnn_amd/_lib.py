@@ -198,6 +198,16 @@ class RankMetricsArgs(C.Structure):   # vbnn_rank_metrics_args
 RANK_MAX_Q = 16                       # VBNN_RANK_MAX_Q
 
 
+class ConformalArgs(C.Structure):     # vbnn_conformal_args
+    _fields_ = [("probs", _vp), ("ld", _i64), ("target", _vp), ("R", _i64), ("C", _i64), ("kind", C.c_int32), ("Q", C.c_int32),
+                ("qhat", _vp), ("score", _vp), ("size", _vp), ("cut_index", _vp), ("cut_prob", _vp), ("covered", _vp),
+                ("member", _vp), ("acc", _vp)]
+
+
+CONFORMAL_MAX_Q = 8                   # VBNN_CONFORMAL_MAX_Q
+CONFORMAL_LAC, CONFORMAL_APS = 0, 1
+
+
 class ReluMomentsArgs(C.Structure):   # vbnn_relu_moments_args
     _fields_ = [("m", _vp), ("ld_m", _i64), ("v1", _vp), ("v2", _vp), ("ld_v", _i64), ("N", _i64), ("O", _i64),
                 ("a", _vp), ("q", _vp), ("c", _vp), ("ld_out", _i64)]
@@ -333,6 +343,7 @@ _SIGS = {
     "vbnn_predict_quantiles": ([_vp, C.POINTER(QuantilesArgs)], _i),
     "vbnn_predict_calibration": ([_vp, C.POINTER(CalibrationArgs)], _i),
     "vbnn_selective": ([_vp, C.POINTER(SelectiveArgs)], _i),
+    "vbnn_conformal": ([_vp, C.POINTER(ConformalArgs)], _i),
     "vbnn_top_rows_workspace_bytes": ([_i64, C.c_int32, C.POINTER(C.c_size_t)], _i),
     "vbnn_top_rows": ([_vp, C.POINTER(TopRowsArgs)], _i),
     "vbnn_kcentre_workspace_bytes": ([_i64, _i64, C.c_int32, C.POINTER(C.c_size_t)], _i),

@@ -9,7 +9,7 @@ dL/dv hand-off in the epilogue, accGradParameters GEMMs with the gradSum / KL-gr
 
 Everything here is argument plumbing around include/vbnn_hip.h; torch is device memory, the
 stream and torch.distributed. The posterior predictives (predictive.py), their calibration (calibration.py), pruning (pruning.py),
-checkpoints (checkpoint.py) and the rank metrics (ranking.py) are mixins of
+checkpoints (checkpoint.py), the rank metrics (ranking.py) and the conformal prediction sets (conformal.py) are mixins of
 FusedMLP.
 """
 import contextlib
@@ -29,6 +29,7 @@ from .pruning import PruneResult, SparsePruneResult, UnitPruneResult, _Pruning  
 from .checkpoint import CheckpointError, _Checkpoint, digest      # noqa: F401
 from .acquisition import AcquireResult, SpreadResult, _Acquisition      # noqa: F401
 from .ranking import RankingResult, _Ranking      # noqa: F401
+from .conformal import ConformalCalibration, ConformalResult, _Conformal      # noqa: F401
 
 
 _NULL_CM = contextlib.nullcontext()
@@ -68,7 +69,7 @@ class _StepGraph:
             self.h = None
 
 
-class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint, _Acquisition, _Ranking):
+class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint, _Acquisition, _Ranking, _Conformal):
     def __init__(self, opt, device=None, world_size=1, rank=0, process_group=None, force_reduce=False, stream=None):
         """stream: a torch.cuda.Stream for this engine's launches (a library context of its own, hence its own reduction
         scratch and tickets): two engines on two streams may compute on one device at the same time. Default: the

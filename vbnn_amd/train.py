@@ -32,6 +32,12 @@ probs and targets on the device (R_dev x D x 4 bytes of probabilities, and as mu
 FusedMLP.ranking ONCE over all of them at the end -- rank metrics are not additive over minibatches -- and logs `dev_auroc` and
 `dev_avg_precision`, the macro means of the per-label AUROC and average precision ("nll": each class against the rest).
 
+opt.conformal_levels = [level, ...] (off by default) with opt.predictive and the NLL criterion: the dev pass keeps each
+minibatch's probs and targets on the device, calibrates split conformal prediction on the FIRST half of the dev rows
+(FusedMLP.conformal_calibrate, opt.conformal_score = "aps" by default, or "lac") and logs, from the sets of the SECOND half
+(FusedMLP.conformal_sets), `dev_cov@<level>` (the fraction of sets that hold the target; at least the level in expectation)
+and `dev_set_size@<level>` (the mean number of classes in a set).
+
 opt.criterion = "bce" (the Bernoulli likelihood: multi-label classification, binary with one label): targets are R x D fp32
 labels, the accuracy is the label accuracy 100 correct / (rows S D), and with opt.predictive the dev pass calls
 FusedMLP.predict_labels and logs `devll_pred` (the joint log-likelihood of a row's label vector), `dev_label_acc`,
@@ -182,6 +188,10 @@ class Main:
         # (R_dev x D x 4 bytes of probabilities) and ranked ONCE after the pass (FusedMLP.ranking): `dev_auroc`, `dev_avg_precision`
         ranking = bool(opt.get("ranking")) and bool(opt.get("predictive")) and not regression
         rank_probs, rank_targets = [], []
+        # opt.conformal_levels (off by default) with a class predictive: calibrated on the first half of the dev rows, measured
+        # on the second (FusedMLP.conformal_calibrate / conformal_sets): `dev_cov@<level>`, `dev_set_size@<level>`
+        conf_levels = [float(v) for v in (opt.get("conformal_levels") or [])] if (opt.get("predictive") and not regression and criterion != "bce") else []
+        conf_probs, conf_targets = [], []
         for t0 in starts:
             inputs, targets = dataset.create_minibatch(t0, bs, n, opt.get("geometry"))
             x, t = self._to_device(inputs, targets)
@@ -217,9 +227,9 @@ class Main:
                     pred["dev_noise_var"] += r.mean_noise_var
             elif opt.get("predictive"):    # the S-draw model average on the same minibatch (its own draws, after test()'s)
                 if analytic:
-                    r = net.predict_analytic(x, targets=t, keep_probs=bool(cal_bins) or ranking)
+                    r = net.predict_analytic(x, targets=t, keep_probs=bool(cal_bins) or ranking or bool(conf_levels))
                 elif getattr(net, "n_classes", 0) > 16:      # predict's head holds a row's classes in one 16-wide tile
-                    r = net.predict_classes(x, targets=t, keep_probs=bool(cal_bins) or ranking)
+                    r = net.predict_classes(x, targets=t, keep_probs=bool(cal_bins) or ranking or bool(conf_levels))
                 else:
                     r = net.predict(x, targets=t)
                 if cal_bins:
@@ -230,6 +240,9 @@ class Main:
                 if ranking:
                     rank_probs.append(r.probs)
                     rank_targets.append(t)
+                if conf_levels:
+                    conf_probs.append(r.probs)
+                    conf_targets.append(t)
         self.predictive = {k: v / len(starts) for k, v in pred.items()} if opt.get("predictive") else None
         if cal is not None:                                  # (sums over the whole dev set, not means of minibatch values)
             self.predictive.update(dev_ece=cal.ece, dev_mce=cal.mce, dev_brier=cal.brier)
@@ -240,6 +253,15 @@ class Main:
         if ranking and rank_probs:                           # (one call over the whole dev set: ranks do not add)
             rk = net.ranking(rank_probs, rank_targets)
             self.predictive.update(dev_auroc=rk.macro_auroc, dev_avg_precision=rk.macro_average_precision)
+        if conf_levels and conf_probs:
+            P, T = torch.cat(conf_probs), torch.cat(conf_targets)
+            h = P.shape[0] // 2
+            if h >= 1:
+                cc = net.conformal_calibrate(P[:h], T[:h], levels=conf_levels, score=opt.get("conformal_score") or "aps")
+                cs = net.conformal_sets(P[h:], cc, targets=T[h:])
+                for lv, cov, sz in zip(conf_levels, cs.coverage, cs.mean_size):
+                    self.predictive[f"dev_cov@{lv:g}"] = cov
+                    self.predictive[f"dev_set_size@{lv:g}"] = sz
         return accuracy / len(starts), error / len(starts)
 
     def _prune_series(self, testSet):
@@ -314,7 +336,7 @@ class Main:
                     if k in rec:
                         self.log.add(k, rec[k])
                 for k in rec:
-                    if k in ("pruned count", "pruned var mean", "held fraction") or k.startswith(("devacc_pruned@", "dev_cal@", "dev_acc@cov")):
+                    if k in ("pruned count", "pruned var mean", "held fraction") or k.startswith(("devacc_pruned@", "dev_cal@", "dev_acc@cov", "dev_cov@", "dev_set_size@")):
                         self.log.add(k, rec[k])
                 self.log.flush()
                 self.save()                                                                # main.lua:181
