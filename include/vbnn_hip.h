@@ -1215,6 +1215,89 @@ typedef struct vbnn_conformal_args {
 } vbnn_conformal_args;
 int vbnn_conformal(vbnn_ctx* ctx, const vbnn_conformal_args* a);
 
+/* Conformal intervals for a regression predictive (additive, ABI 6; vbnn_amd/csrc/conformal_interval.hip; not in the reference):
+ * split conformal prediction with one order statistic per output. Three scores are ONE expression on different planes. With a
+ * lower plane a, an upper plane b (R x D fp32, row pitch ld; plane pair p at + p * plane_stride, plane_stride = 0 when all levels
+ * share one pair), an optional width w and a target t, all fp32, one rounding per operation as written (no fused multiply-add;
+ * the division and the square root correctly rounded):
+ *   v = scale[r, d] (+ scale2[r, d] when scale2 is given), then v = v + scale_add (always added);
+ *   u = sqrtf(v) when scale_is_variance, else v;   w = w_min where u < w_min, else u (a NaN u stays NaN; w_min > 0);
+ *   m = the larger of (a - t) and (t - b), NaN when either difference is NaN;
+ *   s = m / w with a scale plane, m without (no division);
+ *   interval at the threshold q:  lo' = a - q * w,  hi' = b + q * w  (the product, then the sum; q itself without a scale);
+ *   covered = [ s <= q ], a float comparison; a NaN q is taken as +inf.
+ * "absolute": a = b = the mean, no scale (s = |t - mean| exactly). "scaled": a = b = the mean, scale = the variance(s).
+ * "cqr" (conformalised quantile regression): a, b the lower and upper quantile planes of every level, no scale; q may be
+ * negative, lo' > hi' is an EMPTY interval and is counted. COVERED FOLLOWS THE SCORE, not a comparison of t with the rounded end
+ * points: the two differ for targets within a few ulps of an end point, and only the score is the statistic that was calibrated.
+ * A NaN ELEMENT of plane pair p: a, b or w is NaN, or -- with a target -- s is NaN (a NaN t; inf - inf). Inputs are finite
+ * or NaN; other values give what the operations above give.
+ * SCORE MODE, Q = 0 (target required): score[p, r, d] = s (the quiet NaN 0x7fc00000 for a NaN element), row_score[p, r] = the
+ * maximum of the row's scores, NaN if any is NaN (a maximum is exact: no order rule). acc: 2 words, ADDED to:
+ *   { NaN elements, rows with a NaN element }, both over all P plane pairs.
+ * INTERVAL MODE, 1 <= Q <= VBNN_CONFORMAL_MAX_Q, P = 1 or P = Q (level j reads plane pair j). The thresholds are read ON THE
+ * DEVICE: level j, column d at qhat[j * ld_qhat + (per_column ? d : 0)]. Outputs, each optional: lo, hi (Q x R x D; the quiet
+ * NaN for a NaN element); with a target covered (Q x R x D uint8: 1 / 0, 255 for a NaN element) and row_covered (Q x R int32:
+ * the row's covered outputs, -1 for a row with a NaN element). acc: 8 Q + 2 uint64 words, ADDED to. Per level j, 8 j + ..:
+ *   0 elements counted (not the NaN ones);  1 covered elements;  2 rows counted (those without a NaN element);
+ *   3 rows with EVERY output covered;  4 empty intervals (lo' > hi') among the elements counted;  5 .. 7 reserved (untouched).
+ *   acc[8 Q] = NaN elements, acc[8 Q + 1] = rows with a NaN element, both over the P plane pairs.
+ * Words 1 and 3 are untouched without a target. A NaN element changes no other element by a bit. Every accumulated value is an
+ * integer: acc is bit for bit independent of the grid, the arrival order, the chunking and the number of calls; a workgroup
+ * reduces in LDS and issues at most one global add per word. Loads and stores are 16-byte where every pitch in use (ld, ld_s,
+ * ld_t, plane_stride; D for the outputs) is a multiple of 4 and the bases are 16-byte aligned, 4-byte otherwise, chosen per
+ * launch -- the same bits either way. Pad columns are never read.
+ * Refused with VBNN_ERR_INVALID and nothing written: P outside [1, 8]; Q outside [0, 8]; Q >= 1 with P not in {1, Q}; Q = 0
+ * without target; covered or row_covered without target; score or row_score with Q >= 1; lo, hi, covered or row_covered with
+ * Q = 0; qhat NULL with Q >= 1; scale2 without scale; w_min not above 0 with a scale; R or D out of range; a pitch below D; a
+ * pointer that is not 4-byte aligned (acc: 8). No host synchronisation, no allocation. */
+typedef struct vbnn_conformal_interval_args {
+    const float* lower; const float* upper;   /* P plane pairs of R x D (the same pointer for a = b) */
+    int64_t ld;                         /* row pitch of both, >= D */
+    int64_t plane_stride;               /* floats between plane pairs; 0: one pair for every level (P = 1) */
+    int32_t P;                          /* plane pairs: 1 .. VBNN_CONFORMAL_MAX_Q */
+    int32_t Q;                          /* thresholds: 0 (score mode) .. VBNN_CONFORMAL_MAX_Q */
+    const float* scale; const float* scale2;  /* R x D each, or NULL (scale2 needs scale) */
+    int64_t ld_s;                       /* row pitch of both, >= D */
+    float scale_add;                    /* added to the scale sum */
+    int32_t scale_is_variance;          /* nonzero: the width is the square root */
+    float w_min;                        /* smallest width (> 0) */
+    int32_t per_column;                 /* nonzero: a threshold per column */
+    const float* target; int64_t ld_t;  /* R x D, or NULL (interval mode only) */
+    int64_t R, D;                       /* rows (1 .. 2^31 - 1), outputs (>= 1) */
+    const float* qhat; int64_t ld_qhat; /* thresholds ON THE DEVICE; NULL iff Q = 0 */
+    /* outputs, each optional (NULL to skip) */
+    float* score;                       /* P x R x D (score mode) */
+    float* row_score;                   /* P x R (score mode) */
+    float* lo; float* hi;               /* Q x R x D */
+    uint8_t* covered;                   /* Q x R x D (needs target) */
+    int32_t* row_covered;               /* Q x R (needs target) */
+    uint64_t* acc;                      /* 2 (score mode) or 8 Q + 2 words: the call ADDS, the caller zeroes (8-byte aligned) */
+} vbnn_conformal_interval_args;
+int vbnn_conformal_interval(vbnn_ctx* ctx, const vbnn_conformal_interval_args* a);
+
+/* Column-wise order statistics (same file): for every column d of an R x D fp32 matrix x (row pitch ld) and each of Q ranks
+ * k[j] (1-based, 1 <= k <= R, shared by the columns; any order, repeats allowed),
+ *   tau[j * ld_tau + d] = the value of the k[j]-th smallest key of column d under vbnn_selective's key rule exactly (order word
+ *   of the bits, -0 below +0, every NaN the positive quiet NaN 0x7fc00000 above +inf);
+ *   counts[(j * D + d) * 2 ..] = { keys below tau's, keys equal to tau's } (optional);  n_nan[d] = NaN keys (optional).
+ * All outputs are WRITTEN. An exact radix select on integer counts (four 8-bit digits; a workgroup owns 16 neighbouring
+ * columns), bit for bit independent of the grid; no float atomics, no allocation, no host synchronisation. D = 1 is one
+ * workgroup, as vbnn_selective is. Refused with VBNN_ERR_INVALID: a null x or tau; R outside [1, 2^31); D < 1; ld < D; ld_tau
+ * < D; Q outside [1, VBNN_SELECT_COLUMNS_MAX_Q]; a rank outside [1, R]; a pointer that is not 4-byte aligned. */
+#define VBNN_SELECT_COLUMNS_MAX_Q 8    /* most ranks */
+typedef struct vbnn_select_columns_args {
+    const float* x; int64_t ld;         /* R x D, ld >= D */
+    int64_t R, D;
+    int32_t Q;                          /* ranks in k */
+    int32_t reserved;
+    int64_t k[8];                       /* VBNN_SELECT_COLUMNS_MAX_Q entries; the first Q are read */
+    float* tau; int64_t ld_tau;         /* Q x D, ld_tau >= D */
+    uint32_t* counts;                   /* Q x D x 2, or NULL */
+    uint32_t* n_nan;                    /* D, or NULL */
+} vbnn_select_columns_args;
+int vbnn_select_columns(vbnn_ctx* ctx, const vbnn_select_columns_args* a);
+
 /* ---- pool acquisition for active learning (additive, ABI 6; vbnn_amd/csrc/acquire.hip; not in the reference) ----------------
  * vbnn_top_rows: the exact top-k of R fp32 scores WITH their row indices -- which rows of an unlabelled pool to label next.
  * ORDER. A key orders by its bits under vbnn_selective's monotone map (sign clear -> b ^ 0x80000000, sign set -> ~b, compared

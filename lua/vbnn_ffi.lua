@@ -384,6 +384,40 @@ typedef struct vbnn_conformal_args {
     uint64_t* acc;
 } vbnn_conformal_args;
 int vbnn_conformal(vbnn_ctx* ctx, const vbnn_conformal_args* a);
+typedef struct vbnn_conformal_interval_args {
+    const float* lower; const float* upper;
+    int64_t ld;
+    int64_t plane_stride;
+    int32_t P;
+    int32_t Q;
+    const float* scale; const float* scale2;
+    int64_t ld_s;
+    float scale_add;
+    int32_t scale_is_variance;
+    float w_min;
+    int32_t per_column;
+    const float* target; int64_t ld_t;
+    int64_t R, D;
+    const float* qhat; int64_t ld_qhat;
+    float* score;
+    float* row_score;
+    float* lo; float* hi;
+    uint8_t* covered;
+    int32_t* row_covered;
+    uint64_t* acc;
+} vbnn_conformal_interval_args;
+int vbnn_conformal_interval(vbnn_ctx* ctx, const vbnn_conformal_interval_args* a);
+typedef struct vbnn_select_columns_args {
+    const float* x; int64_t ld;
+    int64_t R, D;
+    int32_t Q;
+    int32_t reserved;
+    int64_t k[8];
+    float* tau; int64_t ld_tau;
+    uint32_t* counts;
+    uint32_t* n_nan;
+} vbnn_select_columns_args;
+int vbnn_select_columns(vbnn_ctx* ctx, const vbnn_select_columns_args* a);
 typedef struct vbnn_top_rows_args {
     const float*   score;
     const uint8_t* exclude;

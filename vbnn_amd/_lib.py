@@ -208,6 +208,22 @@ CONFORMAL_MAX_Q = 8                   # VBNN_CONFORMAL_MAX_Q
 CONFORMAL_LAC, CONFORMAL_APS = 0, 1
 
 
+class ConformalIntervalArgs(C.Structure):     # vbnn_conformal_interval_args
+    _fields_ = [("lower", _vp), ("upper", _vp), ("ld", _i64), ("plane_stride", _i64), ("P", C.c_int32), ("Q", C.c_int32),
+                ("scale", _vp), ("scale2", _vp), ("ld_s", _i64), ("scale_add", _f), ("scale_is_variance", C.c_int32),
+                ("w_min", _f), ("per_column", C.c_int32), ("target", _vp), ("ld_t", _i64), ("R", _i64), ("D", _i64),
+                ("qhat", _vp), ("ld_qhat", _i64), ("score", _vp), ("row_score", _vp), ("lo", _vp), ("hi", _vp),
+                ("covered", _vp), ("row_covered", _vp), ("acc", _vp)]
+
+
+class SelectColumnsArgs(C.Structure):         # vbnn_select_columns_args
+    _fields_ = [("x", _vp), ("ld", _i64), ("R", _i64), ("D", _i64), ("Q", C.c_int32), ("reserved", C.c_int32), ("k", _i64 * 8),
+                ("tau", _vp), ("ld_tau", _i64), ("counts", _vp), ("n_nan", _vp)]
+
+
+SELECT_COLUMNS_MAX_Q = 8              # VBNN_SELECT_COLUMNS_MAX_Q
+
+
 class ReluMomentsArgs(C.Structure):   # vbnn_relu_moments_args
     _fields_ = [("m", _vp), ("ld_m", _i64), ("v1", _vp), ("v2", _vp), ("ld_v", _i64), ("N", _i64), ("O", _i64),
                 ("a", _vp), ("q", _vp), ("c", _vp), ("ld_out", _i64)]
@@ -344,6 +360,8 @@ _SIGS = {
     "vbnn_predict_calibration": ([_vp, C.POINTER(CalibrationArgs)], _i),
     "vbnn_selective": ([_vp, C.POINTER(SelectiveArgs)], _i),
     "vbnn_conformal": ([_vp, C.POINTER(ConformalArgs)], _i),
+    "vbnn_conformal_interval": ([_vp, C.POINTER(ConformalIntervalArgs)], _i),
+    "vbnn_select_columns": ([_vp, C.POINTER(SelectColumnsArgs)], _i),
     "vbnn_top_rows_workspace_bytes": ([_i64, C.c_int32, C.POINTER(C.c_size_t)], _i),
     "vbnn_top_rows": ([_vp, C.POINTER(TopRowsArgs)], _i),
     "vbnn_kcentre_workspace_bytes": ([_i64, _i64, C.c_int32, C.POINTER(C.c_size_t)], _i),

@@ -29,7 +29,8 @@ from .pruning import PruneResult, SparsePruneResult, UnitPruneResult, _Pruning  
 from .checkpoint import CheckpointError, _Checkpoint, digest      # noqa: F401
 from .acquisition import AcquireResult, SpreadResult, _Acquisition      # noqa: F401
 from .ranking import RankingResult, _Ranking      # noqa: F401
-from .conformal import ConformalCalibration, ConformalResult, _Conformal      # noqa: F401
+from .conformal import (ConformalCalibration, ConformalResult, IntervalCalibration, IntervalResult,    # noqa: F401
+                        _Conformal)
 
 
 _NULL_CM = contextlib.nullcontext()

@@ -38,6 +38,13 @@ minibatch's probs and targets on the device, calibrates split conformal predicti
 (FusedMLP.conformal_sets), `dev_cov@<level>` (the fraction of sets that hold the target; at least the level in expectation)
 and `dev_set_size@<level>` (the mean number of classes in a set).
 
+opt.conformal_interval_levels = [level, ...] (off by default) with opt.predictive and a regression criterion ("mse" / "gauss"):
+the dev pass keeps each minibatch's result and targets on the device, calibrates split conformal intervals on the FIRST half of the
+dev rows (FusedMLP.conformal_calibrate_intervals; opt.conformal_interval_score = "scaled" by default, "absolute", or "cqr", which
+needs opt.quantile_probs to hold both probabilities of every level; opt.conformal_interval_scope = "per_output" by default, or
+"joint") and logs, from the intervals of the SECOND half (FusedMLP.conformal_intervals), `dev_icov@<level>` (the fraction of the
+targets inside their interval; at least the level in expectation) and `dev_iwidth@<level>` (the mean width hi - lo).
+
 opt.criterion = "bce" (the Bernoulli likelihood: multi-label classification, binary with one label): targets are R x D fp32
 labels, the accuracy is the label accuracy 100 correct / (rows S D), and with opt.predictive the dev pass calls
 FusedMLP.predict_labels and logs `devll_pred` (the joint log-likelihood of a row's label vector), `dev_label_acc`,
@@ -192,6 +199,19 @@ class Main:
         # on the second (FusedMLP.conformal_calibrate / conformal_sets): `dev_cov@<level>`, `dev_set_size@<level>`
         conf_levels = [float(v) for v in (opt.get("conformal_levels") or [])] if (opt.get("predictive") and not regression and criterion != "bce") else []
         conf_probs, conf_targets = [], []
+        # opt.conformal_interval_levels (off by default) with a regression predictive: calibrated on the first half of the dev rows,
+        # measured on the second (FusedMLP.conformal_calibrate_intervals / conformal_intervals): `dev_icov@<level>`,
+        # `dev_iwidth@<level>`
+        ci_levels = [float(v) for v in (opt.get("conformal_interval_levels") or [])] if (opt.get("predictive") and regression) else []
+        ci_score = opt.get("conformal_interval_score") or "scaled"
+        ci_results, ci_targets = [], []
+        if ci_levels:                                        # refused here, not after a pass of predictions
+            from .conformal import check_interval_options
+            if ci_score == "cqr" and analytic:
+                raise ValueError("opt.conformal_interval_score = 'cqr' needs the sampled predictive (opt.predictive = True): "
+                                 "predict_analytic has no quantiles")
+            check_interval_options("opt.conformal_interval_levels", ci_levels, ci_score, opt.get("conformal_interval_scope") or "per_output",
+                                   torch.tensor(qprobs, dtype=torch.float32).tolist() if ci_score == "cqr" else None)
         for t0 in starts:
             inputs, targets = dataset.create_minibatch(t0, bs, n, opt.get("geometry"))
             x, t = self._to_device(inputs, targets)
@@ -225,6 +245,9 @@ class Main:
                     pred["devll_pred"] += r.log_lik
                 if "dev_noise_var" in pred:
                     pred["dev_noise_var"] += r.mean_noise_var
+                if ci_levels:
+                    ci_results.append(qr if (qprobs and not analytic) else r)
+                    ci_targets.append(t)
             elif opt.get("predictive"):    # the S-draw model average on the same minibatch (its own draws, after test()'s)
                 if analytic:
                     r = net.predict_analytic(x, targets=t, keep_probs=bool(cal_bins) or ranking or bool(conf_levels))
@@ -262,6 +285,18 @@ class Main:
                 for lv, cov, sz in zip(conf_levels, cs.coverage, cs.mean_size):
                     self.predictive[f"dev_cov@{lv:g}"] = cov
                     self.predictive[f"dev_set_size@{lv:g}"] = sz
+        if ci_levels and ci_results:
+            from .conformal import split_rows
+            h = sum(t.shape[0] for t in ci_targets) // 2
+            if h >= 1:
+                (r1, t1), (r2, t2) = split_rows(ci_results, ci_targets, h)
+                ic = net.conformal_calibrate_intervals(r1, t1, levels=ci_levels, score=ci_score,
+                                                       scope=opt.get("conformal_interval_scope") or "per_output",
+                                                       noise_var=(tau2 or None) if (criterion == "mse" and ci_score == "scaled") else None)
+                ir = net.conformal_intervals(r2, ic, targets=t2)
+                for lv, cov, wd in zip(ci_levels, ir.coverage, ir.mean_width):
+                    self.predictive[f"dev_icov@{lv:g}"] = cov
+                    self.predictive[f"dev_iwidth@{lv:g}"] = wd
         return accuracy / len(starts), error / len(starts)
 
     def _prune_series(self, testSet):
@@ -336,7 +371,7 @@ class Main:
                     if k in rec:
                         self.log.add(k, rec[k])
                 for k in rec:
-                    if k in ("pruned count", "pruned var mean", "held fraction") or k.startswith(("devacc_pruned@", "dev_cal@", "dev_acc@cov", "dev_cov@", "dev_set_size@")):
+                    if k in ("pruned count", "pruned var mean", "held fraction") or k.startswith(("devacc_pruned@", "dev_cal@", "dev_acc@cov", "dev_cov@", "dev_set_size@", "dev_icov@", "dev_iwidth@")):
                         self.log.add(k, rec[k])
                 self.log.flush()
                 self.save()                                                                # main.lua:181
