@@ -34,10 +34,11 @@ def same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
-def run_conformal(probs, target, kind, qhat, layout="dense", outputs=OUT_KEYS, acc=None, with_acc=True):
+def run_conformal(probs, target, kind, qhat, layout="dense", outputs=OUT_KEYS, acc=None, with_acc=True, ctx=None):
     """vbnn_conformal on NumPy arrays. layout: dense; padded (16-byte rows, NaN in every pad column); odd (pitch C + 3); offset
     (the base one float past a 16-byte boundary). Every output starts as a sentinel (NaN / -7 / 0xdeadbeef); acc: the
-    accumulator's words before the call (zero without). Returns the outputs asked for and acc as uint64."""
+    accumulator's words before the call (zero without). Returns the outputs asked for and acc as uint64. ctx: a context
+    handle of the caller's (its stream is its own: the uploads are awaited before the call and vbnn_sync after) in place of the default one."""
     from vbnn_amd import _lib as L
     from vbnn_amd.nn import Context, _p
     R, Cn = probs.shape
@@ -58,7 +59,11 @@ def run_conformal(probs, target, kind, qhat, layout="dense", outputs=OUT_KEYS, a
     qd = dev(qhat) if Q else None
     a = L.ConformalArgs(probs=buf.data_ptr() + 4 * offset, ld=ld, target=_p(td), R=R, C=Cn, kind=kind, Q=Q, qhat=_p(qd),
                         acc=_p(accd), **{k: _p(v) for k, v in out.items()})
-    L.check(L.lib().vbnn_conformal(Context.get().h, C.byref(a)))
+    if ctx is not None:
+        torch.cuda.synchronize()
+    L.check(L.lib().vbnn_conformal(ctx or Context.get().h, C.byref(a)))
+    if ctx is not None:
+        L.check(L.lib().vbnn_sync(ctx))
     got = {k: host(v) for k, v in out.items()}
     if "member" in got:
         got["member"] = got["member"].view(np.uint32)

@@ -185,13 +185,14 @@ def test_criterion_argument_errors():
 
 
 # ------------------------------------------------------------------------------------------------ the moments kernel
-def run_gmoments(y, t, form, ld_y=None, ld_t=None, y_offset=0, s_min=S_MIN, s_max=S_MAX, totals=True, draw_nll=False):
+def run_gmoments(y, t, form, ld_y=None, ld_t=None, y_offset=0, s_min=S_MIN, s_max=S_MAX, totals=True, draw_nll=False, ctx=None):
     """vbnn_predict_gauss_moments on y (S x R x 2 D fp32 NumPy) and t (R x D or None): STACKED in one call, ACCUMULATE in S calls
     over a state that starts as NaN (draw 0 must not read it). Returns the outputs as NumPy arrays (+ "totals": 5 floats).
-    draw_nll: also "nll" (S x R), every draw's nll_s as the per-draw device function leaves it in the state of a draw-0 call."""
+    draw_nll: also "nll" (S x R), every draw's nll_s as the per-draw device function leaves it in the state of a draw-0 call. ctx: a context handle of the
+    caller's (its stream is its own: the uploads are awaited before the calls and vbnn_sync after) in place of the default one."""
     from vbnn_amd import _lib as L
     from vbnn_amd.nn import Context, _p
-    lib, ctx = L.lib(), Context.get().h
+    lib, own, ctx = L.lib(), ctx is not None, ctx or Context.get().h
     S, R, W = y.shape
     D = W // 2
     ld_y, ld_t = ld_y or W, ld_t or D
@@ -206,12 +207,16 @@ def run_gmoments(y, t, form, ld_y=None, ld_t=None, y_offset=0, s_min=S_MIN, s_ma
                            state=_p(state), mean=_p(out["mean"]), var=_p(out["var"]), noise_var=_p(out["noise_var"]), ld_out=D,
                            row_var=_p(out["row_var"]), row_noise_var=_p(out["row_noise_var"]),
                            row_sq_err=_p(out.get("row_sq_err")), row_log_lik=_p(out.get("row_log_lik")), totals=_p(tot))
+    if own:
+        torch.cuda.synchronize()
     if form == L.MOMENTS_STACKED:
         L.check(lib.vbnn_predict_gauss_moments(ctx, C.byref(a)))
     else:
         for s in range(S):
             a.y, a.draw = yptr + 4 * s * R * ld_y, s
             L.check(lib.vbnn_predict_gauss_moments(ctx, C.byref(a)))
+    if own:
+        L.check(lib.vbnn_sync(ctx))
     got = {k: host(v) for k, v in out.items()}
     if tot is not None:
         got["totals"] = host(tot).tolist()
@@ -223,6 +228,8 @@ def run_gmoments(y, t, form, ld_y=None, ld_t=None, y_offset=0, s_min=S_MIN, s_ma
         for s in range(S):
             b.y = yptr + 4 * s * R * ld_y
             L.check(lib.vbnn_predict_gauss_moments(ctx, C.byref(b)))
+            if own:
+                L.check(lib.vbnn_sync(ctx))
             sth = host(st)
             nll[s] = sth[:, 3 * D]
             assert same_bits(sth[:, 3 * D + 1], -nll[s])               # draw 0 sets L = -nll_0

@@ -191,13 +191,14 @@ def test_criterion_argument_errors():
 
 
 # ------------------------------------------------------------------------------------------------ the moments kernel
-def run_lmoments(y, t, form, ld_y=None, ld_t=None, ld_o=None, y_offset=0, t_offset=0, totals=True):
+def run_lmoments(y, t, form, ld_y=None, ld_t=None, ld_o=None, y_offset=0, t_offset=0, totals=True, ctx=None):
     """vbnn_predict_label_moments on y (S x R x D fp32 NumPy) and t (R x D or None): STACKED in one call, ACCUMULATE in S calls
     over a state that starts as NaN (draw 0 must not read it). Returns the outputs as NumPy arrays (+ "totals": 5 floats,
-    "pads": the spare columns of the three R x ld_o outputs)."""
+    "pads": the spare columns of the three R x ld_o outputs). ctx: a context handle of the
+    caller's (its stream is its own: the uploads are awaited before the calls and vbnn_sync after) in place of the default one."""
     from vbnn_amd import _lib as L
     from vbnn_amd.nn import Context, _p
-    lib, ctx = L.lib(), Context.get().h
+    lib, own, ctx = L.lib(), ctx is not None, ctx or Context.get().h
     S, R, D = y.shape
     ld_y, ld_t, ld_o = ld_y or D, ld_t or D, ld_o or D
     ybuf, yptr = _padded(y.reshape(S * R, D), ld_y, y_offset)
@@ -211,12 +212,16 @@ def run_lmoments(y, t, form, ld_y=None, ld_t=None, ld_o=None, y_offset=0, t_offs
     state = torch.full((R, 3 * D + 2), float("nan"), **f32) if form == L.MOMENTS_ACCUMULATE else None
     a = L.LabelMomentsArgs(y=yptr, ld_y=ld_y, target=tptr, ld_t=ld_t, R=R, D=D, S=S, form=form, state=_p(state), ld_out=ld_o,
                            totals=_p(tot), **{k: _p(v) for k, v in out.items()})
+    if own:
+        torch.cuda.synchronize()
     if form == L.MOMENTS_STACKED:
         L.check(lib.vbnn_predict_label_moments(ctx, C.byref(a)))
     else:
         for s in range(S):
             a.y, a.draw = yptr + 4 * s * R * ld_y, s
             L.check(lib.vbnn_predict_label_moments(ctx, C.byref(a)))
+    if own:
+        L.check(lib.vbnn_sync(ctx))
     got = {k: host(v) for k, v in out.items()}
     got["pads"] = np.stack([got[k][:, D:] for k in ELEM_KEYS])
     for k in ELEM_KEYS:

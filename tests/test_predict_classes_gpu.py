@@ -45,13 +45,14 @@ def _padded(a2d, ld, offset=0):
     return buf, buf.data_ptr() + 4 * offset
 
 
-def run_classes(y, t, form, K=0, ld_y=None, y_offset=0, probs=True, ld_state=None, n_calls=None):
+def run_classes(y, t, form, K=0, ld_y=None, y_offset=0, probs=True, ld_state=None, n_calls=None, ctx=None):
     """vbnn_predict_class_moments on y (S x R x C fp32 NumPy) and t (R int32 or None): STACKED in one call, ACCUMULATE in S calls
     over a state that starts as NaN (draw 0 must not read it). Returns the outputs as NumPy arrays (+ "totals": 5 floats, and for
-    ACCUMULATE "rows": the state's three row values, "L": its R x C running logsumexp; n_calls: only that many draws are run)."""
+    ACCUMULATE "rows": the state's three row values, "L": its R x C running logsumexp; n_calls: only that many draws are run). ctx: a context handle of the
+    caller's (its stream is its own: the uploads are awaited before the calls and vbnn_sync after) in place of the default one."""
     from vbnn_amd import _lib as L
     from vbnn_amd.nn import Context, _p
-    lib, ctx = L.lib(), Context.get().h
+    lib, own, ctx = L.lib(), ctx is not None, ctx or Context.get().h
     S, R, Cn = y.shape
     ld_y = ld_y or Cn
     ybuf, yptr = _padded(y.reshape(S * R, Cn), ld_y, y_offset)
@@ -71,12 +72,16 @@ def run_classes(y, t, form, K=0, ld_y=None, y_offset=0, probs=True, ld_state=Non
                            probs=_p(out.get("probs")), log_probs=_p(out.get("log_probs")), ld_out=Cn, entropy=_p(out["entropy"]),
                            expected_entropy=_p(out["expected_entropy"]), mutual_info=_p(out["mutual_info"]), pred=_p(out["pred"]),
                            topk_idx=_p(out.get("topk_idx")), topk_prob=_p(out.get("topk_prob")), totals=_p(tot))
+    if own:
+        torch.cuda.synchronize()
     if form == L.MOMENTS_STACKED:
         L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a)))
     else:
         for s in range(S if n_calls is None else n_calls):
             a.y, a.draw = yptr + 4 * s * R * ld_y, s
             L.check(lib.vbnn_predict_class_moments(ctx, C.byref(a)))
+    if own:
+        L.check(lib.vbnn_sync(ctx))
     got = {k: host(v) for k, v in out.items()}
     if tot is not None:
         got["totals"] = host(tot).tolist()

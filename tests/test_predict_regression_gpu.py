@@ -42,12 +42,13 @@ def _padded(a2d, ld, offset=0):
     return buf, buf.data_ptr() + 4 * offset
 
 
-def run_moments(y, t, form, noise_var=0.0, ld_y=None, ld_t=None, y_offset=0, want=ROW_KEYS, totals=True):
+def run_moments(y, t, form, noise_var=0.0, ld_y=None, ld_t=None, y_offset=0, want=ROW_KEYS, totals=True, ctx=None):
     """vbnn_predict_moments on y (S x R x D fp32 NumPy) and t (R x D or None): STACKED in one call, ACCUMULATE in S calls over a
-    state that starts as NaN (draw 0 must not read it). Returns the outputs as NumPy arrays (+ "totals": 4 floats)."""
+    state that starts as NaN (draw 0 must not read it). Returns the outputs as NumPy arrays (+ "totals": 4 floats). ctx: a context handle of the
+    caller's (its stream is its own: the uploads are awaited before the calls and vbnn_sync after) in place of the default one."""
     from vbnn_amd import _lib as L
     from vbnn_amd.nn import Context, _p
-    lib, ctx = L.lib(), Context.get().h
+    lib, own, ctx = L.lib(), ctx is not None, ctx or Context.get().h
     S, R, D = y.shape
     ld_y, ld_t = ld_y or D, ld_t or D
     ybuf, yptr = _padded(y.reshape(S * R, D), ld_y, y_offset)
@@ -62,12 +63,16 @@ def run_moments(y, t, form, noise_var=0.0, ld_y=None, ld_t=None, y_offset=0, wan
     a = L.MomentsArgs(y=yptr, ld_y=ld_y, target=tptr, ld_t=ld_t, R=R, D=D, S=S, form=form, noise_var=noise_var, state=_p(state),
                       mean=_p(out.get("mean")), var=_p(out.get("var")), ld_out=D, row_var=_p(out.get("row_var")),
                       row_sq_err=_p(out.get("row_sq_err")), row_log_lik=_p(out.get("row_log_lik")), totals=_p(tot))
+    if own:
+        torch.cuda.synchronize()
     if form == L.MOMENTS_STACKED:
         L.check(lib.vbnn_predict_moments(ctx, C.byref(a)))
     else:
         for s in range(S):
             a.y, a.draw = yptr + 4 * s * R * ld_y, s
             L.check(lib.vbnn_predict_moments(ctx, C.byref(a)))
+    if own:
+        L.check(lib.vbnn_sync(ctx))
     got = {k: host(v) for k, v in out.items()}
     if tot is not None:
         got["totals"] = host(tot).tolist()

@@ -38,6 +38,17 @@ def _lib():
     return L, L.lib(), Context.get().h
 
 
+def _call(name, ctx, *args):
+    """One checked call of an entry point, on the default context or on a context handle of the caller's: that one's stream is its
+    own, so the uploads are awaited before the call and vbnn_sync after."""
+    L, lib, own = _lib()
+    if ctx is not None:
+        torch.cuda.synchronize()
+    L.check(getattr(lib, name)(ctx or own, *args))
+    if ctx is not None:
+        L.check(lib.vbnn_sync(ctx))
+
+
 def _placed(a2d, ld, offset, dtype=torch.float32, fill=float("nan")):
     """a2d (rows x cols) on the device with row pitch ld, `fill` in every pad, starting `offset` ELEMENTS past a 16-byte boundary.
     Returns (the owning tensor, the view of the rows x ld block, the data pointer of element [0, 0])."""
@@ -64,15 +75,15 @@ def relu_inputs(N, O, seed=7):
     return m, v1, v2
 
 
-def run_relu(m, v1, v2, dtype, ld_in, ld_out, in_off=0, out_off=0, want="aqc"):
+def run_relu(m, v1, v2, dtype, ld_in, ld_out, in_off=0, out_off=0, want="aqc", ctx=None):
     """vbnn_relu_moments; returns {name: N x ld_out float array of the WHOLE packed block (pads included)}."""
-    L, lib, ctx = _lib()
+    L = _lib()[0]
     N, O = m.shape
     keep = [_placed(t, ld_in, in_off) for t in ((m, v1) if v2 is None else (m, v1, v2))]
     outs = {k: _placed(np.zeros((N, O), np.float32), ld_out, out_off, TDT[dtype], fill=0.0) for k in want}
     a = L.ReluMomentsArgs(m=keep[0][2], ld_m=ld_in, v1=keep[1][2], v2=keep[2][2] if v2 is not None else None, ld_v=ld_in, N=N, O=O,
                           ld_out=ld_out, **{k: outs[k][2] for k in want})
-    L.check(lib.vbnn_relu_moments(ctx, L.F32 if dtype == "f32" else L.BF16, C.byref(a)))
+    _call("vbnn_relu_moments", ctx, L.F32 if dtype == "f32" else L.BF16, C.byref(a))
     got = {k: host(outs[k][1]) for k in want}
     for k in want:                                             # nothing outside the block either
         assert not host(outs[k][0][:out_off]).any() and not host(outs[k][0][out_off + N * ld_out:]).any(), k
@@ -168,7 +179,12 @@ def test_relu_moments_refuses_bad_arguments():
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("rows,cols", [(1, 1), (3, 5), (7, 64), (5, 67), (33, 130)])
 def test_square_shadow_is_bitwise_the_restatement(rows, cols, dtype, off):
-    L, lib, ctx = _lib()
+    check_square_shadow(rows, cols, dtype, off)
+
+
+def check_square_shadow(rows, cols, dtype, off, ctx=None):
+    """The whole check of one shape; returns the destination block as the device left it."""
+    L, lib, own = _lib()
     g = np.random.default_rng(rows * 1000 + cols)
     src = (g.standard_normal((rows, cols)) * 10.0 ** g.uniform(-3, 2, (rows, cols))).astype(np.float32)
     src[0, 0] = 0.0
@@ -177,15 +193,16 @@ def test_square_shadow_is_bitwise_the_restatement(rows, cols, dtype, off):
     ld = (cols + 63) // 64 * 64 + (1 if off else 0)            # (off: an odd pitch off the 16-byte boundary -- element by element)
     sbuf, sview, sptr = _placed(src, ld, off, TDT[dtype])
     dbuf, dview, dptr = _placed(np.full((rows, cols), 5.0, np.float32), ld + 64, off, TDT[dtype], fill=7.0)
-    L.check(lib.vbnn_square_shadow(ctx, L.F32 if dtype == "f32" else L.BF16, sptr, ld, rows, cols, dptr, ld + 64))
+    _call("vbnn_square_shadow", ctx, L.F32 if dtype == "f32" else L.BF16, sptr, ld, rows, cols, dptr, ld + 64)
     want = src * src
     if dtype == "bf16":
         want = bf16_round(want)
     got = host(dview)
     assert same_bits(got[:, :cols].astype(np.float32), want.astype(np.float32))
     assert (got[:, cols:] == 7.0).all() and (host(dbuf[:off]) == 7.0).all() and (host(dbuf[off + rows * (ld + 64):]) == 7.0).all()
-    assert lib.vbnn_square_shadow(ctx, L.F32 if dtype == "f32" else L.BF16, sptr, cols - 1, rows, cols, dptr, ld + 64) == 1   # ld_src < cols
+    assert lib.vbnn_square_shadow(ctx or own, L.F32 if dtype == "f32" else L.BF16, sptr, cols - 1, rows, cols, dptr, ld + 64) == 1   # ld_src < cols
     torch.cuda.synchronize()
+    return got
 
 
 # ------------------------------------------------------------------------------------------------ vbnn_logit_draws
@@ -202,8 +219,8 @@ def restated_draws(m, v, S, layer, draw, row0, seed=SEED):
     return np.stack([m + np.sqrt(v) * device_normals(R, Cn, layer, draw + s, row0, seed) for s in range(S)]).astype(np.float32)
 
 
-def run_draws(m, v, S, layer, draw, row0, ld_y=None, stride=None, off=0):
-    L, lib, ctx = _lib()
+def run_draws(m, v, S, layer, draw, row0, ld_y=None, stride=None, off=0, ctx=None):
+    L = _lib()[0]
     R, Cn = m.shape
     ld_y = ld_y or Cn
     stride = stride or R * ld_y
@@ -211,7 +228,7 @@ def run_draws(m, v, S, layer, draw, row0, ld_y=None, stride=None, off=0):
     buf = torch.full((S * stride + off + 8,), 9.0, dtype=torch.float32, device="cuda")
     a = L.LogitDrawsArgs(m=C.c_void_p(md.data_ptr()), ld_m=Cn, v=C.c_void_p(vd.data_ptr()), ld_v=Cn, R=R, C=Cn, S=S, seed=SEED,
                          layer=layer, draw=draw, row0=row0, y=C.c_void_p(buf.data_ptr() + 4 * off), ld_y=ld_y, draw_stride=stride)
-    L.check(lib.vbnn_logit_draws(ctx, C.byref(a)))
+    _call("vbnn_logit_draws", ctx, C.byref(a))
     full = host(buf)
     y = np.stack([full[off + s * stride:off + s * stride + R * ld_y].reshape(R, ld_y) for s in range(S)])
     touched = np.zeros(full.shape, bool)

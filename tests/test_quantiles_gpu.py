@@ -37,15 +37,16 @@ def normal(shape, seed):
 
 
 def run_quantiles(y, p, kind, t=None, ld_y=None, y_offset=0, gap=0, ld_q=None, ld_t=None, rows=None, count=None, raw=None,
-                  noise_var=0.0, s_min=0.0, s_max=0.0):
+                  noise_var=0.0, s_min=0.0, s_max=0.0, ctx=None):
     """vbnn_predict_quantiles on y (S x R x W fp32 NumPy; W = D, GAUSS: 2 D) and t (R x D or None). The draws sit on the device
     with row pitch ld_y and `gap` floats between draws, NaN in every pad, the gaps and around, starting y_offset floats past a
     16-byte boundary. rows = (r0, r1): the call works that row range of the same buffer (draw_stride stays the whole draw's).
-    count: the int64 device tensor the call adds to (a zeroed one by default). raw: argument overrides (the error tests).
+    count: the int64 device tensor the call adds to (a zeroed one by default). raw: argument overrides (the error tests). ctx: a context handle of the
+    caller's (its stream is its own: the uploads are awaited before the call and vbnn_sync after) in place of the default one.
     Returns (status, dict of NumPy outputs + the pads of q)."""
     from vbnn_amd import _lib as L
     from vbnn_amd.nn import Context, _p
-    lib, ctx = L.lib(), Context.get().h
+    lib, own, ctx = L.lib(), ctx is not None, ctx or Context.get().h
     S, R, W = y.shape
     D = W // 2 if kind == Q.GAUSS else W
     ld_y, ld_q, ld_t = ld_y or W, ld_q or D, ld_t or D
@@ -75,7 +76,11 @@ def run_quantiles(y, p, kind, t=None, ld_y=None, y_offset=0, gap=0, ld_q=None, l
         a.row_le, a.count_le = C.c_void_p(row_le.data_ptr() + 4 * r0 * Qn), _p(count)
     for k, v in (raw or {}).items():
         setattr(a, k, v)
+    if own:
+        torch.cuda.synchronize()
     status = lib.vbnn_predict_quantiles(ctx, C.byref(a))
+    if own:
+        L.check(lib.vbnn_sync(ctx))
     qh = host(qbuf).reshape(Qn, plane)
     planes = qh[:, :R * ld_q].reshape(Qn, R, ld_q)
     out = dict(q=np.ascontiguousarray(planes[:, :, :D]), q_pads=np.concatenate([planes[:, :, D:].ravel(), qh[:, R * ld_q:].ravel()]),
