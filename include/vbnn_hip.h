@@ -814,7 +814,11 @@ int vbnn_head_forward_backward(vbnn_ctx* ctx, int dtype, const vbnn_head_args* a
  *   L[c] = logsumexp over the draws so far of o_s[c] (online; never a sum of probabilities, which underflow),
  *   sum_s H(p_s) with H(p_s) = -sum_c exp(o_s[c]) o_s[c],  sum_s -o_s[t_r],  sum_s [argmax o_s = t_r].
  * The finish, per row: log p = L - log S, p = exp(log p), entropy = H[p], expected_entropy = sum_s H(p_s) / S,
- * mutual_info = entropy - expected_entropy (the epistemic part), pred = argmax p (first maximum). */
+ * mutual_info = entropy - expected_entropy (the epistemic part), pred = argmax p (first maximum).
+ * Logits are finite or NaN. A NaN logit in any draw of a row (a NaN in h reaches every class of its row) makes every float
+ * output of that row NaN -- probs, log_probs, entropy, expected_entropy, mutual_info -- and the float totals ([0] and [2]) NaN,
+ * and leaves every other row bit for bit alone; the online logsumexp keeps a NaN, as vbnn_predict_class_moments' does. Such a
+ * row is no hit in totals [1], its NaN draw none in [3]; its pred is unspecified but inside [0, C - 1]. */
 enum { VBNN_PREDICT_STACKED = 0, VBNN_PREDICT_ACCUMULATE = 1 };
 typedef struct vbnn_predict_args {
     const void* h; int64_t ld_h;            /* packed input of the final Linear (dtype): S x R rows (STACKED) or R rows (ACCUMULATE) */

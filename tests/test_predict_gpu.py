@@ -290,6 +290,44 @@ def test_training_is_undisturbed(oracle):
     assert torch.equal(ga, gb) and la == lb and ca == cb and da == db
 
 
+@pytest.mark.parametrize("stacked", [True, False])
+def test_a_nan_activation_row_is_nan_in_the_result_and_counted_by_calibration(oracle, stacked):
+    """The head's NaN contract (include/vbnn_hip.h) seen from the engine: one NaN in the head's input, in row 5 of the middle
+    draw of three. The NaN is written into the head's operand after the draw's forward -- an input NaN never gets there: the
+    ReLU between the layers is fmaxf(y, 0), Threshold's x > 0 ? x : 0, which gives 0 for a NaN. That row's probs are NaN, every
+    other row is bitwise the clean call's, and calibration() skips and counts exactly that row."""
+    from vbnn_amd.engine import FusedMLP
+    R, S, row = 37, 3, 5
+    x, t = inputs(oracle, R, 70)
+    x, t = dev(x), dev(t)
+    clean_eng, eng = (FusedMLP(opt_for("lrt", input_size=70, hidden=[50, 34], predict_stacked=stacked)) for _ in range(2))
+    clean_eng.prepare(); eng.prepare()
+    clean = clean_eng.predict(x, S=S, targets=t)
+    forward = eng._draw_forward
+
+    def poisoned(p, xc, rows, c0, s=None):
+        forward(p, xc, rows, c0, s)
+        h = p.bufs[len(eng.vb)].x.t                              # the head's operand: draw s of row r at s rows + r when stacked
+        if s is None:
+            h[1 * rows + row, 3] = float("nan")
+        elif s == 1:
+            h[row, 3] = float("nan")
+    eng._draw_forward = poisoned
+    res = eng.predict(x, S=S, targets=t)
+    assert res.stacked == stacked == clean.stacked
+    others = torch.arange(R, device="cuda") != row
+    for k in ("probs", "log_probs", "entropy", "expected_entropy", "mutual_info"):
+        got, want = getattr(res, k), getattr(clean, k)
+        assert bool(torch.isnan(got[row]).all()), (k, got[row])
+        assert torch.equal(got[others], want[others]), k
+    assert 0 <= int(res.pred[row]) < 10 and torch.equal(res.pred[others], clean.pred[others])
+    assert math.isnan(res.nll) and math.isnan(res.mean_draw_nll)
+    hit = int(clean.pred[row]) == int(t[row])
+    assert abs(res.accuracy - (clean.accuracy - 100.0 * hit / R)) <= 1e-9
+    cal, cal_clean = eng.calibration(res, t), clean_eng.calibration(clean, t)
+    assert (cal.n_nan, cal.n) == (1, R - 1) and (cal_clean.n_nan, cal_clean.n) == (0, R)
+
+
 def test_errors():
     from vbnn_amd import _lib as L
     from vbnn_amd.engine import FusedMLP

@@ -306,10 +306,11 @@ __device__ __forceinline__ float head_row_entropy(const float (&o)[4], int q, in
     return -e;
 }
 
-// log(exp(a) + exp(b)) without leaving the log domain (the draws' probabilities underflow where their logs do not)
+// log(exp(a) + exp(b)) without leaving the log domain (the draws' probabilities underflow where their logs do not). A NaN
+// passes through the |a - b| term, as in the moments family: fmaxf / fminf return the operand that is NOT a NaN, so the earlier
+// form on fminf(a, b) - fmaxf(a, b) -- the same bits for every other pair of operands -- folded a NaN draw in as L + log 2.
 __device__ __forceinline__ float head_logaddexp(float a, float b) {
-    const float m = fmaxf(a, b);
-    return m + log1pf(expf(fminf(a, b) - m));
+    return fmaxf(a, b) + log1pf(expf(-fabsf(a - b)));
 }
 
 // vbnn_head_predict: one workgroup per 16 minibatch rows walks `draws` draws of them in order (draw s = operand rows s R + r).
@@ -415,7 +416,7 @@ __global__ __launch_bounds__(64 * HEAD_FW) void k_head_predict(const T* __restri
                 if (entropy) entropy[r] = ent;
                 if (expected_entropy) expected_entropy[r] = eH;
                 if (mutual_info) mutual_info[r] = ent - eH;
-                if (pred) pred[r] = arg;
+                if (pred) pred[r] = min(arg, C - 1);       // (a NaN row has no maximum: arg is no class and no hit below)
             }
         }
         if (totals) {
