@@ -691,7 +691,9 @@ int vbnn_relu_backward(vbnn_ctx* ctx, const float* x, const float* g, float* gx,
  *   g_logits = (exp(out) - onehot) * inv_n     (= LogSoftMax:backward(ClassNLL:backward)).
  * inv_n = 1 / (global minibatch rows). Targets are 0-based int32. A target outside [0, C - 1] is clamped into it (a negative
  * one counts as class 0, one past the end as class C - 1) for the loss, the gradient and the hit count alike: such a row
- * is never read out of bounds and is never dropped. Of equal maxima the first (lowest class) is the arg-max. */
+ * is never read out of bounds and is never dropped. Of equal maxima the first (lowest class) is the arg-max. The launch's
+ * loss is formed in double in a fixed order (block partials + one finish block, no float atomics) and then added to
+ * loss_sum_dev[0]: bitwise reproducible. */
 int vbnn_logsoftmax_nll(vbnn_ctx* ctx, const float* logits, int64_t ld, const int32_t* target,
                         int64_t N, int64_t C, float inv_n, float* out, float* g_logits,
                         double* loss_sum_dev, int32_t* correct_dev);

@@ -515,7 +515,8 @@ extern "C" int vbnn_relu_backward(vbnn_ctx* ctx, const float* x, const float* g,
 // one wave per row; C <= 64 * 16.
 __global__ __launch_bounds__(256) void k_logsoftmax_nll(const float* __restrict__ logits, int64_t ld,
                                                         const int32_t* __restrict__ target, int64_t N, int64_t C, float inv_n,
-                                                        float* out, float* g_logits, double* loss_sum, int32_t* correct) {
+                                                        float* out, float* g_logits, double* partial, int32_t* correct) {
+    __shared__ double sh[4];
     const int lane = threadIdx.x & 63;
     const int64_t wave_global = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * 4;
@@ -547,10 +548,21 @@ __global__ __launch_bounds__(256) void k_logsoftmax_nll(const float* __restrict_
             corr_acc += (arg == t) ? 1 : 0;
         }
     }
-    if (lane == 0) {
-        if (loss_sum && loss_acc != 0.0) atomicAdd(loss_sum, loss_acc);
-        if (correct && corr_acc) atomicAdd(correct, corr_acc);
+    // the loss: workgroup partials in double, added by one finish block in a fixed order (a double atomicAdd per wave summed in
+    // arrival order: the loss differed in its last bits from run to run); the hit count is an integer, its atomic is exact
+    if (partial) {
+        const double r = vbnn_block_sum256(lane == 0 ? loss_acc : 0.0, sh);
+        if (threadIdx.x == 0) partial[blockIdx.x] = r;
     }
+    if (lane == 0 && correct && corr_acc) atomicAdd(correct, corr_acc);
+}
+// loss[0] += the partials in index order (every launch above adds its rows' losses to the caller's accumulator)
+__global__ __launch_bounds__(256) void k_nll_loss_finish(const double* partial, int nb, double* loss) {
+    __shared__ double sh[4];
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 256) a += partial[b];
+    const double r = vbnn_block_sum256(a, sh);
+    if (threadIdx.x == 0) loss[0] += r;
 }
 extern "C" int vbnn_logsoftmax_nll(vbnn_ctx* ctx, const float* logits, int64_t ld, const int32_t* target, int64_t N,
                                    int64_t C, float inv_n, float* out, float* g_logits, double* loss_sum_dev,
@@ -558,8 +570,11 @@ extern "C" int vbnn_logsoftmax_nll(vbnn_ctx* ctx, const float* logits, int64_t l
     VBNN_API_BEGIN
     VBNN_REQUIRE(ctx && logits && target, "null argument");
     VBNN_REQUIRE(N > 0 && C > 0 && ld >= C, "shape");
-    hipLaunchKernelGGL(k_logsoftmax_nll, dim3(grid_for(N, 4)), dim3(256), 0, ctx->stream, logits, ld, target, N, C, inv_n, out,
-                       g_logits, loss_sum_dev, correct_dev);
+    const int nb = grid_for(N, 4);
+    if ((size_t)nb > ctx->scratch_doubles) { vbnn_set_error("scratch"); return VBNN_ERR_INVALID; }
+    hipLaunchKernelGGL(k_logsoftmax_nll, dim3(nb), dim3(256), 0, ctx->stream, logits, ld, target, N, C, inv_n, out,
+                       g_logits, loss_sum_dev ? ctx->scratch : nullptr, correct_dev);
+    if (loss_sum_dev) hipLaunchKernelGGL(k_nll_loss_finish, dim3(1), dim3(256), 0, ctx->stream, ctx->scratch, nb, loss_sum_dev);
     return vbnn_check_launch("k_logsoftmax_nll");
     VBNN_API_END
 }

@@ -301,7 +301,8 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint, _Acquisition, _
         self._rpd = 0            # > 0 inside run_draws: rows per Monte-Carlo draw of the stacked minibatch
         self._x_in = None        # fp32: the raw minibatch of the current run, read in place by layer 1's GEMMs
         self._draws = None
-        self._shadows_ready = False       # prepare() / update() have packed the operand shadows (predict prepares otherwise)
+        self._tgt_stack = self._tgt_key = None      # run_draws with a generic head: the stacked targets (_stacked_targets)
+        self._shadows_ready = False      # prepare() / update() have packed the operand shadows (predict prepares otherwise)
         self._pruned = None               # the pruned view predict() reads its operands from (use_pruned), or None
         self._pver = 0                    # parameter version: a pruned view is a snapshot of ONE version (prune / predict)
         self._prune_ws = None
@@ -611,6 +612,19 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint, _Acquisition, _
                       gvT_prev=vl.gvT_s.ptr if (lrt and vl.gvT_s) else None, ld_gpT=vl.gT_s.ld if vl.gT_s else 0)
         L.check(lib.vbnn_grad_input(ctx, code, C.byref(dx)))
 
+    def _stacked_targets(self, targets):
+        """run_draws with a generic head: the minibatch's targets S times over, one per operand row, in a buffer the ENGINE owns
+        (kept per draws x shape x dtype). A captured step records this buffer's address (capture_step): a temporary -- what
+        targets.repeat() made -- goes back to the caching allocator when run() returns, and every replay would then write S
+        copies of the targets into a block that may by now belong to something else. The fill is a broadcasting copy_ on the
+        engine's stream: it allocates nothing, is recorded with the step, and so every replay re-reads the caller's targets."""
+        key = (self._draws, tuple(targets.shape), targets.dtype)
+        if self._tgt_key != key:
+            self._tgt_stack = torch.empty((self._draws,) + tuple(targets.shape), dtype=targets.dtype, device=self.device)
+            self._tgt_key = key
+        self._tgt_stack.copy_(targets.unsqueeze(0).expand_as(self._tgt_stack))
+        return self._tgt_stack.view(self._draws * targets.shape[0], *targets.shape[1:])
+
     # ---- argument blocks of the three GEMM families for VB layer `li` (also used by bench.py to time
     # exactly the launches of the step in isolation)
     # The blocks are built once per (layer, batch shape, ...) and kept (the launch-bound step is ~50 us of GPU time: rebuilding
@@ -804,7 +818,7 @@ class FusedMLP(_Predictive, _Calibration, _Pruning, _Checkpoint, _Acquisition, _
                                                vl.gvT_s.ptr if (lrt and vl.gvT_s) else None, vl.gT_s.ld if vl.gT_s else 0))
         else:
             if self._rpd:                                 # (the generic criteria take one target per operand row)
-                targets = targets.repeat(self._draws) if targets.dim() == 1 else targets.repeat(self._draws, 1)
+                targets = self._stacked_targets(targets)
             self._generic_head(N, targets, inv_n, accumulate, backward)
             if not backward:
                 self._first = False
